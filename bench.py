@@ -8,8 +8,12 @@
 One "step" = one iteration of MD2/trainer.py:297-315: attack (Phy_obj_atk, 10 steps, 12 scenes) ->
 GPU-side sample synthesis -> encoder/decoder forward -> fused photometric+SSIM+smoothness loss ->
 backward -> gradient all-reduce (flat bucket, RCCL) -> Adam.  fp32 throughout, random-init ResNet-18 U-Net.
-Rank 0 prints ONE JSON line with the contract fields plus ``roofline`` (dominant K1 kernel, HIP-event timed inside
-the timed region) and ``cpu_baseline`` (the CPU oracle on bounded samples, N=1 only).
+Rank 0 prints ONE JSON line with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, config).
+A plain run sets up, warms up, times the --steps steps and prints that line, nothing else.  ``--full`` adds what takes work
+of its own: ``roofline`` (one extra fully instrumented step, the dominant K1 kernel HIP-event timed inside the timed region),
+``cpu_baseline`` (the CPU oracle on bounded samples, N=1 only) and, for N > 1, the all-reduce's HIP-event
+timings and a second timing in the other attack / all-reduce order.  ``--dump-outputs DIR`` writes what the last timed step
+computed as .npy files (dump_outputs()).
 
 Launcher: with ``--gpus N`` (N > 1) and no torchrun environment, this process starts N children (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set) BEFORE anything touches the GPU, relays rank 0's
@@ -349,7 +353,14 @@ def parse(argv=None):
     ap.add_argument("--device", type=str, default="cuda", choices=["cuda", "cpu"],
                     help="cpu: launcher / collective plumbing test only (gloo); no kernels run")
     ap.add_argument("--phases", action="store_true", help="also print a per-phase GPU-time breakdown to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (an extra instrumented step), "
+                         "cpu_baseline (N=1), and for N > 1 the all-reduce timings and the other attack / all-reduce order")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     explicit = {x.split("=")[0].lstrip("-") for x in (sys.argv[1:] if argv is None else argv) if x.startswith("--")}
     for k, v in BASELINE_CONFIGS[a.config][1].items():
         if k not in explicit:           # an explicit flag wins over the config's preset
@@ -506,24 +517,28 @@ def run_rank(a):
     # ~10 us of dispatch latency around a launch, and a step has ~1,300 instrumented launches (timing all of them cost
     # 8.5 ms of a 174 ms step).  The other kernels' durations (roofline.others) come from ONE extra, untimed, fully
     # instrumented step BEFORE the timed region (so that the timed region is the tail of a kernel trace).
-    from depthmodelhardening_amd.networks import ResnetEncoder
-    holders = list(job.models.values()) + [getattr(job, "gt_model", None)] if a.harness == "trainer" else \
-        [job.model_rob, job.model_ori]
-    encoders = {id(m): m for h in holders if h is not None for m in h.modules() if isinstance(m, ResnetEncoder)}
-    meter = FlopMeter(list(encoders.values()))
-    ops.enable_profile(True)
-    meter.on = True
+    # Without --full the step the full run instruments still runs, uninstrumented: with and without --full the timed steps
+    # start from the same state, so final_loss and --dump-outputs do not depend on the option.
+    hot = ("photo_",) if a.harness == "trainer" else ("paste_",)      # the kernels of the roofline entry carry events
+    if a.full:
+        from depthmodelhardening_amd.networks import ResnetEncoder
+        holders = list(job.models.values()) + [getattr(job, "gt_model", None)] if a.harness == "trainer" else \
+            [job.model_rob, job.model_ori]
+        encoders = {id(m): m for h in holders if h is not None for m in h.modules() if isinstance(m, ResnetEncoder)}
+        meter = FlopMeter(list(encoders.values()))
+        ops.enable_profile(True)
+        meter.on = True
     job.train_step()
     job._apply_pending_update()
     sync()
-    meter.on = False
-    kbytes = ops.profile_bytes()
-    hot = ("photo_",) if a.harness == "trainer" else ("paste_",)      # the kernels of the roofline entry carry events
-    ops.enable_profile(True, only=hot)
+    if a.full:
+        meter.on = False
+        kbytes = ops.profile_bytes()
+        ops.enable_profile(True, only=hot)
     atk = getattr(getattr(job, "dataset", None), "depth_atk", None) or getattr(job, "depth_atk", None)
     it0 = (getattr(atk, "total_iterations", 0), getattr(atk, "total_calls", 0))
     bucket = getattr(job, "bucket", None)
-    if world > 1 and bucket is not None:
+    if a.full and world > 1 and bucket is not None:
         bucket.timing = True
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -535,12 +550,17 @@ def run_rank(a):
     # the L0 attack runs atk_steps ... 2 atk_steps iterations by its patch's L0 ratio: the timed region's mean per attack
     atk_iters = round((it1[0] - it0[0]) / float(it1[1] - it0[1]), 2) if it1[1] > it0[1] else None
     note("timed region done: %.3fs for %d steps" % (elapsed, a.steps))
-    kms = {k: v for k, v in ops.profile_ms().items() if k.startswith(hot)}
-    kb_timed = ops.profile_bytes()
-    ops.enable_profile(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(job, losses, a.dump_outputs)
+        note("outputs of the last timed step written to %s" % a.dump_outputs)
+    kms, kb_timed = {}, {}
+    if a.full:
+        kms = {k: v for k, v in ops.profile_ms().items() if k.startswith(hot)}
+        kb_timed = ops.profile_bytes()
+        ops.enable_profile(False)
     other_mode = None
     ar_times = None
-    if world > 1 and bucket is not None:
+    if a.full and world > 1 and bucket is not None:
         # the side-stream all-reduce of every timed step by HIP events (this rank's; the device is idle: sync() above)
         tm = bucket.timings()
         bucket.timing = False
@@ -558,7 +578,7 @@ def run_rank(a):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        if a.harness == "trainer":
+        if a.full and a.harness == "trainer":
             # the same K steps once more in the OTHER ordering of attack and gradient exchange (both numbers in one line):
             # overlapped = the attack is enqueued before the optimiser waits for the all-reduce (weights one step stale,
             # north_star); sync_attack = the reference's strict order (results identical to the reference's)
@@ -679,15 +699,16 @@ def run_rank(a):
                           "global_batch": a.batch_size * world, "per_gpu_batch": a.batch_size, "parallelism": "dp%d" % world,
                           "attack_overlap": bool(world > 1 and not a.sync_attack and a.harness == "trainer"),
                           "attack_scenes": a.atk_scenes, "shared_patch": bool(a.shared_patch),
-                          "graph_attack": bool(a.graph_attack), "final_loss": round(loss_val, 6)},
-               "roofline": roof}
+                          "graph_attack": bool(a.graph_attack), "final_loss": round(loss_val, 6)}}
+        if a.full:
+            out["roofline"] = roof
         if atk_iters is not None:
             out["config"]["attack_iterations_per_step"] = atk_iters
         if other_mode is not None:
             out["config"]["other_order"] = other_mode
         if ar_times is not None:
             out["config"]["all_reduce"] = ar_times
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             gpu_loss_ms = round(sum(kms.values()), 4) if kms else None
             out["cpu_baseline"] = cpu_baseline(a.height, a.width, a.atk_steps, a.batch_size,
                                                gpu_loss_ms if a.harness == "trainer" else None)
@@ -695,6 +716,30 @@ def run_rank(a):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20       # elements of the weight and gradient vectors --dump-outputs writes (4 MB each in float32)
+
+
+def dump_outputs(job, losses, out_dir):
+    """--dump-outputs: what the last timed step computed, as float32 ``out_dir/<name>.npy``: every entry of the losses dict
+    train_step() returned (``loss/0`` -> ``loss_0.npy``), the gradient the step's optimiser update applied (the flat bucket) and
+    the trained weights after that update, both as the same fixed, seeded sample of DUMP_SAMPLE of their ~14M elements
+    (``grad_sample``, ``weights_sample``), and the adversarial object patch of the step's attack where the harness keeps one
+    (``adv_patch``).  All inputs are seeded: the same flags give the same inputs on every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"".join(c if c.isalnum() else "_" for c in k): v.detach() for k, v in losses.items() if torch.is_tensor(v)}
+    b = job.bucket
+    idx = torch.randperm(b.numel, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(b.flat.device)
+    arrays["grad_sample"] = b.flat[idx]
+    arrays["weights_sample"] = torch.cat([p.detach().reshape(-1) for p in b.params])[idx]
+    patch = getattr(getattr(job, "dataset", None), "obj_img_adv", None)
+    if patch is not None:
+        arrays["adv_patch"] = patch
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def phase_breakdown(trainer, iters=3):

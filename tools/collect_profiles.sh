@@ -10,7 +10,7 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "$MODE" = "benchonly" ]; then     # only the whole-step trace (after a change that leaves the per-kernel passes as they are)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 bench.py --steps 3 --warmup 1 --no_cpu_baseline > $OUT/bench.json 2> $OUT/bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 bench.py --steps 3 --warmup 1 --no_cpu_baseline --full > $OUT/bench.json 2> $OUT/bench.err
   tail -1 $OUT/bench.json | cut -c1-200
   exit 0
 fi
@@ -46,6 +46,6 @@ for shp in "l1 64 64 80 256 1 12" "l3 256 256 20 64 1 12" "up21 128 64 80 256 0 
 done
 echo "k10 passes done"
 if [ "$MODE" = "bench" ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 bench.py --steps 3 --warmup 1 --no_cpu_baseline > $OUT/bench.json 2> $OUT/bench.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- python3 bench.py --steps 3 --warmup 1 --no_cpu_baseline --full > $OUT/bench.json 2> $OUT/bench.err
   tail -1 $OUT/bench.json
 fi
