@@ -10,34 +10,19 @@ the train pass (batch 32):
     rel-L2(HIP vs fp64)  <=  1.5 x rel-L2(library fp32 vs fp64) + 1e-7
 
 Winograd F(2x2,3x3) kernels (K10 / K17 / K18) are in the same numerics class as MIOpen's own F(2,3) and must be as close to
-exact arithmetic as the library is.  The direct MFMA kernels (K11 / K15 / K16) sum an output's products in ONE accumulator
+exact arithmetic as the library is -- as every launch here is (K10 at few regions in its stream-K or channel-split form).  One
+known exception lives in tests/test_gpu_conv_epilogue.py: K10's whole-item form (the fused epilogue without a workspace) sums an
+output's C transformed products in one accumulator, and at C = 512 and batch 2 its chain rounding (6.7e-7) is 3x the library's
+non-Winograd algorithm there (2.2e-7; MIOpen's F(2,3) measures 6.6e-7 at batch 12).  It is held to that chain's estimate.  The direct MFMA kernels (K11 / K15 / K16) sum an output's products in ONE accumulator
 chain where the library's implicit GEMMs split it: they get the chain's own rounding (0.5 sqrt(n) 2^-24) beside that bound.
 """
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.util import conv_data as _data, fp64_bound as _bound, rel_fp64 as _rel
+
 pytestmark = pytest.mark.gpu
-
-
-def _rel(a, ref64):
-    return float((a.double() - ref64).norm() / ref64.norm())
-
-
-def _bound(name, e_hip, e_lib, chain=0):
-    """``chain``: length of the kernel's single fp32 accumulation chain per output (the direct MFMA kernels K11 / K15 / K16
-    sum all C x 9 products of an output into ONE accumulator; the library's implicit GEMMs split that sum): a chain of n
-    rounded additions carries ~ 0.5 sqrt(n) 2^-24 of relative error (random-walk estimate), which is allowed beside the
-    library-relative bound -- 1.4e-6 for layer4.0's 2,304 products, two orders below north_star's 1e-4."""
-    print("%-44s rel-L2 vs fp64: hip %.3g  library fp32 %.3g" % (name, e_hip, e_lib))
-    assert e_hip <= max(1.5 * e_lib + 1e-7, 0.5 * chain ** 0.5 * 2.0 ** -24), (name, e_hip, e_lib)
-
-
-def _data(B, C, K, H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, C, H, W, generator=g).cuda()
-    w = (torch.randn(K, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).cuda()
-    return x, w
 
 
 def _wgrad64(x, g, pad):

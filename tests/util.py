@@ -131,3 +131,32 @@ def no_miopen(fn):
         with torch.backends.cudnn.flags(enabled=False):
             return fn(*a, **kw)
     return wrapped
+
+
+# ---- float64 anchors of the convolution kernels (tests/test_gpu_conv_anchor.py, tests/test_gpu_conv_epilogue.py) ----------------
+
+def rel_fp64(a, ref64):
+    """rel-L2 of ``a`` against a float64 reference on the same device."""
+    return float((a.detach().double() - ref64).norm() / ref64.norm())
+
+
+def fp64_bound(name, e_hip, e_lib, chain=0, factor=1.5, chain_margin=1.0):
+    """rel-L2(HIP vs fp64) <= factor x rel-L2(library fp32 vs fp64) + 1e-7.
+
+    ``chain``: length of the kernel's single fp32 accumulation chain per output (the direct MFMA kernels K11 / K15 / K16
+    sum all C x 9 products of an output into ONE accumulator; the library's implicit GEMMs split that sum): a chain of n
+    rounded additions carries ~ 0.5 sqrt(n) 2^-24 of relative error (random-walk estimate), which is allowed beside the
+    library-relative bound -- 1.4e-6 for layer4.0's 2,304 products, two orders below north_star's 1e-4.
+    ``factor``: 2 for a chain of two launches measured as one (a block node), each held to 1.5 on its own.
+    ``chain_margin``: a multiple of the chain estimate (the same 1.5 the library gets, where the estimate is the kernel's
+    measured error itself)."""
+    print("%-44s rel-L2 vs fp64: hip %.3g  library fp32 %.3g  (ratio %.2f)" % (name, e_hip, e_lib, e_hip / e_lib if e_lib else 0.0))
+    assert e_hip <= max(factor * e_lib + 1e-7, chain_margin * 0.5 * chain ** 0.5 * 2.0 ** -24), (name, e_hip, e_lib)
+
+
+def conv_data(B, C, K, H, W, seed):
+    """x ~ N(0, 1) [B, C, H, W] and a He-scaled 3x3 filter [K, C, 3, 3] on the GPU (outputs of the order of x)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, C, H, W, generator=g).cuda()
+    w = (torch.randn(K, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).cuda()
+    return x, w
