@@ -6,7 +6,7 @@ import torch
 
 from . import ops
 from .datasets import make_object
-from .torchattacks import PGD_depth, Phy_obj_atk, Phy_obj_atk_l0
+from .torchattacks import PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_l0
 
 STEREO_SCALE_FACTOR = 5.4
 MIN_DEPTH = 1e-3
@@ -38,6 +38,8 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
     elif args['norm_type'] == "l_0":
         depth_atk = Phy_obj_atk_l0(model2atk, obj_tensor, mask_tensor, adam_lr=args["adam_lr"], steps=args["step"],
                                    mask_wt=args["mask_wt"], l0_thresh=args["l0_thresh"])
+    elif args['norm_type'] == "APGD":
+        depth_atk = Phy_obj_atk_APGD(model2atk, obj_tensor, mask_tensor, eps=args['epsilon'], steps=args['step'])
     elif args['norm_type'] == "image":
         depth_atk = PGD_depth(model2atk, eps=args['epsilon'], alpha=args['alpha'], steps=args['step'])
         depth_atk._targeted = True

@@ -12,6 +12,8 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::masked_sq_mean       phy_obj_atk.py:94, pgd_depth.py:68-70             (K6)   + dmh::masked_sq_mean_bwd
     dmh::gt_depth_mse         MD2/trainer.py:551-557 (--supervised_adv --gt_depth) (K6b)  + dmh::gt_depth_mse_bwd
     dmh::pgd_linf_step        phy_obj_atk.py:98-101, pgd_depth.py:76-78         (K4)
+    dmh::apgd_step            phy_obj_atk_apgd.py:207-215                       (K22, in place)
+    dmh::apgd_commit          phy_obj_atk_apgd.py:255-290                       (K22, in place)
     dmh::l0_compose           phy_obj_atk_l0.py:94-99,43-52                     (K5)   + dmh::l0_compose_bwd
     dmh::l0_mask_cost         phy_obj_atk_l0.py:130-132                         (K5)   + dmh::l0_mask_cost_bwd
     dmh::photo_smooth_loss    MD2/trainer.py:472-523,539-674 (DH/trainer.py:638-741 with variant 1)   (K1 + K2 + finalise)
@@ -193,6 +195,30 @@ def pgd_linf_step(x: torch.Tensor, x0: torch.Tensor, grad: torch.Tensor, alpha: 
 @pgd_linf_step.register_fake
 def _(x, x0, grad, alpha, eps):
     return torch.empty_like(x)
+
+
+# ---------------------------------------------------------------------------------------------------------------- K22
+@custom_op("dmh::apgd_step", mutates_args=("x_adv", "x_old", "cursor"))
+def apgd_step(x_adv: torch.Tensor, x_old: torch.Tensor, x0: torch.Tensor, grad: torch.Tensor, ctl: torch.Tensor,
+              cursor: torch.Tensor, steps: int, eps: float) -> None:
+    ops.apgd_step(x_adv, x_old, x0, grad, ctl, cursor, steps, eps)
+
+
+@apgd_step.register_fake
+def _(x_adv, x_old, x0, grad, ctl, cursor, steps, eps):
+    return None
+
+
+@custom_op("dmh::apgd_commit", mutates_args=("x_adv", "grad", "x_best", "grad_best", "x_ret", "ctl", "hist", "cursor"))
+def apgd_commit(x_adv: torch.Tensor, g_new: torch.Tensor, grad: torch.Tensor, x_best: torch.Tensor, grad_best: torch.Tensor,
+                x_ret: torch.Tensor, loss: torch.Tensor, ctl: torch.Tensor, hist: torch.Tensor, cursor: torch.Tensor,
+                steps: int, size_decr: int, steps_min: int, rho: float) -> None:
+    ops.apgd_commit(x_adv, g_new, grad, x_best, grad_best, x_ret, loss, ctl, hist, cursor, steps, size_decr, steps_min, rho)
+
+
+@apgd_commit.register_fake
+def _(x_adv, g_new, grad, x_best, grad_best, x_ret, loss, ctl, hist, cursor, steps, size_decr, steps_min, rho):
+    return None
 
 
 # ----------------------------------------------------------------------------------------------------------------- K5
@@ -477,4 +503,5 @@ smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 
 
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
-       "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd")
+       "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
+       "apgd_step", "apgd_commit")

@@ -513,6 +513,64 @@ def pgd_linf_step(x, x0, grad, alpha, eps, out=None):
     return out
 
 
+APGD_REC = 16       # floats per controller record (DMH_APGD_REC)
+
+
+def apgd_controller(steps, eps, loss0, rho=0.75):
+    """Device state of the Auto-PGD controller (K22) for one attack of ``steps`` iterations: (ctl [steps + 1, 16] with record 0
+    filled from phy_obj_atk_apgd.py:137,190-200, hist [steps] zeros, cursor int32 [2] zeros, size_decr, steps_min).  ``loss0``:
+    the device scalar holding the loss at the start point (loss_best and loss_best_last_check start there); nothing is read back."""
+    steps = int(steps)
+    if steps < 1 or steps >= 1 << 24:
+        raise RuntimeError("apgd_controller: steps must lie in [1, 2^24)")
+    if not loss0.is_cuda:
+        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % loss0.device)
+    k0, steps_min, size_decr = max(int(0.22 * steps), 1), max(int(0.06 * steps), 1), max(int(0.03 * steps), 1)
+    host = torch.zeros((steps + 1, APGD_REC), dtype=torch.float32)
+    host[0, 0], host[0, 1], host[0, 4], host[0, 7] = 2.0 * float(torch.tensor(eps, dtype=torch.float32)), 1.0, k0, 1.0
+    ctl = host.to(loss0.device, non_blocking=True)
+    ctl[0, 2:4] = loss0.detach().reshape(1).to(torch.float32)
+    hist = torch.zeros(steps, device=loss0.device, dtype=torch.float32)
+    cursor = torch.zeros(2, device=loss0.device, dtype=torch.int32)
+    return ctl, hist, cursor, size_decr, steps_min
+
+
+def _apgd_check(name, steps, ctl, hist, cursor, tensors):
+    n = tensors[0].numel()
+    for t in tensors:
+        if t.numel() != n or t.dtype != torch.float32:
+            raise RuntimeError("%s: the patch-sized tensors must be fp32 and of one size" % name)
+    if int(steps) < 1 or ctl.dtype != torch.float32 or ctl.numel() < (int(steps) + 1) * APGD_REC:
+        raise RuntimeError("%s: ctl must hold steps + 1 records of %d floats" % (name, APGD_REC))
+    if hist is not None and (hist.dtype != torch.float32 or hist.numel() < int(steps)):
+        raise RuntimeError("%s: hist must hold steps floats" % name)
+    if cursor.dtype != torch.int32 or cursor.numel() < 2:
+        raise RuntimeError("%s: cursor must be int32[2]" % name)
+    return n
+
+
+def apgd_step(x_adv, x_old, x0, grad, ctl, cursor, steps, eps):
+    """In place: x_old <- x_adv, x_adv <- Auto-PGD's momentum step (phy_obj_atk_apgd.py:207-215) with the step size and the
+    momentum weight of the controller record the device cursor points at.  No host value of the iteration enters."""
+    n = _apgd_check("apgd_step", steps, ctl, None, cursor, (x_adv, x_old, x0, grad))
+    N.check(N.lib().dmh_apgd_step(N.ptr(x_adv), N.ptr(x_old), N.ptr(x0), N.ptr(grad), N.ptr(ctl), N.ptr(cursor), int(steps),
+                                  float(eps), n, N.stream()))
+    return x_adv
+
+
+def apgd_commit(x_adv, g_new, grad, x_best, grad_best, x_ret, loss, ctl, hist, cursor, steps, size_decr, steps_min, rho=0.75):
+    """In place, decided on the device from ``loss`` (device scalar: the cost at the new x_adv, ``g_new`` its gradient) and the
+    controller record: best point, loss history, checkpoint, step halving, restart (phy_obj_atk_apgd.py:255-290); writes the
+    next record and advances the cursor."""
+    n = _apgd_check("apgd_commit", steps, ctl, hist, cursor, (x_adv, g_new, grad, x_best, grad_best, x_ret))
+    if loss.numel() != 1 or loss.dtype != torch.float32:
+        raise RuntimeError("apgd_commit: loss must be one fp32 value")
+    N.check(N.lib().dmh_apgd_commit(N.ptr(x_adv), N.ptr(g_new), N.ptr(grad), N.ptr(x_best), N.ptr(grad_best), N.ptr(x_ret),
+                                    N.ptr(loss), N.ptr(ctl), N.ptr(hist), N.ptr(cursor), int(steps), int(size_decr),
+                                    int(steps_min), float(rho), n, N.stream()))
+    return x_adv
+
+
 class _L0Compose(torch.autograd.Function):
     @staticmethod
     def forward(ctx, obj, pos, neg, l0_clip, finalize):

@@ -246,18 +246,7 @@ class Phy_obj_atk(Attack):
         coeff_cur.copy_(coeffs[1])
         tab_cur.copy_(tabs[1])
         main = torch.cuda.current_stream(dev)
-        if self._graph_pool is None:
-            # the allocator drops a pool with its last graph: a one-kernel graph that is never destroyed keeps this one
-            pool, side, keeper = torch.cuda.graph_pool_handle(), torch.cuda.Stream(device=dev), torch.cuda.CUDAGraph()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                keeper.capture_begin(pool=pool)
-                try:
-                    torch.zeros(8, device=dev)
-                finally:
-                    keeper.capture_end()
-            self._graph_pool = (pool, side, keeper)
-        pool, side, _ = self._graph_pool
+        pool, side = self._capture_pool(main)
         side.wait_stream(main)
         g = torch.cuda.CUDAGraph()
         try:
@@ -300,6 +289,22 @@ class Phy_obj_atk(Attack):
         done.record(main)
         self._graph = (g, done)
         return out, self.steps
+
+    def _capture_pool(self, main):
+        """(memory pool, side stream) this attack object captures its graphs into, made at the first capture."""
+        if self._graph_pool is None:
+            dev = self.device
+            # the allocator drops a pool with its last graph: a one-kernel graph that is never destroyed keeps this one
+            pool, side, keeper = torch.cuda.graph_pool_handle(), torch.cuda.Stream(device=dev), torch.cuda.CUDAGraph()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                keeper.capture_begin(pool=pool)
+                try:
+                    torch.zeros(8, device=dev)
+                finally:
+                    keeper.capture_end()
+            self._graph_pool = (pool, side, keeper)
+        return self._graph_pool[0], self._graph_pool[1]
 
     def _shard_without_scenes(self, obj_img_adv, dist, group):
         """A rank whose share of the attack batch is empty (world > batch_size): it contributes a zero gradient to every

@@ -204,6 +204,30 @@ int dmh_pgd_linf_step(const float* x, const float* x0, const float* g, float alp
                       int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K22  Auto-PGD (L_inf) on the object patch: momentum step and step-size controller, both driven from device memory.
+ * Replaces: phy_obj_atk_apgd.py:205-225 (step), :255-290 (best point, loss history, checkpoint, halving, restart).
+ *   ctl    [steps + 1][DMH_APGD_REC] floats, 16-byte aligned.  Record i is read by iteration i; commit writes record i + 1.
+ *          Words: 0 step size, 1 momentum weight a, 2 loss_best, 3 loss_best at the last checkpoint, 4 k, 5 iterations
+ *          since the last checkpoint, 6 iteration index, 7 reduced at the last checkpoint (starts 1), and about the
+ *          iteration before: 8 its loss, 9 it was a checkpoint, 10 it halved the step and restarted, 11 loss_best moved,
+ *          12 how many of the last k losses rose; 13-15 zero.  The caller fills record 0 and zeroes the rest.
+ *   hist   [steps] floats, zeroed by the caller: the loss of every iteration.
+ *   cursor int32[2], zeroed by the caller: step runs iteration cursor[0] and copies it to cursor[1]; commit finishes
+ *          iteration cursor[1] and sets cursor[0] to the next.  A cursor outside [0, steps) makes both a no-op.
+ * step:   x_old <- x_adv;  x_adv <- the momentum step of :207-215 with step size and a of record i, every operation
+ *         rounded on its own (bit-equal to the element-wise fp32 expression).
+ * commit: with loss[0] = the cost at the new x_adv and g_new its gradient: x_ret <- x_adv; if loss > loss_best:
+ *         x_best <- x_adv, grad_best <- g_new; hist[i] <- loss; on a checkpoint that reduces: x_adv <- x_best,
+ *         grad <- grad_best, else grad <- g_new; record i + 1.  All tensor arguments hold n floats and must not alias.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_APGD_REC 16
+int dmh_apgd_step(float* x_adv, float* x_old, const float* x0, const float* grad, const float* ctl, int32_t* cursor,
+                  int steps, float eps, int64_t n, void* stream);
+int dmh_apgd_commit(float* x_adv, const float* g_new, float* grad, float* x_best, float* grad_best, float* x_ret,
+                    const float* loss, float* ctl, float* hist, int32_t* cursor, int steps, int size_decr, int steps_min,
+                    double rho, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K5  L0 attack pieces (phy_obj_atk_l0.py).
  * compose (:94-99,:43-52): adv = clamp(obj + clamp(pos,0,1) - clamp(neg,0,1), 0, 1);
  *   l0_count (int32, zeroed by caller) += #pixels whose thresholded pattern is non-zero.
