@@ -80,6 +80,7 @@ _SIGNATURES = {
     "dmh_pgd_linf_step": (C.c_int, [_fp, _fp, _fp, C.c_float, C.c_float, _fp, C.c_int64, _fp]),
     "dmh_apgd_step": (C.c_int, [_fp] * 6 + [C.c_int, C.c_float, C.c_int64, _fp]),
     "dmh_apgd_commit": (C.c_int, [_fp] * 10 + [C.c_int] * 3 + [C.c_double, C.c_int64, _fp]),
+    "dmh_l0_fused_step": (C.c_int, [_fp] * 15 + [C.c_int] * 3 + [C.c_float] * 3 + [_fp]),
     "dmh_l0_compose_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp]),
     "dmh_l0_compose_bwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp]),
     "dmh_l0_mask_partials_size": (C.c_int64, [C.c_int]),

@@ -14,6 +14,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::pgd_linf_step        phy_obj_atk.py:98-101, pgd_depth.py:76-78         (K4)
     dmh::apgd_step            phy_obj_atk_apgd.py:207-215                       (K22, in place)
     dmh::apgd_commit          phy_obj_atk_apgd.py:255-290                       (K22, in place)
+    dmh::l0_fused_step        phy_obj_atk_l0.py:105-111,136-138,94-99           (K23, in place)
     dmh::l0_compose           phy_obj_atk_l0.py:94-99,43-52                     (K5)   + dmh::l0_compose_bwd
     dmh::l0_mask_cost         phy_obj_atk_l0.py:130-132                         (K5)   + dmh::l0_mask_cost_bwd
     dmh::photo_smooth_loss    MD2/trainer.py:472-523,539-674 (DH/trainer.py:638-741 with variant 1)   (K1 + K2 + finalise)
@@ -218,6 +219,22 @@ def apgd_commit(x_adv: torch.Tensor, g_new: torch.Tensor, grad: torch.Tensor, x_
 
 @apgd_commit.register_fake
 def _(x_adv, g_new, grad, x_best, grad_best, x_ret, loss, ctl, hist, cursor, steps, size_decr, steps_min, rho):
+    return None
+
+
+# ---------------------------------------------------------------------------------------------------------------- K23
+@custom_op("dmh::l0_fused_step", mutates_args=("pos", "neg", "m_pos", "v_pos", "m_neg", "v_neg", "adv", "count", "rec", "cursor"))
+def l0_fused_step(obj: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, m_pos: torch.Tensor, v_pos: torch.Tensor,
+                  m_neg: torch.Tensor, v_neg: torch.Tensor, g_adv: torch.Tensor, adv: torch.Tensor, count: torch.Tensor,
+                  rec: torch.Tensor, cursor: torch.Tensor, tab: torch.Tensor, adv_cost: torch.Tensor,
+                  mask_cost: Optional[torch.Tensor], steps: int, mask_wt: float, thresh: float, l0_clip: float) -> None:
+    ops.l0_fused_step(obj, pos, neg, m_pos, v_pos, m_neg, v_neg, g_adv, adv, count, rec, cursor, tab, adv_cost, mask_cost, steps,
+                      mask_wt, thresh, l0_clip)
+
+
+@l0_fused_step.register_fake
+def _(obj, pos, neg, m_pos, v_pos, m_neg, v_neg, g_adv, adv, count, rec, cursor, tab, adv_cost, mask_cost, steps, mask_wt, thresh,
+      l0_clip):
     return None
 
 
@@ -504,4 +521,4 @@ smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
-       "apgd_step", "apgd_commit")
+       "apgd_step", "apgd_commit", "l0_fused_step")

@@ -632,6 +632,79 @@ def l0_mask_cost(pos, neg):
     return _L0MaskCost.apply(_c(pos), _c(neg))
 
 
+L0_REC = 8          # floats per record of the fused L0 update (DMH_L0_REC)
+L0_BETAS = (0.5, 0.9)   # phy_obj_atk_l0.py:85; K23 holds them as constants
+
+
+def l0_adam_table(steps, lr):
+    """Adam's bias corrections for t = 1 .. 2 * steps as K23 reads them: a host fp32 tensor [2 * steps, 2] of
+    (lr / (1 - b1^t), sqrt(1 - b2^t)), computed in double and rounded once."""
+    import math
+    b1, b2 = L0_BETAS
+    rows = [(float(lr) / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)) for t in range(1, 2 * int(steps) + 1)]
+    return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+
+class L0FusedState(object):
+    """The device buffers of one fused L0 attack of ``steps`` (2 * steps iterations at the most): the two patterns (taken over,
+    updated in place), Adam's m / v for both, the composed patch, and the controller's words -- count int32 [2 steps + 1], rec
+    [2 steps, L0_REC], cursor int32 [2], tab [2 steps, 2].  Nothing here is read by the host while the attack runs."""
+
+    def __init__(self, pos, neg, steps, lr):
+        steps = int(steps)
+        if steps < 1 or steps >= 1 << 24:
+            raise RuntimeError("L0FusedState: steps must lie in [1, 2^24)")
+        if not pos.is_cuda:
+            raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % pos.device)
+        dev = pos.device
+        self.steps = steps
+        self.pos, self.neg = _c(pos.detach()), _c(neg.detach())
+        state = torch.zeros((4,) + tuple(pos.shape), device=dev, dtype=torch.float32)
+        self.m_pos, self.v_pos, self.m_neg, self.v_neg = state[0], state[1], state[2], state[3]
+        self.adv = torch.empty_like(self.pos)
+        self.count = torch.zeros(2 * steps + 1, device=dev, dtype=torch.int32)
+        self.rec = torch.zeros((2 * steps, L0_REC), device=dev, dtype=torch.float32)
+        self.cursor = torch.zeros(2, device=dev, dtype=torch.int32)
+        self.tab = l0_adam_table(steps, lr).to(dev, non_blocking=True)
+
+    def step(self, obj, g_adv, adv_cost, mask_cost, mask_wt, thresh, l0_clip):
+        return l0_fused_step(obj, self.pos, self.neg, self.m_pos, self.v_pos, self.m_neg, self.v_neg, g_adv, self.adv,
+                             self.count, self.rec, self.cursor, self.tab, adv_cost, mask_cost, self.steps, mask_wt, thresh,
+                             l0_clip)
+
+
+def l0_fused_step(obj, pos, neg, m_pos, v_pos, m_neg, v_neg, g_adv, adv, count, rec, cursor, tab, adv_cost, mask_cost, steps,
+                  mask_wt, thresh, l0_clip=1.0 / 255.0):
+    """K23, in place: iteration i = cursor[0] of the L0 attack from ``g_adv`` = d adv_cost / d composed patch to the next composed
+    patch ``adv`` -- mask weight from count[i] / count[0] <= thresh, both clamps' gates, the mask cost's gradient, Adam on both
+    patterns, compose, count[i + 1], record i, cursor + 1 (phy_obj_atk_l0.py:92-138).  No host value of the iteration enters."""
+    steps = int(steps)
+    if obj.dim() != 4 or obj.shape[0] != 1:
+        raise RuntimeError("l0_fused_step: obj must be [1,C,H,W]")
+    n = obj.numel()
+    for t in (obj, pos, neg, m_pos, v_pos, m_neg, v_neg, g_adv, adv):
+        if t.numel() != n or t.dtype != torch.float32:
+            raise RuntimeError("l0_fused_step: the patch-sized tensors must be fp32 and of one size")
+    if steps < 1 or steps >= 1 << 24:
+        raise RuntimeError("l0_fused_step: steps must lie in [1, 2^24)")
+    if count.dtype != torch.int32 or count.numel() < 2 * steps + 1:
+        raise RuntimeError("l0_fused_step: count must be int32[2 * steps + 1]")
+    if rec.dtype != torch.float32 or rec.numel() < 2 * steps * L0_REC:
+        raise RuntimeError("l0_fused_step: rec must hold 2 * steps records of %d floats" % L0_REC)
+    if tab.dtype != torch.float32 or tab.numel() < 4 * steps:
+        raise RuntimeError("l0_fused_step: tab must hold 2 * steps pairs of floats")
+    if cursor.dtype != torch.int32 or cursor.numel() < 2:
+        raise RuntimeError("l0_fused_step: cursor must be int32[2]")
+    for name, t in (("adv_cost", adv_cost), ("mask_cost", mask_cost)):
+        if t is not None and (t.numel() != 1 or t.dtype != torch.float32):
+            raise RuntimeError("l0_fused_step: %s must be one fp32 value" % name)
+    N.check(N.lib().dmh_l0_fused_step(N.ptr(obj), N.ptr(pos), N.ptr(neg), N.ptr(m_pos), N.ptr(v_pos), N.ptr(m_neg), N.ptr(v_neg),
+                                      N.ptr(g_adv), N.ptr(adv), N.ptr(count), N.ptr(rec), N.ptr(cursor), N.ptr(tab),
+                                      N.ptr(adv_cost), N.ptr(mask_cost), steps, obj.shape[1], obj.shape[2] * obj.shape[3],
+                                      float(mask_wt), float(thresh), float(l0_clip), N.stream()))
+    return adv
+
+
 class _UpCatPad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, skip):
@@ -2190,6 +2263,23 @@ class CleanHead(object):
         if self.dirty2 is not None:
             self._put_back(self.pristine2, self.work2, self.dirty2)
             self.dirty2 = None
+
+
+def clean_head_snapshot():
+    """The Python-side state a traced-but-never-executed attack iteration changes (a HIP-graph capture): the keys of the
+    frozen-weights cache and, of every CleanHead in it, the dirty windows, the generation and the private origin copies."""
+    heads = [(h, h.dirty, h.dirty2, h.generation, dict(h._own)) for h in _wino_cache.values() if isinstance(h, CleanHead)]
+    return set(_wino_cache), heads
+
+
+def clean_head_restore(snap):
+    """Put back what clean_head_snapshot() saw: entries made since are dropped (after a failed capture they point at pool memory
+    that no kernel wrote), and every CleanHead names the window the last EXECUTED iteration left dirty."""
+    keys, heads = snap
+    for k in [k for k in _wino_cache if k not in keys]:
+        del _wino_cache[k]
+    for h, dirty, dirty2, generation, own in heads:
+        h.dirty, h.dirty2, h.generation, h._own = dirty, dirty2, generation, own
 
 
 class _EncHeadInc(torch.autograd.Function):

@@ -110,7 +110,12 @@ class MonodepthOptions:
         p.add_argument("--graph_attack", action="store_true",
                        help="L_inf attack: one set of window sizes for all steps, step 1 captured in a HIP graph and replayed "
                             "for steps 2 .. n-1 (torchattacks/attacks/phy_obj_atk.py, use_graph): takes the step's ~130 launches "
-                            "off the host; for ranks whose GPU share is small (strong scaling)")
+                            "off the host; for ranks whose GPU share is small (strong scaling).  L_0 attack: the same for the "
+                            "fused iteration (implies --atk_fused_l0)")
+        p.add_argument("--atk_fused_l0", action="store_true",
+                       help="L_0 attack: the update of an iteration (mask-weight selection, both backward routes, Adam, next "
+                            "compose + L0 count) as ONE launch that reads its decisions from device memory "
+                            "(torchattacks/attacks/phy_obj_atk_l0.py, fused); with --graph_attack also replayed from a HIP graph")
         p.add_argument("--step_log", type=str, default="",
                        help="JSONL step log written by rank 0 (SURVEY.md section 5): one line per iteration with the loss, "
                             "images/s and the GPU time of each phase (attack / forward + loss / backward / all-reduce + "

@@ -17,8 +17,16 @@ import torch.nn.functional as F
 from ... import color_jitter, ops
 from ...my_utils import object_dataset_root, ori_H, ori_W, to_device_async
 from ...physicalTrans import PhysicalTrans
-from ...roi import RoiPlan
+from ...roi import RoiPlan, common_size_plans
 from ..attack import Attack
+from .phy_obj_atk import Phy_obj_atk
+
+
+def host_below(counts, stp, thresh):
+    """The fused attack's decision for iteration ``stp`` from a host copy of its count array, in float32 exactly as K23
+    evaluates it on the device (csrc/l0_fused.hip, l0_below): count[stp] / count[0] <= thresh."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return bool(np.float32(counts[stp]) / np.float32(counts[0]) <= np.float32(thresh))
 
 
 class Phy_obj_atk_l0(Attack):
@@ -51,6 +59,22 @@ class Phy_obj_atk_l0(Attack):
         self.shard = None       # (rank, world, group): data-parallel shared-patch mode, see Phy_obj_atk.shard
         self.trace = None  # set to a list to record (l0, mask_weight, adv_cost, mask_cost) per iteration
         self.grad_trace = None  # set to a list to record the two pattern gradients Adam is handed, per iteration (tests)
+        # fused: everything between the model's gradient and the next composed patch is ONE launch (K23, csrc/l0_fused.hip) that
+        # reads its decisions from device memory -- no torch.optim.Adam, no torch.where, no autograd node for the mask cost; the
+        # trace is read once after the loop from K23's record array (kept in ``records``).  Off by default.
+        self.fused = False
+        # use_graph / common_windows: as on Phy_obj_atk -- one set of window sizes for all 2 * steps draws, iteration 0 eager,
+        # iteration 1 captured in a HIP graph, later iterations two small device copies + a replay.  Implies ``fused``.
+        self.use_graph = False
+        self.common_windows = False
+        self.records = None             # K23's record array [2 * steps, ops.L0_REC] of the last fused attack (device)
+        self.graph_replays = 0          # how many iterations of the last attack were graph replays
+        self.graph_failure = None       # why use_graph switched itself off (a failed capture), else None
+        self._capture_fault = False     # test hook: make the capture fail after the whole iteration has been traced
+        self._graph_pool = None
+        self._graph = None              # (graph of the previous attack, event behind its last replay)
+
+    _capture_pool = Phy_obj_atk._capture_pool
 
     def cal_l0(self):
         """Number of pixels whose thresholded pattern is non-zero (:43-52), as a device tensor."""
@@ -76,6 +100,15 @@ class Phy_obj_atk_l0(Attack):
             if not mine:
                 raise RuntimeError("Phy_obj_atk_l0.shard: more ranks than attack scenes is not supported")
             share = len(mine) / float(batch_size)
+        if self.shard is not None and (self.fused or self.use_graph):
+            raise NotImplementedError("Phy_obj_atk_l0: shard together with fused / use_graph is not built (the sharded attack's "
+                                      "two all-reduces sit between the backward kernels the fused update replaces)")
+        if color_jit and self.use_graph:
+            raise NotImplementedError("Phy_obj_atk_l0: color_jit=True together with use_graph is not built (the colour "
+                                      "augmentation takes the whole-frame path; fused alone works with it)")
+        if self.grad_trace is not None and (self.fused or self.use_graph):
+            raise NotImplementedError("Phy_obj_atk_l0: grad_trace belongs to the unfused path (the fused update never "
+                                      "materialises the pattern gradients)")
         n_local = batch_size if mine is None else len(mine)
         if img_B != 1 and img_B != n_local:
             raise RuntimeError('Batch size doesn\'t match!')
@@ -131,56 +164,63 @@ class Phy_obj_atk_l0(Attack):
         # so neither the windows' "unchanged outside the box" nor the cached clean-frame features hold: whole-frame path)
         if (ops.ROI_ENABLED and self.use_roi and not color_jit and hasattr(self.model, "masked_sq_mean")
                 and self.device.type == "cuda"):
-            plans = [RoiPlan(pt.mask_boxes(z0, al, self.scene_size), *self.scene_size, depth=ops.ROI_DEPTH) for z0, al in draws]
+            boxes = [pt.mask_boxes(z0, al, self.scene_size) for z0, al in draws]
+            if self.use_graph or self.common_windows:       # one set of window sizes for all 2 * steps draws (see Phy_obj_atk)
+                plans = common_size_plans(boxes, *self.scene_size, depth=ops.ROI_DEPTH)
+            if plans is None:
+                plans = [RoiPlan(b, *self.scene_size, depth=ops.ROI_DEPTH) for b in boxes]
             tabs = to_device_async(np.stack([p.table() for p in plans], 0), self.device)
             for p_, t_ in zip(plans, tabs):     # one H2D copy for all steps; each plan keeps ITS slice (RoiPlan.bind_table)
                 p_.bind_table(t_)
             with torch.no_grad():       # the frames without the object: see Phy_obj_atk.forward
                 clean, _ = ops.eot_paste(scene_imgs, self.obj_img, torch.zeros_like(mask), coeffs[0], l_pad, t_pad,
                                          self.scene_size)
-        thresh = torch.full((), float(self.l0_thresh), device=self.device)      # fill kernels: no host sync
-        w_on = torch.full((), float(self.mask_weight_init), device=self.device)
-        w_off = torch.zeros((), device=self.device)
-        l0_norm_init = None
-        mw = w_on
-        ran = 0
-        for stp in range(max_iter):
-            obj_img_adv, l0_norm = ops.l0_compose(self.obj_img, self.pattern_pos_tensor, self.pattern_neg_tensor,
-                                                  self.l0_clip)
-            if stp == 0:
-                l0_norm_init = l0_norm
-            below = (l0_norm.float() / l0_norm_init.float())[0] <= thresh
-            if stp >= self.steps and bool(below):  # the only host read of the ratio (:106-109)
-                mw = w_off
-                break
-            mw = torch.where(below, w_off, w_on)
-            adv_scenes, adv_obj_mask = ops.eot_paste(scene_imgs, obj_img_adv, mask, coeffs[stp], l_pad, t_pad,
-                                                     self.scene_size)
-            if plans is not None:
-                adv_cost = self.model.masked_sq_mean(adv_scenes, adv_obj_mask, plans[stp], tabs[stp], clean)
-            else:
-                if color_jit:       # :122-124 (off the hot path: composed from tensor operations, see color_jitter.py)
-                    adv_scenes = self.color_aug(adv_scenes)
-                adv_depth = self.model(adv_scenes)
-                adv_cost = ops.masked_sq_mean(adv_depth, adv_obj_mask)
-            mask_cost = ops.l0_mask_cost(self.pattern_pos_tensor, self.pattern_neg_tensor)
-            total_cost = adv_cost + mw * mask_cost
-            if mine is not None:    # this rank's part of the job's cost: the sum over the ranks below is the one-process gradient
-                total_cost = adv_cost * share + mw * mask_cost * (1.0 / world)
-            # same update as zero_grad(); total_cost.backward(); step() (:136-138), but only the two
-            # pattern tensors get gradients: the reference's backward() also fills (and later discards)
-            # weight gradients of the attacked model -- a third of the conv backward work
-            g_pos, g_neg = torch.autograd.grad(total_cost, [self.pattern_pos_tensor, self.pattern_neg_tensor])
-            if mine is not None:
-                dist.all_reduce(g_pos, op=dist.ReduceOp.SUM, group=group)
-                dist.all_reduce(g_neg, op=dist.ReduceOp.SUM, group=group)
-            if self.grad_trace is not None:
-                self.grad_trace.append((g_pos.detach().clone(), g_neg.detach().clone()))
-            self.pattern_pos_tensor.grad, self.pattern_neg_tensor.grad = g_pos, g_neg
-            optimizer.step()
-            ran += 1
-            if self.trace is not None:
-                self.trace.append((int(l0_norm), float(mw), float(adv_cost), float(mask_cost)))
+        if self.fused or self.use_graph:
+            ran, mw = self._fused_loop(scene_imgs, mask, coeffs, l_pad, t_pad, plans, tabs, clean, color_jit, max_iter)
+        else:
+            thresh = torch.full((), float(self.l0_thresh), device=self.device)      # fill kernels: no host sync
+            w_on = torch.full((), float(self.mask_weight_init), device=self.device)
+            w_off = torch.zeros((), device=self.device)
+            l0_norm_init = None
+            mw = w_on
+            ran = 0
+            for stp in range(max_iter):
+                obj_img_adv, l0_norm = ops.l0_compose(self.obj_img, self.pattern_pos_tensor, self.pattern_neg_tensor,
+                                                      self.l0_clip)
+                if stp == 0:
+                    l0_norm_init = l0_norm
+                below = (l0_norm.float() / l0_norm_init.float())[0] <= thresh
+                if stp >= self.steps and bool(below):  # the only host read of the ratio (:106-109)
+                    mw = w_off
+                    break
+                mw = torch.where(below, w_off, w_on)
+                adv_scenes, adv_obj_mask = ops.eot_paste(scene_imgs, obj_img_adv, mask, coeffs[stp], l_pad, t_pad,
+                                                         self.scene_size)
+                if plans is not None:
+                    adv_cost = self.model.masked_sq_mean(adv_scenes, adv_obj_mask, plans[stp], tabs[stp], clean)
+                else:
+                    if color_jit:       # :122-124 (off the hot path: composed from tensor operations, see color_jitter.py)
+                        adv_scenes = self.color_aug(adv_scenes)
+                    adv_depth = self.model(adv_scenes)
+                    adv_cost = ops.masked_sq_mean(adv_depth, adv_obj_mask)
+                mask_cost = ops.l0_mask_cost(self.pattern_pos_tensor, self.pattern_neg_tensor)
+                total_cost = adv_cost + mw * mask_cost
+                if mine is not None:    # this rank's part of the job's cost: the sum over the ranks below is the one-process gradient
+                    total_cost = adv_cost * share + mw * mask_cost * (1.0 / world)
+                # same update as zero_grad(); total_cost.backward(); step() (:136-138), but only the two
+                # pattern tensors get gradients: the reference's backward() also fills (and later discards)
+                # weight gradients of the attacked model -- a third of the conv backward work
+                g_pos, g_neg = torch.autograd.grad(total_cost, [self.pattern_pos_tensor, self.pattern_neg_tensor])
+                if mine is not None:
+                    dist.all_reduce(g_pos, op=dist.ReduceOp.SUM, group=group)
+                    dist.all_reduce(g_neg, op=dist.ReduceOp.SUM, group=group)
+                if self.grad_trace is not None:
+                    self.grad_trace.append((g_pos.detach().clone(), g_neg.detach().clone()))
+                self.pattern_pos_tensor.grad, self.pattern_neg_tensor.grad = g_pos, g_neg
+                optimizer.step()
+                ran += 1
+                if self.trace is not None:
+                    self.trace.append((int(l0_norm), float(mw), float(adv_cost), float(mask_cost)))
         random.setstate(states_after[ran])     # as if only the iterations that ran, and then the final poses, had drawn
         # the loop runs ``steps`` ... 2 ``steps`` iterations, by the patch's L0 ratio (:105-109): callers that time the attack
         # (bench.py) report how many it ran
@@ -198,3 +238,125 @@ class Phy_obj_atk_l0(Attack):
             ben_scenes, _ = ops.eot_paste(scene_imgs, self.obj_img, mask, cf, l_pad, t_pad, self.scene_size)
         self.mask_weight = float(mw)
         return adv_scenes, ben_scenes, obj_masks_out, obj_img_adv
+
+    # ------------------------------------------------------------------------------------------------ fused path (K23)
+    def _fused_loop(self, scene_imgs, mask, coeffs, l_pad, t_pad, plans, tabs, clean, color_jit, max_iter):
+        """Iterations of the attack with K23 as the update: eot_paste -> cost -> autograd.grad(adv_cost, patch) -> l0_fused_step.
+        Iterations below ``steps`` read nothing back; from ``steps`` on the host reads the count array before each iteration
+        and ends the loop as the reference does (:105-109).  Returns (iterations run, last mask weight)."""
+        dev = self.device
+        obj = self.obj_img.to(dev).contiguous()
+        st = ops.L0FusedState(self.pattern_pos_tensor, self.pattern_neg_tensor, self.steps, self.learning_rate)
+        self.pattern_pos_tensor, self.pattern_neg_tensor = st.pos, st.neg     # plain device buffers, updated in place
+        with torch.no_grad():           # iteration 0's patch and count[0] (K5); every later one comes out of K23
+            adv0, c0 = ops.l0_compose(obj, st.pos, st.neg, self.l0_clip)
+            st.adv.copy_(adv0)
+            st.count[:1].copy_(c0)
+        one = torch.ones((), device=dev, dtype=torch.float32)
+        tracing = self.trace is not None
+        mask_wt, thresh = float(self.mask_weight_init), float(self.l0_thresh)
+
+        def iteration(coeff, plan, tab):
+            p = st.adv.detach().requires_grad_(True)
+            adv_scenes, adv_obj_mask = ops.eot_paste(scene_imgs, p, mask, coeff, l_pad, t_pad, self.scene_size)
+            if plan is not None:
+                adv_cost = self.model.masked_sq_mean(adv_scenes, adv_obj_mask, plan, tab, clean)
+            else:
+                if color_jit:
+                    adv_scenes = self.color_aug(adv_scenes)
+                adv_cost = ops.masked_sq_mean(self.model(adv_scenes), adv_obj_mask)
+            (g,) = torch.autograd.grad(adv_cost, p, grad_outputs=one if adv_cost.dim() == 0 and adv_cost.dtype == torch.float32 else None)
+            mask_cost = None
+            if tracing:
+                with torch.no_grad():
+                    mask_cost = ops.l0_mask_cost(st.pos, st.neg)
+            st.step(obj, g.contiguous(), adv_cost.detach(), mask_cost, mask_wt, thresh, self.l0_clip)
+
+        graph_mode = bool(self.use_graph and plans is not None and dev.type == "cuda" and not ops.profiling_every_launch())
+        coeff_cur = tab_cur = g = None
+        if graph_mode:      # the captured iteration reads its pose from fixed buffers (see Phy_obj_atk._graph_steps)
+            coeff_cur, tab_cur = coeffs[0].clone(), tabs[0].clone()
+            plans[0].bind_table(tab_cur)
+            plans[0].table_rewritten = True
+        self.graph_replays = 0
+        ran, exited, counts = 0, False, None
+        for stp in range(max_iter):
+            if stp >= self.steps:       # the only host read of the loop (:106-109)
+                counts = st.count.cpu().numpy()
+                if host_below(counts, stp, self.l0_thresh):
+                    exited = True
+                    break
+            if graph_mode and stp > 0:
+                coeff_cur.copy_(coeffs[stp])
+                tab_cur.copy_(tabs[stp])
+                if g is None:
+                    g = self._capture(lambda: iteration(coeff_cur, plans[0], tab_cur))
+                    if g is None:       # the capture failed: the eager loop takes over on the same common-size plans
+                        graph_mode = False
+                        plans[0].table_rewritten = False
+                        for p_, t_ in zip(plans, tabs):
+                            p_.bind_table(t_)
+            if graph_mode and stp > 0:
+                g.replay()
+                self.graph_replays += 1
+            elif graph_mode:
+                iteration(coeff_cur, plans[0], tab_cur)     # iteration 0, eager: it fills the caches of the frozen-weights scope
+            elif plans is not None:
+                iteration(coeffs[stp], plans[stp], tabs[stp])
+            else:
+                iteration(coeffs[stp], None, None)
+            ran += 1
+        if g is not None:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self._graph = (g, ev)
+        self.records = st.rec
+        rec = st.rec[:ran].cpu().numpy() if (tracing or not exited) and ran else None
+        if tracing and rec is not None:
+            for r in rec:
+                self.trace.append((int(r[0]), float(r[1]), float(r[2]), float(r[3])))
+        mw = 0.0 if exited or rec is None else float(rec[ran - 1][1])
+        return ran, mw
+
+    def _capture(self, iteration):
+        """One fused iteration as a HIP graph, with Phy_obj_atk's capture discipline (side stream, this object's memory pool,
+        thread_local error mode); None after a failed capture, with ``graph_failure`` set and ``use_graph`` switched off.  A
+        capture executes nothing on the device, but tracing the iteration runs the Python-side bookkeeping of the incremental
+        encoder head (ops.CleanHead: which window is dirty, its generation, its private origin copies) and may add entries to the
+        frozen-weights cache that point at pool memory no kernel ever wrote: both are snapshotted before the capture and put back
+        after a failed one, so that the eager loop continues from the state iteration 0 really left."""
+        dev = self.device
+        if self._graph is not None:     # the previous attack's graph: let its last replay finish before it is destroyed
+            self._graph[1].synchronize()
+            self._graph = None
+        main = torch.cuda.current_stream(dev)
+        pool, side = self._capture_pool(main)
+        side.wait_stream(main)
+        g = torch.cuda.CUDAGraph()
+        snap = ops.clean_head_snapshot()
+        try:
+            with torch.cuda.stream(side):
+                ops._sk_workspace(dev)
+                g.capture_begin(pool=pool, capture_error_mode="thread_local")
+                try:
+                    iteration()
+                    if self._capture_fault:     # test hook: a capture that dies after the whole iteration has been traced
+                        raise RuntimeError("injected capture fault")
+                except BaseException:
+                    try:
+                        g.capture_end()
+                    except Exception:
+                        pass
+                    raise
+                g.capture_end()
+        except RuntimeError as e:
+            main.wait_stream(side)
+            ops.clean_head_restore(snap)
+            self.use_graph = False
+            self.graph_failure = "%s: %s" % (type(e).__name__, str(e).splitlines()[0] if str(e) else "")
+            import warnings
+            warnings.warn("Phy_obj_atk_l0: HIP-graph capture of the attack iteration failed (%s); continuing with eager launches"
+                          % self.graph_failure)
+            return None
+        main.wait_stream(side)
+        return g

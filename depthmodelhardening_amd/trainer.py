@@ -136,6 +136,25 @@ class LazyOutputs(dict):
         return self[key] if key in self else default
 
 
+def attack_switches(opt):
+    """Attributes the training attack object gets from the options: --graph_attack is ``use_graph`` of Phy_obj_atk (l_inf) or
+    ``fused`` + ``use_graph`` of Phy_obj_atk_l0 (l_0); --atk_fused_l0 is ``fused`` of the latter.  Raises for combinations that
+    are not built (the attack object itself refuses ``shard`` together with ``fused``)."""
+    out = {}
+    l0 = opt.norm_type == "l_0"
+    if getattr(opt, "atk_fused_l0", False):
+        if not l0:
+            raise NotImplementedError("--atk_fused_l0 is the L_0 attack's option (Phy_obj_atk_l0.fused)")
+        out["fused"] = True
+    if getattr(opt, "graph_attack", False):
+        if opt.norm_type not in ("l_inf", "l_0"):
+            raise NotImplementedError("--graph_attack is an option of the L_inf and L_0 object attacks (use_graph)")
+        if l0:
+            out["fused"] = True
+        out["use_graph"] = True
+    return out
+
+
 class Trainer:
     def __init__(self, options, rank=0, world_size=1, device=None, host_only=False):
         """``host_only=True`` (tests of the checkpoint layout and the gradient bucket): a non-CUDA device is accepted for the
@@ -253,10 +272,8 @@ class Trainer:
             self.adv_args = args
             if getattr(self.opt, "shared_patch", False) and self.world_size > 1:
                 self.dataset.depth_atk.shard = (self.rank, self.world_size, None)
-            if getattr(self.opt, "graph_attack", False):
-                if self.opt.norm_type != "l_inf":
-                    raise NotImplementedError("--graph_attack is the L_inf attack's option (Phy_obj_atk.use_graph)")
-                self.dataset.depth_atk.use_graph = True
+            for name, value in attack_switches(self.opt).items():
+                setattr(self.dataset.depth_atk, name, value)
             self.update_adv_obj()   # trainer.py:231-233
 
         # The reference builds SSIM() and per-scale BackprojectDepth / Project3D modules here (MD2/trainer.py:240-254);

@@ -228,6 +228,27 @@ int dmh_apgd_commit(float* x_adv, const float* g_new, float* grad, float* x_best
                     double rho, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K23  L0 object attack: one iteration's update in one launch, decisions read from device memory.
+ * Replaces: phy_obj_atk_l0.py:105-111 (mask-weight selection), the backward of :94-99 and :130-132, Adam's step (:138,
+ * betas (0.5, 0.9), eps 1e-8, state m / v in fp32) and the compose + L0 count of the next iteration (:94-99, :43-52).
+ *   count  int32 [2 steps + 1]: count[i] = L0 count of the patch iteration i attacks; the caller fills count[0] (K5) and
+ *          zeroes the rest.  Iteration i reads count[i], count[0] and adds into count[i + 1].
+ *   tab    [2 steps][2] floats: (lr / (1 - b1^t), sqrt(1 - b2^t)), t = 1 .. 2 steps.
+ *   rec    [2 steps][DMH_L0_REC] floats, 16-byte aligned.  Record i: 0 l0_i, 1 mask weight used, 2 adv_cost[0], 3 mask_cost[0]
+ *          (0 if mask_cost is NULL), 4 t = i + 1, 5 ratio was below the threshold; 6-7 zero.
+ *   cursor int32 [2]: cursor[0] = i, advanced by the launch; cursor[1] = its ticket counter, zero between launches.
+ *          A cursor outside 0 .. 2 steps - 1 makes the launch a no-op.
+ * mw_i = (float)count[i] / (float)count[0] <= thresh ? 0 : mask_wt.  pos, neg, m_*, v_* are updated in place; adv receives
+ * clamp(obj + clamp(pos,0,1) - clamp(neg,0,1), 0, 1) of the updated patterns.  All nine tensors hold C * HW floats and must
+ * not alias.  16-byte accesses when all nine are 16-byte aligned and HW % 4 == 0, a scalar form otherwise.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_L0_REC 8
+int dmh_l0_fused_step(const float* obj, float* pos, float* neg, float* m_pos, float* v_pos, float* m_neg, float* v_neg,
+                      const float* g_adv, float* adv, int32_t* count, float* rec, int32_t* cursor, const float* tab,
+                      const float* adv_cost, const float* mask_cost, int steps, int C, int HW, float mask_wt, float thresh,
+                      float l0_clip, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K5  L0 attack pieces (phy_obj_atk_l0.py).
  * compose (:94-99,:43-52): adv = clamp(obj + clamp(pos,0,1) - clamp(neg,0,1), 0, 1);
  *   l0_count (int32, zeroed by caller) += #pixels whose thresholded pattern is non-zero.
