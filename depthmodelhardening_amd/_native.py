@@ -81,6 +81,8 @@ _SIGNATURES = {
     "dmh_apgd_step": (C.c_int, [_fp] * 6 + [C.c_int, C.c_float, C.c_int64, _fp]),
     "dmh_apgd_commit": (C.c_int, [_fp] * 10 + [C.c_int] * 3 + [C.c_double, C.c_int64, _fp]),
     "dmh_l0_fused_step": (C.c_int, [_fp] * 15 + [C.c_int] * 3 + [C.c_float] * 3 + [_fp]),
+    "dmh_tube_light_compose": (C.c_int, [_fp] * 4 + [C.c_int] * 3 + [_fp]),
+    "dmh_tube_light_commit": (C.c_int, [_fp] * 4 + [C.c_int, _fp]),
     "dmh_l0_compose_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp]),
     "dmh_l0_compose_bwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp]),
     "dmh_l0_mask_partials_size": (C.c_int64, [C.c_int]),
@@ -208,6 +210,15 @@ def ptr(t):
         raise RuntimeError("libdmh_hip ops need contiguous tensors")
     if t.dtype not in (torch.float32, torch.int32, torch.uint8):
         raise RuntimeError("libdmh_hip ops compute in fp32; got %s" % t.dtype)
+    return C.c_void_p(t.data_ptr())
+
+
+def ptr_f64(t):
+    """Device pointer of a contiguous float64 CUDA tensor (K24's record table: the one float64 argument of the library)."""
+    if not t.is_cuda:
+        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % t.device)
+    if not t.is_contiguous() or t.dtype != torch.float64:
+        raise RuntimeError("libdmh_hip: expected a contiguous float64 tensor; got %s" % t.dtype)
     return C.c_void_p(t.data_ptr())
 
 

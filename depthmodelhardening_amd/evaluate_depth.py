@@ -6,7 +6,7 @@ import torch
 
 from . import ops
 from .datasets import make_object
-from .torchattacks import PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_l0
+from .torchattacks import PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_l0, Phy_obj_atk_light, Phy_obj_atk_vanila
 
 STEREO_SCALE_FACTOR = 5.4
 MIN_DEPTH = 1e-3
@@ -40,6 +40,10 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
                                    mask_wt=args["mask_wt"], l0_thresh=args["l0_thresh"])
     elif args['norm_type'] == "APGD":
         depth_atk = Phy_obj_atk_APGD(model2atk, obj_tensor, mask_tensor, eps=args['epsilon'], steps=args['step'])
+    elif args['norm_type'] == "light":      # :150-151; ``n_init`` / ``n_search``: the reference's literals 200 and 20
+        depth_atk = Phy_obj_atk_light(model2atk, obj_tensor, mask_tensor, n_init=args.get('n_init', 200),
+                                      n_search=args.get('n_search', 20))
+        vanila_atk = Phy_obj_atk_vanila(model2atk, obj_tensor, mask_tensor)
     elif args['norm_type'] == "image":
         depth_atk = PGD_depth(model2atk, eps=args['epsilon'], alpha=args['alpha'], steps=args['step'])
         depth_atk._targeted = True
@@ -50,11 +54,16 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
         data = SyntheticKITTIDataset(320, 1024, [0, "s"], 4, 1 << 30, device, seed=17, pool=max(8, args['batch_size']))
         scene_source = data.next_scenes
     errors = []
-    for _ in range(eval_count):
+    for i in range(eval_count):
         scene_img = scene_source(args['batch_size'])
         if args['norm_type'] == "image":
             adv_images, ben_images = depth_atk(scene_img)
             obj_masks_out = None
+        elif args['norm_type'] == "light":      # :178-182: the first batch runs the search, the others paste what it found
+            if i == 0:
+                adv_images, ben_images, obj_masks_out, obj_img_adv = depth_atk(scene_img, args['batch_size'], eval=True)
+            else:
+                adv_images, ben_images, obj_masks_out, _ = vanila_atk(scene_img, obj_img_adv, args['batch_size'], eval=True)
         else:
             adv_images, ben_images, obj_masks_out, _ = depth_atk(scene_img, args['batch_size'], eval=True)
         with torch.no_grad():

@@ -14,6 +14,8 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::pgd_linf_step        phy_obj_atk.py:98-101, pgd_depth.py:76-78         (K4)
     dmh::apgd_step            phy_obj_atk_apgd.py:207-215                       (K22, in place)
     dmh::apgd_commit          phy_obj_atk_apgd.py:255-290                       (K22, in place)
+    dmh::tube_light_compose   phy_obj_atk_light.py:130-138, light_simulation.py  (K24, writes ``out``)
+    dmh::tube_light_commit    phy_obj_atk_light.py:165-167                      (K24, in place)
     dmh::l0_fused_step        phy_obj_atk_l0.py:105-111,136-138,94-99           (K23, in place)
     dmh::l0_compose           phy_obj_atk_l0.py:94-99,43-52                     (K5)   + dmh::l0_compose_bwd
     dmh::l0_mask_cost         phy_obj_atk_l0.py:130-132                         (K5)   + dmh::l0_mask_cost_bwd
@@ -235,6 +237,27 @@ def l0_fused_step(obj: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, m_pos
 @l0_fused_step.register_fake
 def _(obj, pos, neg, m_pos, v_pos, m_neg, v_neg, g_adv, adv, count, rec, cursor, tab, adv_cost, mask_cost, steps, mask_wt, thresh,
       l0_clip):
+    return None
+
+
+# ---------------------------------------------------------------------------------------------------------------- K24
+@custom_op("dmh::tube_light_compose", mutates_args=("out",))
+def tube_light_compose(table: torch.Tensor, index: torch.Tensor, base_u8: torch.Tensor, out: torch.Tensor) -> None:
+    ops.tube_light_compose(table, index, base_u8, out)
+
+
+@tube_light_compose.register_fake
+def _(table, index, base_u8, out):
+    return None
+
+
+@custom_op("dmh::tube_light_commit", mutates_args=("cost", "best", "state"))
+def tube_light_commit(cost_in: torch.Tensor, cost: torch.Tensor, best: torch.Tensor, state: torch.Tensor) -> None:
+    ops.tube_light_commit(cost_in, cost, best, state)
+
+
+@tube_light_commit.register_fake
+def _(cost_in, cost, best, state):
     return None
 
 
@@ -521,4 +544,4 @@ smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
-       "apgd_step", "apgd_commit", "l0_fused_step")
+       "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit")

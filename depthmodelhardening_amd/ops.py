@@ -9,6 +9,7 @@ import ctypes as C
 import os
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -569,6 +570,95 @@ def apgd_commit(x_adv, g_new, grad, x_best, grad_best, x_ret, loss, ctl, hist, c
                                     N.ptr(loss), N.ptr(ctl), N.ptr(hist), N.ptr(cursor), int(steps), int(size_decr),
                                     int(steps_min), float(rho), n, N.stream()))
     return x_adv
+
+
+LIGHT_REC = 10      # doubles per query record (DMH_LIGHT_REC)
+
+
+def tube_light_table(params, alpha=1.0):
+    """Host: the record array [n, 10] float64 of K24 for ``params`` [n, 4] = (wavelength, angle, b, beta) per query.  Every scalar
+    is made in float64 the way the reference's Python makes it: k = round(tan(radians(angle)), 2) (phy_obj_atk_light.py:130-131),
+    full_end = int(sqrt(beta) + 0.5), light_end = int(sqrt(beta * 20) + 0.5), the divisor sqrt(1 + k k) and the colour of
+    wavelength_to_rgb with its ``** 0.8`` times alpha (light_simulation.py:40-84,143-146,150)."""
+    import math
+    params = np.asarray(params).reshape(-1, 4)
+    out = np.zeros((len(params), LIGHT_REC), dtype=np.float64)
+    for row, (wl, angle, b, beta) in zip(out, params.tolist()):
+        k = round(math.tan(math.radians(angle)), 2)
+        w, g = float(wl), 0.8
+        if 380 <= w <= 440:         # the first matching band wins at a shared boundary
+            att = 0.3 + 0.7 * (w - 380) / (440 - 380)
+            c = (((-(w - 440) / (440 - 380)) * att) ** g, 0.0, (1.0 * att) ** g)
+        elif 440 <= w <= 490:
+            c = (0.0, ((w - 440) / (490 - 440)) ** g, 1.0)
+        elif 490 <= w <= 510:
+            c = (0.0, 1.0, (-(w - 510) / (510 - 490)) ** g)
+        elif 510 <= w <= 580:
+            c = (((w - 510) / (580 - 510)) ** g, 1.0, 0.0)
+        elif 580 <= w <= 645:
+            c = (1.0, (-(w - 645) / (645 - 580)) ** g, 0.0)
+        elif 645 <= w <= 750:
+            c = ((1.0 * (0.3 + 0.7 * (750 - w) / (750 - 645))) ** g, 0.0, 0.0)
+        else:
+            c = (0.0, 0.0, 0.0)
+        row[:9] = (k, b, beta, int(math.sqrt(beta) + 0.5), int(math.sqrt(beta * 20) + 0.5), math.sqrt(1 + k * k),
+                   c[0] * alpha, c[1] * alpha, c[2] * alpha)
+    return out
+
+
+def tube_light_host(base_hwc, rec):
+    """Host twin of K24's compose in numpy (``Phy_obj_atk_light(host_chain=True)``): uint8 [H, W, 3] base and one record ->
+    the lit uint8 [H, W, 3], float64 / fp32 with the roundings of the reference's chain."""
+    h, w, _ = base_hwc.shape
+    k, b, beta, full, end, s = (rec[i] for i in range(6))
+    d = np.abs(k * np.arange(w, dtype=np.float64)[None, :] - np.arange(h, dtype=np.float64)[:, None] + b) / s
+    with np.errstate(divide="ignore", invalid="ignore"):
+        att = np.where(d <= full, 1.0, np.where(d <= end, beta / (d * d), 0.0))
+    lit = (np.stack([rec[6 + i] * att for i in range(3)], -1) * 255.0).astype(np.float32)
+    return np.clip(base_hwc.astype(np.float32) + lit, 0.0, 255.0).astype(np.uint8)
+
+
+def tube_light_state(n_queries, device):
+    """Device state of one tube-light search (K24): (state int32 [2] = (cursor 0, best query -1), best float [1] = 1e10,
+    cost float [n_queries] zeros)."""
+    if int(n_queries) < 1:
+        raise RuntimeError("tube_light_state: need at least one query")
+    state = torch.tensor([0, -1], dtype=torch.int32).to(device, non_blocking=True)
+    best = torch.full((1,), 1e10, device=device, dtype=torch.float32)
+    return state, best, torch.zeros(int(n_queries), device=device, dtype=torch.float32)
+
+
+def tube_light_compose(table, index, base_u8, out=None):
+    """The object lit by the tube light of record ``index[0]`` (a device int32: nothing of the query comes from the host) of
+    ``table`` [n, 10] float64: ``base_u8`` [1 or no batch, 3, H, W] uint8 -> fp32 [1, 3, H, W], bit-equal to the reference's
+    numpy / OpenCV / PIL chain.  An index outside [0, n) leaves ``out`` as it is."""
+    if table.dim() != 2 or table.shape[1] != LIGHT_REC:
+        raise RuntimeError("tube_light_compose: table must be [n, %d] float64" % LIGHT_REC)
+    if index.dtype != torch.int32 or index.numel() < 1:
+        raise RuntimeError("tube_light_compose: index must be int32")
+    if base_u8.dtype != torch.uint8 or base_u8.numel() % 3 or base_u8.dim() < 3 or base_u8.shape[-3] != 3 \
+            or base_u8.numel() != 3 * base_u8.shape[-2] * base_u8.shape[-1]:
+        raise RuntimeError("tube_light_compose: base must be uint8 [3, H, W]")
+    H, W = int(base_u8.shape[-2]), int(base_u8.shape[-1])
+    if out is None:
+        out = torch.zeros((1, 3, H, W), device=base_u8.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.numel() != base_u8.numel():
+        raise RuntimeError("tube_light_compose: out must be fp32 of the base's size")
+    N.check(N.lib().dmh_tube_light_compose(N.ptr_f64(table), N.ptr(index), N.ptr(base_u8), N.ptr(out), int(table.shape[0]), H, W,
+                                           N.stream()))
+    return out
+
+
+def tube_light_commit(cost_in, cost, best, state):
+    """In place, on the device (phy_obj_atk_light.py:165-167): the query the cursor state[0] points at gets ``cost_in`` (device
+    scalar) into ``cost``; a strictly smaller cost than ``best`` becomes the best and its query state[1]; the cursor advances."""
+    if cost_in.numel() != 1 or cost_in.dtype != torch.float32 or best.numel() != 1 or best.dtype != torch.float32 \
+            or cost.dtype != torch.float32:
+        raise RuntimeError("tube_light_commit: cost_in and best must be one fp32 value each, cost fp32")
+    if state.dtype != torch.int32 or state.numel() < 2:
+        raise RuntimeError("tube_light_commit: state must be int32[2]")
+    N.check(N.lib().dmh_tube_light_commit(N.ptr(cost_in), N.ptr(cost), N.ptr(best), N.ptr(state), int(cost.numel()), N.stream()))
+    return state
 
 
 class _L0Compose(torch.autograd.Function):

@@ -1,1 +1,3 @@
 from .phy_obj_atk_apgd import Phy_obj_atk_APGD  # noqa: F401
+from .phy_obj_atk_light import Phy_obj_atk_light  # noqa: F401
+from .phy_obj_atk_vanila import Phy_obj_atk_vanila  # noqa: F401

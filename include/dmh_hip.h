@@ -249,6 +249,25 @@ int dmh_l0_fused_step(const float* obj, float* pos, float* neg, float* m_pos, fl
                       float l0_clip, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K24  Tube-light object attack (a random search): the lit patch and the "keep the best" step, driven from device memory.
+ * Replaces: phy_obj_atk_light.py:130-138 with light_simulation.py:23-28,:124-163 (compose), :165-167 (commit).
+ *   table  [n_queries][DMH_LIGHT_REC] doubles, made on the host in float64: 0 k, 1 b, 2 beta, 3 full_end = int(sqrt(beta) + .5),
+ *          4 light_end = int(sqrt(20 beta) + .5), 5 sqrt(1 + k k), 6-8 c[i] * alpha (wavelength_to_rgb), 9 zero.
+ *   index  int32[>= 1]: compose lights the object with record index[0]; an index outside [0, n_queries) makes it a no-op.
+ *   base   uint8 [3][H][W]: the clean object, trunc(obj * 255).   out: float [3][H][W] = uint8 result / 255.
+ *   state  int32[2]: 0 the cursor (the caller zeroes it), 1 the best query (the caller sets -1).  best: float[1], 1e10 at start.
+ * compose: d = |k x - y + b| / s;  att = d <= full_end ? 1 : d <= light_end ? beta / (d d) : 0;  v = (c att) 255.0, all in
+ *          double, every operation rounded on its own; out = trunc(clip((float)base + (float)v, 0, 255)) / 255 in fp32:
+ *          bit-equal to the reference's chain.  16-byte stores when W % 4 == 0, base is 4-byte and out 16-byte aligned.
+ * commit:  q = state[0]; cost[q] <- cost_in[0]; if cost_in[0] < best[0]: best[0] <- it, state[1] <- q; state[0] <- q + 1.
+ *          A cursor outside [0, n_queries) makes it a no-op.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_LIGHT_REC 10
+int dmh_tube_light_compose(const double* table, const int32_t* index, const uint8_t* base, float* out, int n_queries, int H,
+                           int W, void* stream);
+int dmh_tube_light_commit(const float* cost_in, float* cost, float* best, int32_t* state, int n_queries, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K5  L0 attack pieces (phy_obj_atk_l0.py).
  * compose (:94-99,:43-52): adv = clamp(obj + clamp(pos,0,1) - clamp(neg,0,1), 0, 1);
  *   l0_count (int32, zeroed by caller) += #pixels whose thresholded pattern is non-zero.
