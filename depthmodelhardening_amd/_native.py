@@ -83,6 +83,13 @@ _SIGNATURES = {
     "dmh_l0_fused_step": (C.c_int, [_fp] * 15 + [C.c_int] * 3 + [C.c_float] * 3 + [_fp]),
     "dmh_tube_light_compose": (C.c_int, [_fp] * 4 + [C.c_int] * 3 + [_fp]),
     "dmh_tube_light_commit": (C.c_int, [_fp] * 4 + [C.c_int, _fp]),
+    "dmh_eigen_select_ws_size": (C.c_int64, [C.c_int]),
+    "dmh_eigen_partials_size": (C.c_int64, [C.c_int]),
+    "dmh_eigen_gt_stats": (C.c_int, [_fp, C.c_int64, _fp, _fp] + [C.c_int] * 7 + [_fp] * 4),
+    "dmh_eigen_pred_depth": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, C.c_int64, _fp, _fp] + [C.c_int] * 7
+                             + [C.c_float, C.c_int64, _fp, C.c_int64, _fp, _fp]),
+    "dmh_eigen_pred_ratio": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, _fp] + [C.c_int] * 6 + [_fp] * 5),
+    "dmh_eigen_metrics": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, _fp, _fp] + [C.c_int] * 6 + [_fp] * 4),
     "dmh_l0_compose_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _fp, _fp]),
     "dmh_l0_compose_bwd": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp]),
     "dmh_l0_mask_partials_size": (C.c_int64, [C.c_int]),

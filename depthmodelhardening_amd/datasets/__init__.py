@@ -1,3 +1,3 @@
-from .synthetic import SyntheticKITTIDataset, kitti_like, make_object
+from .synthetic import SyntheticEvalSet, SyntheticKITTIDataset, kitti_like, make_object
 
-__all__ = ["SyntheticKITTIDataset", "kitti_like", "make_object"]
+__all__ = ["SyntheticEvalSet", "SyntheticKITTIDataset", "kitti_like", "make_object"]

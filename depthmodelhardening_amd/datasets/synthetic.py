@@ -258,3 +258,35 @@ class SyntheticKITTIDataset(object):
             cam["stereo_T"] = T.contiguous()
             self._cam_cache = (batch_size, cam)
         return dict(self._cam_cache[1])
+
+
+class SyntheticEvalSet(object):
+    """A small test set for ``evaluate_depth.evaluate`` when there is no KITTI on disk: ``n`` seeded frames [3, height, width]
+    on the device (``frames()`` yields them in batches, the last one short) and ``gt_depths``, one LiDAR-like ground-truth map
+    per frame as the reference's ``gt_depths.npz`` holds them: fp32, of KITTI's own ragged sizes (around 375 x 1242), zero
+    except at a few percent of the pixels of the lower two thirds, which carry 1 - 90 m of a smooth field -- so that the
+    1e-3 .. 80 m range mask and the Eigen crop both bite."""
+
+    SIZES = ((375, 1242), (370, 1226), (374, 1238), (376, 1241), (370, 1224))     # the sizes of KITTI raw's drives
+
+    def __init__(self, n, height, width, device, seed=1234, batch_size=16, sizes=None, valid_frac=0.045):
+        self.n, self.batch_size, self.device = int(n), int(batch_size), torch.device(device)
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        self.images = kitti_like(self.n, 3, height, width, self.device, gen)
+        rng = np.random.RandomState(seed)
+        sizes = sizes or self.SIZES
+        self.gt_depths = []
+        for i in range(self.n):
+            gh, gw = sizes[i % len(sizes)]
+            # a smooth field: depth falls from the horizon row to the bottom row, with a lateral wave and per-map phase
+            ys, xs = np.meshgrid(np.linspace(0, 1, gh), np.linspace(0, 1, gw), indexing="ij")
+            field = 90.0 ** (1.0 - np.clip((ys - 0.3) / 0.7, 0, 1)) * (1 + 0.15 * np.sin(6.3 * (xs + rng.rand())))
+            hit = (rng.rand(gh, gw) < valid_frac) & (ys > 0.33)
+            self.gt_depths.append(np.where(hit, np.clip(field, 1.0, 90.0), 0.0).astype(np.float32))
+
+    def __len__(self):
+        return self.n
+
+    def frames(self):
+        for i in range(0, self.n, self.batch_size):
+            yield self.images[i:i + self.batch_size]

@@ -1,11 +1,21 @@
-"""In-training attack evaluation: the reference's ``MD2/evaluate_depth.py`` pieces that ``Trainer.val`` reaches
-(``trainer.py:454-465``): ``compute_errors`` :57-99 and ``evaluate_attacks`` :113-214, with the metric pass fused on the
-device (K8, ops.masked_depth_errors) instead of D2H copies + eight numpy reductions per batch."""
+"""Evaluation: the reference's ``MD2/evaluate_depth.py``.  The pieces ``Trainer.val`` reaches (``trainer.py:454-465``):
+``compute_errors`` :57-99 and ``evaluate_attacks`` :113-214, with the metric pass fused on the device (K8,
+ops.masked_depth_errors) instead of D2H copies + eight numpy reductions per batch.  And the benign protocol ``evaluate`` :245-395:
+resize to every ground-truth map's own size, Eigen crop and range mask, median scaling, eight metrics -- on the device (K25,
+ops.eigen_depth_errors), one copy to the host at the end.
+
+    python -m depthmodelhardening_amd.evaluate_depth --eval_mono --dataset synthetic [--post_process] [--synthetic_len 16]
+    python -m depthmodelhardening_amd.evaluate_depth --eval_stereo --ext_disp_to_eval disps.npy --eval_gt_path gt_depths.npz
+"""
+import os
+
 import numpy as np
 import torch
 
 from . import ops
 from .datasets import make_object
+from .layers import disp_to_depth
+from .my_utils import to_device_async
 from .torchattacks import PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_l0, Phy_obj_atk_light, Phy_obj_atk_vanila
 
 STEREO_SCALE_FACTOR = 5.4
@@ -79,3 +89,152 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
     print("Max Error:\n  " + ("{:>8} | " * 8).format(*names))
     print(("&{: 8.3f}  " * 8).format(*max_errors.tolist()) + "\\\\")
     return mean_errors
+
+
+ERROR_NAMES = ("abs_err", "abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
+EVAL_BATCH = 16     # the reference's DataLoader batch (:269)
+
+
+def batch_post_process_disparity(l_disp, r_disp):
+    """:102-110 on [n, h, w] tensors, in float64 as the reference's numpy masks make it.  Used where the blended disparities
+    themselves are wanted (--save_pred_disps); the evaluation blends inside K25."""
+    w = l_disp.shape[-1]
+    pos = torch.linspace(0, 1, w, dtype=torch.float64, device=l_disp.device)
+    l_mask = 1.0 - torch.clamp(20 * (pos - 0.05), 0, 1)
+    r_mask = l_mask.flip(0)
+    m_disp = (0.5 * (l_disp + r_disp)).double()
+    return r_mask * l_disp + l_mask * r_disp + (1.0 - l_mask - r_mask) * m_disp
+
+
+def load_gt_depths(path):
+    """The reference's ``gt_depths.npz`` (:335-336): an object array ``data`` of 2-D maps."""
+    return list(np.load(path, fix_imports=True, encoding='latin1', allow_pickle=True)["data"])
+
+
+def evaluate(opt, encoder, depth_decoder, encoder_dict, frames=None, gt_depths=None):
+    """Evaluates a model on a test set (MD2/evaluate_depth.py:245-395) and returns the mean of the eight metrics.
+
+    ``frames``: an iterable of [n, 3, h, w] device batches (n <= 64; the reference's DataLoader gives 16 and a short last one) in
+    place of KITTIRAWDataset; ``gt_depths``: a sequence of 2-D maps of their own sizes, an ``ops.EigenGtPack`` made from one, or
+    the path of the reference's ``gt_depths.npz``.  The loop enqueues everything and reads nothing back: the per-image errors
+    and ratios of all batches come to the host in one copy after the last batch.  --no_eval returns None after saving."""
+    assert sum((opt.eval_mono, opt.eval_stereo)) == 1, \
+        "Please choose mono or stereo evaluation by setting either --eval_mono or --eval_stereo"
+    if opt.eval_split == "benchmark":
+        raise NotImplementedError("--eval_split benchmark (PNG export through OpenCV, :318-333) is out of scope (DESIGN.md section 8)")
+    if getattr(opt, "eval_eigen_to_benchmark", False):
+        raise NotImplementedError("--eval_eigen_to_benchmark (:302-306) is out of scope (DESIGN.md section 8)")
+    save = bool(opt.save_pred_disps)
+    if opt.eval_stereo:     # :340-344; set before the loop here because the loop already evaluates
+        scale_factor, median_scaling = STEREO_SCALE_FACTOR, False
+    else:
+        scale_factor, median_scaling = opt.pred_depth_scale_factor, not opt.disable_median_scaling
+    pack = None
+    if not opt.no_eval:     # the ground truth goes to the device once, before the first launch
+        if gt_depths is None:
+            raise RuntimeError("evaluate: no ground truth (gt_depths: a sequence of maps or the path of a gt_depths.npz)")
+        if isinstance(gt_depths, ops.EigenGtPack):
+            pack = gt_depths
+            if pack.eval_split != opt.eval_split:
+                raise RuntimeError("evaluate: the pack was made for split %r, not %r" % (pack.eval_split, opt.eval_split))
+        else:
+            maps = load_gt_depths(gt_depths) if isinstance(gt_depths, (str, os.PathLike)) else gt_depths
+            params = [p for m in (encoder, depth_decoder) if isinstance(m, torch.nn.Module) for p in m.parameters()]
+            pack = ops.eigen_gt_pack(maps, opt.eval_split, params[0].device if params else torch.device("cuda"))
+
+    results, saved, first = [], [], 0
+
+    def enqueue(disp, flip):
+        nonlocal first
+        if not opt.no_eval:
+            errors, ratios = ops.eigen_depth_errors(disp, pack, first, pred_disp_flip=flip, scale_factor=scale_factor,
+                                                    median_scaling=median_scaling)
+            results.append(torch.cat([errors, ratios[:, None]], 1))
+        first += disp.shape[0]
+
+    if opt.ext_disp_to_eval is None:
+        if frames is None:
+            raise RuntimeError("evaluate: no frames (an iterable of [n, 3, h, w] device batches)")
+        print("-> Computing predictions with size {}x{}".format(encoder_dict['width'], encoder_dict['height']))
+        with torch.no_grad():
+            for input_color in frames:
+                n = input_color.shape[0]
+                if not opt.no_eval and first + n > len(pack):
+                    raise RuntimeError("evaluate: more predictions than the %d ground-truth maps" % len(pack))
+                if opt.post_process:    # :280-282: two forward passes per image
+                    input_color = torch.cat((input_color, torch.flip(input_color, [3])), 0)
+                output = depth_decoder(encoder(input_color))
+                pred_disp, _ = disp_to_depth(output[("disp", 0)], opt.min_depth, opt.max_depth)
+                pred_disp = pred_disp[:, 0].contiguous()
+                flip = pred_disp[n:] if opt.post_process else None
+                pred_disp = pred_disp[:n]
+                if save:
+                    saved.append(batch_post_process_disparity(pred_disp, flip.flip(2)) if opt.post_process else pred_disp)
+                enqueue(pred_disp, flip)
+        pred_disps = torch.cat(saved).cpu().numpy() if save else None
+    else:
+        print("-> Loading predictions from {}".format(opt.ext_disp_to_eval))
+        pred_disps = np.load(opt.ext_disp_to_eval)
+        if not opt.no_eval:
+            if pred_disps.shape[0] != len(pack):
+                raise RuntimeError("evaluate: %d predictions but %d ground-truth maps" % (pred_disps.shape[0], len(pack)))
+            for i in range(0, pred_disps.shape[0], EVAL_BATCH):
+                enqueue(to_device_async(np.ascontiguousarray(pred_disps[i:i + EVAL_BATCH], dtype=np.float32), pack.gt.device), None)
+    if save:
+        output_path = os.path.join(os.path.expanduser(opt.load_weights_folder), "disps_{}_split.npy".format(opt.eval_split))
+        print("-> Saving predicted disparities to ", output_path)
+        np.save(output_path, pred_disps)
+    if opt.no_eval:
+        print("-> Evaluation disabled. Done.")
+        return None
+    if first != len(pack):
+        raise RuntimeError("evaluate: %d predictions but %d ground-truth maps" % (first, len(pack)))
+    print("-> Evaluating")
+    if opt.eval_stereo:
+        print("   Stereo evaluation - "
+              "disabling median scaling, scaling by {}".format(STEREO_SCALE_FACTOR))
+        opt.disable_median_scaling = True
+        opt.pred_depth_scale_factor = STEREO_SCALE_FACTOR
+    else:
+        print("   Mono evaluation - using median scaling")
+    table = torch.cat(results).cpu().numpy().astype(np.float64)     # the one copy: [images, 8 errors + ratio]
+    errors, ratios = table[:, :8], table[:, 8]
+    if median_scaling:
+        med = np.median(ratios)
+        print(" Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
+    mean_errors = errors.mean(0)
+    print("\n  " + ("{:>8} | " * 8).format(*ERROR_NAMES))
+    print(("&{: 8.3f}  " * 8).format(*mean_errors.tolist()) + "\\\\")
+    print("\n-> Done!")
+    return mean_errors
+
+
+def main(argv=None):
+    from .depth_model import import_depth_model
+    from .options import MonodepthOptions
+    opt = MonodepthOptions().parse(argv)
+    device = torch.device("cuda")
+    frames = gt_depths = encoder = decoder = None
+    if opt.dataset == "synthetic" and opt.eval_gt_path is None:
+        from .datasets import SyntheticEvalSet
+        data = SyntheticEvalSet(opt.synthetic_len, 320, 1024, device, seed=opt.seed, batch_size=EVAL_BATCH)
+        frames, gt_depths = data.frames(), data.gt_depths
+    else:
+        gt_depths = opt.eval_gt_path
+        if opt.ext_disp_to_eval is None:
+            if opt.eval_frames_path is None:
+                raise RuntimeError("no KITTI loader here: give --eval_frames_path (an .npy of [N, 3, 320, 1024] frames in [0, 1]) or "
+                                   "--ext_disp_to_eval, or use --dataset synthetic")
+            images = np.load(opt.eval_frames_path, mmap_mode="r")
+            frames = (torch.from_numpy(np.ascontiguousarray(images[i:i + EVAL_BATCH], dtype=np.float32)).to(device)
+                      for i in range(0, images.shape[0], EVAL_BATCH))
+    if opt.ext_disp_to_eval is None:
+        model = import_depth_model((1024, 320), pre_model_path=opt.load_weights_folder).to(device).eval()
+        encoder, decoder = model.encoder, model.decoder
+    if opt.load_weights_folder is None and opt.save_pred_disps:
+        raise RuntimeError("--save_pred_disps writes into --load_weights_folder")
+    return evaluate(opt, encoder, decoder, {"height": 320, "width": 1024}, frames=frames, gt_depths=gt_depths)
+
+
+if __name__ == "__main__":
+    main()

@@ -17,6 +17,8 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::tube_light_compose   phy_obj_atk_light.py:130-138, light_simulation.py  (K24, writes ``out``)
     dmh::tube_light_commit    phy_obj_atk_light.py:165-167                      (K24, in place)
     dmh::l0_fused_step        phy_obj_atk_l0.py:105-111,136-138,94-99           (K23, in place)
+    dmh::eigen_gt_stats       MD2/evaluate_depth.py:360-373,377 (ground truth)  (K25)
+    dmh::eigen_depth_errors   MD2/evaluate_depth.py:351-384, :102-110, :61-76   (K25)
     dmh::l0_compose           phy_obj_atk_l0.py:94-99,43-52                     (K5)   + dmh::l0_compose_bwd
     dmh::l0_mask_cost         phy_obj_atk_l0.py:130-132                         (K5)   + dmh::l0_mask_cost_bwd
     dmh::photo_smooth_loss    MD2/trainer.py:472-523,539-674 (DH/trainer.py:638-741 with variant 1)   (K1 + K2 + finalise)
@@ -259,6 +261,33 @@ def tube_light_commit(cost_in: torch.Tensor, cost: torch.Tensor, best: torch.Ten
 @tube_light_commit.register_fake
 def _(cost_in, cost, best, state):
     return None
+
+
+# ---------------------------------------------------------------------------------------------------------------- K25
+@custom_op("dmh::eigen_gt_stats", mutates_args=())
+def eigen_gt_stats(gt: torch.Tensor, table: torch.Tensor, blk_img: torch.Tensor, first: int, n: int, b0: int, grid: int,
+                   eigen: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.eigen_gt_stats(_cu(gt), _cu(table), _cu(blk_img), first, n, b0, grid, eigen)
+
+
+@eigen_gt_stats.register_fake
+def _(gt, table, blk_img, first, n, b0, grid, eigen):
+    return gt.new_empty((n,)), table.new_empty((n,))
+
+
+@custom_op("dmh::eigen_depth_errors", mutates_args=())
+def eigen_depth_errors(pred_disp: torch.Tensor, pred_disp_flip: Optional[torch.Tensor], gt: torch.Tensor, table: torch.Tensor,
+                       blk_img: torch.Tensor, med_gt: torch.Tensor, first: int, b0: int, grid: int, px0: int, npx: int,
+                       eigen: bool, scale_factor: float,
+                       median_scaling: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.eigen_depth_errors_launch(pred_disp, pred_disp_flip, _cu(gt), _cu(table), _cu(blk_img), _cu(med_gt), first, b0, grid,
+                                         px0, npx, eigen, scale_factor, median_scaling)
+
+
+@eigen_depth_errors.register_fake
+def _(pred_disp, pred_disp_flip, gt, table, blk_img, med_gt, first, b0, grid, px0, npx, eigen, scale_factor, median_scaling):
+    n = pred_disp.shape[0]
+    return pred_disp.new_empty((n, 8)), pred_disp.new_empty((n,)), pred_disp.new_empty((npx,)), pred_disp.new_empty((n,))
 
 
 # ----------------------------------------------------------------------------------------------------------------- K5
@@ -544,4 +573,5 @@ smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
-       "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit")
+       "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
+       "eigen_gt_stats", "eigen_depth_errors")

@@ -2623,3 +2623,169 @@ def masked_depth_errors(disp_gt, disp_pred, mask=None, min_depth=0.1, max_depth=
                                         min_depth, max_depth, scale, clamp_lo, clamp_hi, N.ptr(part), N.ptr(out),
                                         N.stream()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- K25
+EIGEN_REC, EIGEN_CHUNK, EIGEN_MAX_BATCH = 8, 8192, 64       # DMH_EIGEN_* of include/dmh_hip.h
+
+
+def eigen_crop(gt_h, gt_w):
+    """The Eigen crop (y0, y1, x0, x1) of a gt_h x gt_w map, in double and truncated as MD2/evaluate_depth.py:363-364 does."""
+    return np.array([0.40810811 * gt_h, 0.99189189 * gt_h, 0.03594771 * gt_w, 0.96405229 * gt_w]).astype(np.int32)
+
+
+def _eigen_f32(t, name):
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise RuntimeError("libdmh_hip ops compute in fp32; got %s for %s" % (getattr(t, "dtype", type(t)), name))
+    return t
+
+
+def _eigen_i32(t, name):
+    if not torch.is_tensor(t) or t.dtype != torch.int32:
+        raise RuntimeError("%s must be int32; got %s" % (name, getattr(t, "dtype", type(t))))
+    return t
+
+
+def _eigen_ws(n, device):
+    return torch.empty(N.lib().dmh_eigen_select_ws_size(n), device=device, dtype=torch.int32)
+
+
+def eigen_gt_stats(gt, table, blk_img, first, n, b0, grid, eigen):
+    """K25 on the ground truth alone: (medians fp32 [n], valid counts int32 [n]) of the images first .. first + n - 1 of a pack
+    (np.median of the valid values; NaN and 0 for a map without a valid pixel).  Three histogram passes, no sort."""
+    lib = N.lib()
+    _eigen_f32(gt, "gt"), _eigen_i32(table, "table"), _eigen_i32(blk_img, "blk_img")
+    if not 0 < n <= EIGEN_MAX_BATCH:
+        raise RuntimeError("eigen_gt_stats: 1 .. %d images per call; got %d" % (EIGEN_MAX_BATCH, n))
+    med = torch.empty(n, device=gt.device, dtype=torch.float32)
+    cnt = torch.empty(n, device=gt.device, dtype=torch.int32)
+    ws = _eigen_ws(n, gt.device)
+    N.check(lib.dmh_eigen_gt_stats(N.ptr(gt), gt.numel(), N.ptr(table), N.ptr(blk_img), int(table.shape[0]), blk_img.numel(),
+                                   int(first), int(n), int(b0), int(grid), int(bool(eigen)), N.ptr(ws), N.ptr(med), N.ptr(cnt),
+                                   N.stream()))
+    return med, cnt
+
+
+def eigen_depth_errors_launch(pred_disp, pred_disp_flip, gt, table, blk_img, med_gt, first, b0, grid, px0, npx, eigen,
+                              scale_factor=1.0, median_scaling=True):
+    """K25's launches for one batch on plain tensors (what ``eigen_depth_errors`` and ``torch.ops.dmh.eigen_depth_errors`` share):
+    (errors [n, 8], ratios [n], depth [npx], medians of the valid depths [n]).  ``px0`` / ``npx``: offset and pixel count of the
+    batch inside ``gt``; ``b0`` / ``grid``: its work blocks.  Without median scaling the medians are not computed: they and
+    ``ratios`` are NaN."""
+    lib = N.lib()
+    _eigen_f32(pred_disp, "pred_disp"), _eigen_f32(gt, "gt"), _eigen_f32(med_gt, "med_gt")
+    _eigen_i32(table, "table"), _eigen_i32(blk_img, "blk_img")
+    if pred_disp.dim() != 3:
+        raise RuntimeError("eigen_depth_errors: pred_disp must be [n, h, w]")
+    n, h, w = [int(v) for v in pred_disp.shape]
+    if not 0 < n <= EIGEN_MAX_BATCH:
+        raise RuntimeError("eigen_depth_errors: 1 .. %d predictions per call; got %d" % (EIGEN_MAX_BATCH, n))
+    if pred_disp_flip is not None and (_eigen_f32(pred_disp_flip, "pred_disp_flip").shape != pred_disp.shape):
+        raise RuntimeError("eigen_depth_errors: pred_disp_flip must have pred_disp's shape")
+    if med_gt.numel() != table.shape[0] or table.dim() != 2 or table.shape[1] != EIGEN_REC:
+        raise RuntimeError("eigen_depth_errors: table must be [N, %d] and med_gt [N]" % EIGEN_REC)
+    if px0 < 0 or npx <= 0 or px0 + npx > gt.numel():
+        raise RuntimeError("eigen_depth_errors: the batch's pixels must lie in gt")
+    dev = pred_disp.device
+    pred_disp = _c(pred_disp.detach())
+    flip = None if pred_disp_flip is None else _c(pred_disp_flip.detach())
+    depth = torch.empty(int(npx), device=dev, dtype=torch.float32)
+    errors = torch.empty((n, 8), device=dev, dtype=torch.float32)
+    part = torch.empty(lib.dmh_eigen_partials_size(int(grid)), device=dev, dtype=torch.float32)
+    ws = _eigen_ws(n, dev) if median_scaling else None
+    sizes = (int(table.shape[0]), blk_img.numel(), int(first), n, int(b0), int(grid))
+    N.check(lib.dmh_eigen_pred_depth(N.ptr(pred_disp), N.ptr(flip), h, w, N.ptr(gt), gt.numel(), N.ptr(table), N.ptr(blk_img),
+                                     *sizes, int(bool(eigen)), float(scale_factor), int(px0), N.ptr(depth), depth.numel(),
+                                     N.ptr(ws), N.stream()))
+    if median_scaling:
+        med = torch.empty(n, device=dev, dtype=torch.float32)
+        ratios = torch.empty(n, device=dev, dtype=torch.float32)
+        N.check(lib.dmh_eigen_pred_ratio(N.ptr(depth), depth.numel(), int(px0), gt.numel(), N.ptr(table), N.ptr(blk_img), *sizes,
+                                         N.ptr(ws), N.ptr(med_gt), N.ptr(med), N.ptr(ratios), N.stream()))
+    else:
+        ratios = torch.full((n,), float("nan"), device=dev, dtype=torch.float32)
+        med = ratios.clone()
+    N.check(lib.dmh_eigen_metrics(N.ptr(gt), gt.numel(), N.ptr(depth), depth.numel(), int(px0), N.ptr(table), N.ptr(blk_img),
+                                  *sizes, N.ptr(ratios if median_scaling else None), N.ptr(part), N.ptr(errors), N.stream()))
+    return errors, ratios, depth, med
+
+
+class EigenGtPack(object):
+    """The ground truth of an evaluation set on the device (``eigen_gt_pack``): ``gt`` the maps one after the other (fp32),
+    ``table`` / ``blk_img`` K25's tables, ``counts`` / ``medians`` the valid pixels and np.median of the valid values of every map
+    (they depend on the ground truth only: computed once, here).  Host copies: ``shapes``, ``crops`` (y0, y1, x0, x1),
+    ``offsets`` [N + 1] and ``blk_first`` [N + 1]."""
+
+    def __init__(self, gt, table, blk_img, shapes, crops, offsets, blk_first, eval_split):
+        self.gt, self.table, self.blk_img = gt, table, blk_img
+        self.shapes, self.crops, self.offsets, self.blk_first = shapes, crops, offsets, blk_first
+        self.eval_split, self.eigen = eval_split, eval_split == "eigen"
+        self.counts = self.medians = None
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def view(self, flat, first, i):
+        """Image ``first + i`` of a batch's flat buffer (``return_pred``) as [gt_h, gt_w]."""
+        o = int(self.offsets[first + i] - self.offsets[first])
+        gh, gw = self.shapes[first + i]
+        return flat[o:o + gh * gw].view(gh, gw)
+
+
+def eigen_gt_pack(gt_list, eval_split, device):
+    """Packs the 2-D ground-truth maps ``gt_list`` (their own, different sizes) for K25: one flat fp32 buffer, the record table
+    (crop bounds of MD2/evaluate_depth.py:363-364 for split ``eigen``, the whole map otherwise), and per map the number of valid
+    pixels and the median of the valid values."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % device)
+    maps = [np.ascontiguousarray(np.asarray(g), dtype=np.float32) for g in gt_list]
+    if not maps or any(m.ndim != 2 or m.size == 0 for m in maps):
+        raise RuntimeError("eigen_gt_pack: need at least one ground-truth map, all of them 2-D and not empty")
+    shapes = [tuple(int(v) for v in m.shape) for m in maps]
+    sizes = np.array([h * w for h, w in shapes], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    blocks = (sizes + EIGEN_CHUNK - 1) // EIGEN_CHUNK
+    blk_first = np.concatenate([[0], np.cumsum(blocks)])
+    if offsets[-1] >= 2 ** 31:
+        raise RuntimeError("eigen_gt_pack: %d pixels; a pack holds fewer than 2^31" % offsets[-1])
+    eigen = eval_split == "eigen"
+    crops = np.stack([eigen_crop(h, w) if eigen else np.array([0, h, 0, w], dtype=np.int32) for h, w in shapes])
+    table = np.zeros((len(maps), EIGEN_REC), dtype=np.int32)
+    table[:, 0], table[:, 1], table[:, 2] = offsets[:-1], [s[0] for s in shapes], [s[1] for s in shapes]
+    table[:, 3:7], table[:, 7] = crops, blk_first[:-1]
+    blk_img = np.repeat(np.arange(len(maps), dtype=np.int32), blocks)
+    flat = np.concatenate([m.ravel() for m in maps])
+    pack = EigenGtPack(torch.from_numpy(flat).to(device), torch.from_numpy(table).to(device), torch.from_numpy(blk_img).to(device),
+                       shapes, crops, offsets, blk_first, eval_split)
+    med, cnt = [], []
+    for first in range(0, len(maps), EIGEN_MAX_BATCH):
+        n = min(EIGEN_MAX_BATCH, len(maps) - first)
+        m, c = eigen_gt_stats(pack.gt, pack.table, pack.blk_img, first, n, int(blk_first[first]),
+                              int(blk_first[first + n] - blk_first[first]), eigen)
+        med.append(m)
+        cnt.append(c)
+    pack.medians, pack.counts = torch.cat(med), torch.cat(cnt)
+    return pack
+
+
+def eigen_depth_errors(pred_disp, pack, first, *, pred_disp_flip=None, scale_factor=1.0, median_scaling=True, return_pred=False):
+    """MD2/evaluate_depth.py:351-384 for the predictions ``pred_disp`` [n, h, w] (disparities at network resolution) of the images
+    ``first`` .. ``first + n - 1`` of ``pack``: (errors [n, 8], ratios [n]) on the device, nothing read by the host.
+    ``pred_disp_flip``: the predictions of the mirrored frames (not mirrored back): --post_process.  ``scale_factor``:
+    --pred_depth_scale_factor.  ``median_scaling`` off: no medians, ``ratios`` is NaN.  ``return_pred``: also the scratch buffer,
+    laid out like the batch's ground truth (``pack.view``): the depth before median scaling at the valid pixels, NaN (all bits
+    set) at the others; and the medians [n] of its valid values."""
+    if not isinstance(pack, EigenGtPack):
+        raise RuntimeError("eigen_depth_errors: pack must come from eigen_gt_pack")
+    if not torch.is_tensor(pred_disp) or pred_disp.dim() != 3:
+        raise RuntimeError("eigen_depth_errors: pred_disp must be [n, h, w]")
+    n, first = int(pred_disp.shape[0]), int(first)
+    if first < 0 or n == 0 or first + n > len(pack):
+        raise RuntimeError("eigen_depth_errors: predictions %d .. %d, but the pack holds %d ground-truth maps" % (
+            first, first + n - 1, len(pack)))
+    px0, b0 = int(pack.offsets[first]), int(pack.blk_first[first])
+    errors, ratios, depth, med = eigen_depth_errors_launch(
+        pred_disp, pred_disp_flip, pack.gt, pack.table, pack.blk_img, pack.medians, first, b0, int(pack.blk_first[first + n]) - b0,
+        px0, int(pack.offsets[first + n]) - px0, pack.eigen, scale_factor, median_scaling)
+    return (errors, ratios, depth, med) if return_pred else (errors, ratios)

@@ -62,7 +62,7 @@ class MonodepthOptions:
         # LOGGING
         p.add_argument("--log_frequency", type=int, default=250)
         p.add_argument("--save_frequency", type=int, default=1)
-        # EVALUATION (accepted for command-line compatibility; evaluation scripts are out of scope)
+        # EVALUATION (read by evaluate_depth.evaluate; --eval_out_dir belongs to scripts that are out of scope)
         p.add_argument("--eval_stereo", action="store_true")
         p.add_argument("--eval_mono", action="store_true")
         p.add_argument("--disable_median_scaling", action="store_true")
@@ -89,6 +89,11 @@ class MonodepthOptions:
                        help="md2 = MD2/trainer.py:647-660; dh = DepthHints normalisation, DH/trainer.py:700-708")
         p.add_argument("--synthetic_len", type=int, default=64, help="items per epoch of --dataset synthetic")
         p.add_argument("--seed", type=int, default=1234)
+        p.add_argument("--eval_gt_path", type=str,
+                       help="evaluate_depth: the ground truth, an .npz with the object array ``data`` of 2-D maps (the reference "
+                            "reads splits/<eval_split>/gt_depths.npz); default with --dataset synthetic: made-up LiDAR-like maps")
+        p.add_argument("--eval_frames_path", type=str,
+                       help="evaluate_depth: the test frames, an .npy [N, 3, 320, 1024] in [0, 1] (stands in for KITTIRAWDataset)")
         p.add_argument("--sync_attack", action="store_true",
                        help="strict reference order: wait for the gradient all-reduce + Adam before the next attack")
         p.add_argument("--shared_patch", action="store_true",

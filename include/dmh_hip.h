@@ -268,6 +268,42 @@ int dmh_tube_light_compose(const double* table, const int32_t* index, const uint
 int dmh_tube_light_commit(const float* cost_in, float* cost, float* best, int32_t* state, int n_queries, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K25  Benign depth evaluation (MD2/evaluate_depth.py:351-391): depth at ground-truth resolution, exact medians, eight metrics.
+ *   gt       float [gt_len]: the ground-truth maps of a pack, one after the other.
+ *   table    int32 [n_images][DMH_EIGEN_REC]: 0 offset into gt, 1 gt_h, 2 gt_w, 3 y0, 4 y1, 5 x0, 6 x1 (crop; the whole map for
+ *            splits other than eigen), 7 the image's first work block.  A work block is DMH_EIGEN_CHUNK pixels of one image.
+ *   blk_img  int32 [n_blocks]: the image of every work block of the pack.
+ *   A call covers the images first .. first + n - 1 (n <= DMH_EIGEN_MAX_BATCH); their work blocks are b0 .. b0 + grid - 1 and
+ *   the grid is one workgroup per work block.  px0 = table[first][0]: depth[i - px0] belongs to gt[i].
+ *   eigen != 0: valid = 1e-3 < gt < 80 inside the crop; eigen == 0: valid = gt > 0.
+ *   ws       uint32 [dmh_eigen_select_ws_size(n)]: histograms and selection state, zeroed by the entry points themselves.
+ * gt_stats:   count[n] valid pixels and med[n] = np.median of the valid ground truth (NaN without a valid pixel).
+ * pred_depth: depth = factor / resize(disp) at every valid pixel (OpenCV INTER_LINEAR float arithmetic, no antialiasing), the
+ *             bit pattern 0xffffffff elsewhere.  flip != NULL: every tap is the blend of batch_post_process_disparity (:102-110)
+ *             of pred and the mirrored flip.  ws != NULL: also the first histogram pass of the median (for pred_ratio).
+ * pred_ratio: med_pred[n] = np.median of the valid depths, ratio[n] = med_gt[first + i] / med_pred[i]; needs pred_depth's ws.
+ * metrics:    errors[n][8] = abs_err, abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 of compute_errors' unmasked branch (:61-76) on
+ *             clamp(depth * ratio, 1e-3, 80) (ratio == NULL: no scaling); partials: float [dmh_eigen_partials_size(grid)].
+ *             fp32 sums per work block, combined in double in a fixed order.  No valid pixel: a row of NaN.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_EIGEN_REC 8
+#define DMH_EIGEN_CHUNK 8192
+#define DMH_EIGEN_MAX_BATCH 64
+int64_t dmh_eigen_select_ws_size(int n);
+int64_t dmh_eigen_partials_size(int grid);
+int dmh_eigen_gt_stats(const float* gt, int64_t gt_len, const int32_t* table, const int32_t* blk_img, int n_images, int n_blocks,
+                       int first, int n, int b0, int grid, int eigen, uint32_t* ws, float* med, int32_t* count, void* stream);
+int dmh_eigen_pred_depth(const float* pred, const float* flip, int h, int w, const float* gt, int64_t gt_len, const int32_t* table,
+                         const int32_t* blk_img, int n_images, int n_blocks, int first, int n, int b0, int grid, int eigen,
+                         float factor, int64_t px0, float* depth, int64_t depth_len, uint32_t* ws, void* stream);
+int dmh_eigen_pred_ratio(const float* depth, int64_t depth_len, int64_t px0, int64_t gt_len, const int32_t* table,
+                         const int32_t* blk_img, int n_images, int n_blocks, int first, int n, int b0, int grid, uint32_t* ws,
+                         const float* med_gt, float* med_pred, float* ratio, void* stream);
+int dmh_eigen_metrics(const float* gt, int64_t gt_len, const float* depth, int64_t depth_len, int64_t px0, const int32_t* table,
+                      const int32_t* blk_img, int n_images, int n_blocks, int first, int n, int b0, int grid, const float* ratio,
+                      float* partials, float* errors, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K5  L0 attack pieces (phy_obj_atk_l0.py).
  * compose (:94-99,:43-52): adv = clamp(obj + clamp(pos,0,1) - clamp(neg,0,1), 0, 1);
  *   l0_count (int32, zeroed by caller) += #pixels whose thresholded pattern is non-zero.
