@@ -83,6 +83,8 @@ _SIGNATURES = {
     "dmh_l0_fused_step": (C.c_int, [_fp] * 15 + [C.c_int] * 3 + [C.c_float] * 3 + [_fp]),
     "dmh_tube_light_compose": (C.c_int, [_fp] * 4 + [C.c_int] * 3 + [_fp]),
     "dmh_tube_light_commit": (C.c_int, [_fp] * 4 + [C.c_int, _fp]),
+    "dmh_gauss_blur_windows": (C.c_int, [_fp] * 5 + [C.c_int] * 9 + [_fp]),
+    "dmh_gauss_blur_compose": (C.c_int, [_fp] * 4 + [C.c_int] * 8 + [_fp]),
     "dmh_eigen_select_ws_size": (C.c_int64, [C.c_int]),
     "dmh_eigen_partials_size": (C.c_int64, [C.c_int]),
     "dmh_eigen_gt_stats": (C.c_int, [_fp, C.c_int64, _fp, _fp] + [C.c_int] * 7 + [_fp] * 4),
@@ -221,7 +223,7 @@ def ptr(t):
 
 
 def ptr_f64(t):
-    """Device pointer of a contiguous float64 CUDA tensor (K24's record table: the one float64 argument of the library)."""
+    """Device pointer of a contiguous float64 CUDA tensor (K24's record table, K26's weights)."""
     if not t.is_cuda:
         raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % t.device)
     if not t.is_contiguous() or t.dtype != torch.float64:

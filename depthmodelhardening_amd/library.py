@@ -16,6 +16,8 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::apgd_commit          phy_obj_atk_apgd.py:255-290                       (K22, in place)
     dmh::tube_light_compose   phy_obj_atk_light.py:130-138, light_simulation.py  (K24, writes ``out``)
     dmh::tube_light_commit    phy_obj_atk_light.py:165-167                      (K24, in place)
+    dmh::gauss_blur_windows   phy_obj_atk_guassian.py:96-101 (scipy gaussian_filter + clip, all steps)   (K26)
+    dmh::gauss_blur_compose   phy_obj_atk_guassian.py:103                       (K26, writes ``out``)
     dmh::l0_fused_step        phy_obj_atk_l0.py:105-111,136-138,94-99           (K23, in place)
     dmh::eigen_gt_stats       MD2/evaluate_depth.py:360-373,377 (ground truth)  (K25)
     dmh::eigen_depth_errors   MD2/evaluate_depth.py:351-384, :102-110, :61-76   (K25)
@@ -288,6 +290,30 @@ def eigen_depth_errors(pred_disp: torch.Tensor, pred_disp_flip: Optional[torch.T
 def _(pred_disp, pred_disp_flip, gt, table, blk_img, med_gt, first, b0, grid, px0, npx, eigen, scale_factor, median_scaling):
     n = pred_disp.shape[0]
     return pred_disp.new_empty((n, 8)), pred_disp.new_empty((n,)), pred_disp.new_empty((npx,)), pred_disp.new_empty((n,))
+
+
+# ---------------------------------------------------------------------------------------------------------------- K26
+@custom_op("dmh::gauss_blur_windows", mutates_args=())
+def gauss_blur_windows(obj: torch.Tensor, weights: torch.Tensor, radii: torch.Tensor, r0: int, r1: int, c0: int, c1: int) -> torch.Tensor:
+    return ops.gauss_blur_windows(obj, weights, radii, (r0, r1, c0, c1))
+
+
+@gauss_blur_windows.register_fake
+def _(obj, weights, radii, r0, r1, c0, c1):
+    H, W = obj.shape[-2], obj.shape[-1]
+    (a, b, _), (c, d, _) = slice(r0, r1).indices(H), slice(c0, c1).indices(W)
+    return obj.new_empty((weights.shape[0], obj.shape[-3], max(b - a, 0), max(d - c, 0)))
+
+
+@custom_op("dmh::gauss_blur_compose", mutates_args=("out",))
+def gauss_blur_compose(windows: torch.Tensor, index: torch.Tensor, obj: torch.Tensor, out: torch.Tensor, r0: int, r1: int, c0: int,
+                       c1: int) -> None:
+    ops.gauss_blur_compose(windows, index, obj, (r0, r1, c0, c1), out)
+
+
+@gauss_blur_compose.register_fake
+def _(windows, index, obj, out, r0, r1, c0, c1):
+    return None
 
 
 # ----------------------------------------------------------------------------------------------------------------- K5
@@ -574,4 +600,4 @@ smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
-       "eigen_gt_stats", "eigen_depth_errors")
+       "gauss_blur_windows", "gauss_blur_compose", "eigen_gt_stats", "eigen_depth_errors")

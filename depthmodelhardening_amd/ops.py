@@ -661,6 +661,124 @@ def tube_light_commit(cost_in, cost, best, state):
     return state
 
 
+GAUSS_REGION = (90, 170, 100, 200)      # rows 90:170, columns 100:200 of the object (phy_obj_atk_guassian.py:88)
+
+
+def gauss_sigmas(steps, h, w):
+    """Host: the sigmas of a ``steps``-step Gaussian-blur attack on an h x w object, in Python floats as the reference
+    accumulates them (phy_obj_atk_guassian.py:76-95): ``epsilon += 1.0 / steps``, ``sigma = epsilon * (max(h, w) // 2)``."""
+    if int(steps) < 1:
+        raise RuntimeError("gauss_sigmas: need at least one step")
+    epsilon, stepsize, max_sigma, out = 0.0, 1.0 / int(steps), max(int(h), int(w)) // 2, []
+    for _ in range(int(steps)):
+        epsilon += stepsize
+        out.append(epsilon * max_sigma)
+    return out
+
+
+def gauss_blur_table(sigmas):
+    """Host: (weights float64 [n, max lw + 1], radii int32 [n]) of K26.  Row s holds p[0 .. lw] -- the left half and the centre
+    of the symmetric kernel -- of scipy's ``_gaussian_kernel1d`` for sigma s with truncate 4.0, in float64 and in its order:
+    lw = int(4.0 * s + 0.5), p = exp(-0.5 / (s * s) * x ** 2) for x = -lw .. lw, p / p.sum(); zero padded."""
+    sigmas = [float(s) for s in sigmas]
+    if not sigmas:
+        raise RuntimeError("gauss_blur_table: need at least one sigma")
+    if not all(s > 0.0 and np.isfinite(s) for s in sigmas):
+        raise RuntimeError("gauss_blur_table: every sigma must be positive and finite")
+    radii = np.asarray([int(4.0 * s + 0.5) for s in sigmas], dtype=np.int32)
+    weights = np.zeros((len(sigmas), int(radii.max()) + 1), dtype=np.float64)
+    for row, s, lw in zip(weights, sigmas, radii.tolist()):
+        x = np.arange(-lw, lw + 1)
+        p = np.exp(-0.5 / (s * s) * x ** 2)
+        row[:lw + 1] = (p / p.sum())[:lw + 1]
+    return weights, radii
+
+
+def _gauss_region(region, H, W, name):
+    """``region`` = (r0, r1, c0, c1) clipped to an H x W patch the way the slices [r0:r1, c0:c1] clip."""
+    if len(region) != 4:
+        raise RuntimeError("%s: region must be (r0, r1, c0, c1)" % name)
+    r0, r1, _ = slice(int(region[0]), int(region[1])).indices(H)
+    c0, c1, _ = slice(int(region[2]), int(region[3])).indices(W)
+    if r1 <= r0 or c1 <= c0:
+        raise RuntimeError("%s: the rectangle %s clips to empty on a %d x %d patch" % (name, tuple(region), H, W))
+    return r0, r1, c0, c1
+
+
+def _gauss_axis_host(a, idx, p, lw):
+    """correlate1d of scipy (symmetric branch, mode 'reflect') along the last axis of ``a`` at the positions ``idx``: float64,
+    the taps in scipy's order, every operation rounded on its own; the result rounded to fp32."""
+    n = a.shape[-1]
+    a = a.astype(np.float64)
+
+    def r(j):
+        m = np.mod(j, 2 * n)
+        return np.where(m >= n, 2 * n - 1 - m, m)
+    tmp = a[..., idx] * p[lw]
+    for ll in range(-lw, 0):
+        tmp = tmp + (a[..., r(idx + ll)] + a[..., r(idx - ll)]) * p[lw + ll]
+    return tmp.astype(np.float32)
+
+
+def gauss_blur_host(x, sigma, region=None):
+    """Host twin of K26 in numpy (``Phy_obj_atk_guassian(host_chain=True)``): np.clip(gaussian_filter(x, [0, .., 0, s, s]), 0, 1) of
+    fp32 ``x`` [..., H, W] on the rectangle ``region`` (the whole patch by default), bit-equal to scipy's."""
+    x = np.asarray(x, dtype=np.float32)
+    H, W = x.shape[-2:]
+    r0, r1, c0, c1 = _gauss_region((0, H, 0, W) if region is None else region, H, W, "gauss_blur_host")
+    weights, radii = gauss_blur_table([sigma])
+    p, lw = weights[0], int(radii[0])
+    rows = _gauss_axis_host(np.swapaxes(x, -1, -2), np.arange(r0, r1), p, lw)        # axis H first: [..., W, rh]
+    out = _gauss_axis_host(np.swapaxes(rows, -1, -2), np.arange(c0, c1), p, lw)      # then axis W: [..., rh, rw]
+    return np.clip(out, 0, 1)
+
+
+def _gauss_obj(obj, name):
+    if obj.dtype != torch.float32 or obj.dim() not in (3, 4) or (obj.dim() == 4 and obj.shape[0] != 1):
+        raise RuntimeError("%s: obj must be fp32 [1, C, H, W] or [C, H, W]" % name)
+    return tuple(int(v) for v in obj.shape[-3:])
+
+
+def gauss_blur_windows(obj, weights, radii, region=GAUSS_REGION):
+    """K26: np.clip(scipy.ndimage.gaussian_filter(obj, [0, 0, s, s]), 0, 1) on the rectangle ``region`` = (r0, r1, c0, c1) of
+    fp32 ``obj`` [1, C, H, W] for every row of ``(weights, radii) = gauss_blur_table(sigmas)`` (device float64 [n, k] / int32
+    [n]) -> fp32 [n, C, r1 - r0, c1 - c0], bit-equal to scipy's; two launches for all n."""
+    C_, H, W = _gauss_obj(obj, "gauss_blur_windows")
+    if weights.dim() != 2 or weights.dtype != torch.float64:
+        raise RuntimeError("gauss_blur_windows: weights must be float64 [steps, k]")
+    n = int(weights.shape[0])
+    if n < 1 or int(weights.shape[1]) < 1:
+        raise RuntimeError("gauss_blur_windows: need at least one step")
+    if radii.dtype != torch.int32 or radii.dim() != 1 or int(radii.shape[0]) != n:
+        raise RuntimeError("gauss_blur_windows: radii must be int32 [steps]")
+    r0, r1, c0, c1 = _gauss_region(region, H, W, "gauss_blur_windows")
+    tmp = torch.empty((n, C_, r1 - r0, W), device=obj.device, dtype=torch.float32)
+    windows = torch.empty((n, C_, r1 - r0, c1 - c0), device=obj.device, dtype=torch.float32)
+    N.check(N.lib().dmh_gauss_blur_windows(N.ptr(obj), N.ptr_f64(weights), N.ptr(radii), N.ptr(tmp), N.ptr(windows), n,
+                                           int(weights.shape[1]), C_, H, W, r0, r1, c0, c1, N.stream()))
+    return windows
+
+
+def gauss_blur_compose(windows, index, obj, region=GAUSS_REGION, out=None):
+    """The object with window ``index[0]`` (a device int32: nothing of the step comes from the host) of ``windows``
+    [n, C, rh, rw] in the rectangle ``region`` and ``obj`` elsewhere -> fp32 [1, C, H, W].  An index outside [0, n) leaves
+    ``out`` as it is."""
+    C_, H, W = _gauss_obj(obj, "gauss_blur_compose")
+    r0, r1, c0, c1 = _gauss_region(region, H, W, "gauss_blur_compose")
+    if windows.dtype != torch.float32 or windows.dim() != 4 or int(windows.shape[0]) < 1 \
+            or tuple(windows.shape[1:]) != (C_, r1 - r0, c1 - c0):
+        raise RuntimeError("gauss_blur_compose: windows must be fp32 [steps, %d, %d, %d] for this rectangle" % (C_, r1 - r0, c1 - c0))
+    if index.dtype != torch.int32 or index.numel() < 1:
+        raise RuntimeError("gauss_blur_compose: index must be int32")
+    if out is None:
+        out = torch.zeros((1, C_, H, W), device=obj.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or out.numel() != obj.numel():
+        raise RuntimeError("gauss_blur_compose: out must be fp32 of the object's size")
+    N.check(N.lib().dmh_gauss_blur_compose(N.ptr(windows), N.ptr(index), N.ptr(obj), N.ptr(out), int(windows.shape[0]), C_, H, W,
+                                           r0, r1, c0, c1, N.stream()))
+    return out
+
+
 class _L0Compose(torch.autograd.Function):
     @staticmethod
     def forward(ctx, obj, pos, neg, l0_clip, finalize):

@@ -268,6 +268,26 @@ int dmh_tube_light_compose(const double* table, const int32_t* index, const uint
 int dmh_tube_light_commit(const float* cost_in, float* cost, float* best, int32_t* state, int n_queries, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K26  Gaussian-blur object attack (a search over growing sigmas): scipy.ndimage.gaussian_filter(x, [0, 0, s, s]) (mode
+ * 'reflect', truncate 4.0) followed by np.clip(., 0, 1), bit for bit, for the rectangle [r0, r1) x [c0, c1) of the object.
+ * Replaces: phy_obj_atk_guassian.py:96-103 (windows, compose); keep-the-best (:121-123) is dmh_tube_light_commit.
+ *   obj      float [C][H][W]: the clean object.
+ *   weights  double [steps][wstride], made on the host in float64: row s = p[0 .. lw_s] of exp(-0.5 / (s s) x^2), x = -lw .. lw,
+ *            divided by its sum (the kernel is symmetric: the left half and the centre), zero padded.
+ *   radii    int32 [steps]: lw_s = int(4.0 s + 0.5); the kernels clamp it to [0, wstride - 1].
+ *   tmp      float [steps][C][r1 - r0][W]: workspace, pass 1 (axis H) rounded to fp32.
+ *   windows  float [steps][C][r1 - r0][c1 - c0]: pass 2 (axis W), clipped.
+ * Per output and axis, in double, every operation rounded on its own:
+ *   t = a[i] p[lw];  for ll = -lw .. -1: t = t + (a[r(i + ll)] + a[r(i - ll)]) p[lw + ll];  r(j): j mod 2n, 2n - 1 - j if >= n.
+ * windows: two launches (one per pass) for all steps.
+ * compose: out = obj with windows[index[0]] in the rectangle; an index outside [0, steps) makes it a no-op.
+ * ---------------------------------------------------------------------------------- */
+int dmh_gauss_blur_windows(const float* obj, const double* weights, const int32_t* radii, float* tmp, float* windows, int steps,
+                           int wstride, int C, int H, int W, int r0, int r1, int c0, int c1, void* stream);
+int dmh_gauss_blur_compose(const float* windows, const int32_t* index, const float* obj, float* out, int steps, int C, int H,
+                           int W, int r0, int r1, int c0, int c1, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K25  Benign depth evaluation (MD2/evaluate_depth.py:351-391): depth at ground-truth resolution, exact medians, eight metrics.
  *   gt       float [gt_len]: the ground-truth maps of a pack, one after the other.
  *   table    int32 [n_images][DMH_EIGEN_REC]: 0 offset into gt, 1 gt_h, 2 gt_w, 3 y0, 4 y1, 5 x0, 6 x1 (crop; the whole map for
