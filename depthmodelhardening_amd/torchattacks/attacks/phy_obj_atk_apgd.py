@@ -23,7 +23,6 @@ import torch
 
 from ... import ops
 from ...my_utils import object_dataset_root
-from ...roi import RoiPlan
 from .phy_obj_atk import Phy_obj_atk
 
 
@@ -85,8 +84,7 @@ class Phy_obj_atk_APGD(Phy_obj_atk):
         if self.shard is not None:
             raise NotImplementedError("Phy_obj_atk_APGD: shard is not built (evaluation runs on one rank)")
         images = images.detach().to(self.device)
-        if images.size()[0] != 1 and images.size()[0] != batch_size:
-            raise RuntimeError('Batch size doesn\'t match!')
+        self._check_batch(images, batch_size)
         scene_imgs = images
         dev, steps = self.device, int(self.steps)
         x0 = self.obj_img.detach().to(dev).contiguous()
@@ -104,29 +102,21 @@ class Phy_obj_atk_APGD(Phy_obj_atk):
         pt = self.phy_trans_ben
         z0_it, al_it = pt.draw_samples(batch_size, rs=np.random.RandomState(self.seed))
         z0_sample, alpha_sample = sample(pt.dist_range, batch_size), sample(pt.angle_range, batch_size)
-        if eval:
-            z0_sample[0] = 7
-            alpha_sample[0] = 0
+        self._eval_pose(z0_sample, alpha_sample, eval)
         coeffs = self._coeffs([(z0_it, al_it), (z0_sample, alpha_sample)])
         l_pad, t_pad = pt.l_pad, pt.t_pad
 
-        plan = tab = clean = None
-        if ops.ROI_ENABLED and self.use_roi and hasattr(self.model, "masked_sq_mean") and dev.type == "cuda":
-            plan = RoiPlan(pt.mask_boxes(z0_it, al_it, self.scene_size), *self.scene_size, depth=ops.ROI_DEPTH)
-            tab = plan.device_table(dev)
-            with torch.no_grad():       # the frames without the object (see Phy_obj_atk.forward)
-                clean, _ = ops.eot_paste(scene_imgs, self.obj_img, torch.zeros_like(mask), coeffs[0], l_pad, t_pad,
-                                         self.scene_size)
+        plans, tabs, clean = self._window_plans([(z0_it, al_it)], scene_imgs, mask, coeffs[0])
         self._one = torch.ones((), device=dev, dtype=torch.float32)
 
         def cost_and_grad(x):
             p = x.detach().requires_grad_(True)
             adv, m = ops.eot_paste(scene_imgs, p, mask, coeffs[0], l_pad, t_pad, self.scene_size)
-            if plan is not None:
-                cost = self._neg_cost(adv, m, plan, tab, clean)
+            if plans is not None:
+                cost = self._neg_cost(adv, m, plans[0], tabs[0], clean)
             else:
                 cost = -ops.masked_sq_mean(self.model(adv), m)      # -MSE(adv_depth * mask, 0) (:176)
-            (g,) = torch.autograd.grad(cost, p, grad_outputs=self._one if cost.dim() == 0 and cost.dtype == torch.float32 else None)
+            (g,) = torch.autograd.grad(cost, p, grad_outputs=self._grad_seed(cost))
             return cost.detach().reshape(1), g
 
         # the state of attack_single_run (:148-200), all of it on the device
@@ -148,16 +138,24 @@ class Phy_obj_atk_APGD(Phy_obj_atk):
             done = 1
             if patches is not None:
                 patches.append(x_ret.clone())
-            g = self._capture(iteration)
+
+            def traced():
+                if self._capture_fault:     # test hook: a capture that dies before its first launch
+                    raise RuntimeError("injected capture fault")
+                iteration()
+
+            # Every buffer the iteration updates is updated in place by the two K22 launches, so after a failed capture the
+            # eager loop goes on from the state of the eager iteration.  The windows of this attack never move: the cells of
+            # the cached clean features that a half-traced iteration left marked are exactly the cells the next paste
+            # overwrites (no restore_head).
+            g = self._capture_graph(traced, what="the attack iteration")
             if g is not None:
                 for _ in range(1, steps):
                     g.replay()
                     if patches is not None:
                         patches.append(x_ret.clone())
                 done = steps
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                self._graph = (g, ev)
+                self._keep_graph(g)
         for _ in range(done, steps):
             iteration()
             if patches is not None:
@@ -171,50 +169,5 @@ class Phy_obj_atk_APGD(Phy_obj_atk):
                                        checkpoint=bool(nxt[9]), reduced=bool(nxt[10]), moved=bool(nxt[11]), n_rose=int(nxt[12]),
                                        patch=patches[i]))
 
-        adv_patch = x_ret               # x_best_adv of :255: the last iterate as it was before a possible restart
-        self.phy_trans_adv.reset_img(adv_patch, self.obj_mask)
-        with torch.no_grad():
-            adv_scenes, obj_masks_out = ops.eot_paste(scene_imgs, adv_patch, mask, coeffs[1], l_pad, t_pad, self.scene_size)
-            ben_scenes, _ = ops.eot_paste(scene_imgs, self.obj_img, mask, coeffs[1], l_pad, t_pad, self.scene_size)
-        return adv_scenes, ben_scenes, obj_masks_out, adv_patch
-
-    def _capture(self, iteration):
-        """One iteration as a HIP graph, with the parent's capture discipline (side stream, the attack object's memory pool,
-        thread_local error mode); None after a failed capture, with ``graph_failure`` set and ``use_graph`` switched off.  A
-        capture executes nothing, and every buffer the iteration updates is updated in place by the two K22 launches, so after a
-        failure the device still holds the state of the eager iteration and the eager loop goes on from there.  The windows of
-        this attack never move: the cells of the cached clean features that a half-traced iteration left marked are exactly the
-        cells the next paste overwrites."""
-        dev = self.device
-        if self._graph is not None:     # the previous attack's graph: let its last replay finish before it is destroyed
-            self._graph[1].synchronize()
-            self._graph = None
-        main = torch.cuda.current_stream(dev)
-        pool, side = self._capture_pool(main)
-        side.wait_stream(main)
-        g = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.stream(side):
-                ops._sk_workspace(dev)
-                g.capture_begin(pool=pool, capture_error_mode="thread_local")
-                try:
-                    if self._capture_fault:     # test hook: a capture that dies before its first launch
-                        raise RuntimeError("injected capture fault")
-                    iteration()
-                except BaseException:
-                    try:
-                        g.capture_end()
-                    except Exception:
-                        pass
-                    raise
-                g.capture_end()
-        except RuntimeError as e:
-            main.wait_stream(side)
-            self.use_graph = False
-            self.graph_failure = "%s: %s" % (type(e).__name__, str(e).splitlines()[0] if str(e) else "")
-            import warnings
-            warnings.warn("Phy_obj_atk_APGD: HIP-graph capture of the attack iteration failed (%s); continuing with eager launches"
-                          % self.graph_failure)
-            return None
-        main.wait_stream(side)
-        return g
+        # x_best_adv of :255: the last iterate as it was before a possible restart
+        return self._return_scenes(scene_imgs, x_ret, self.obj_img, mask, coeffs[1])

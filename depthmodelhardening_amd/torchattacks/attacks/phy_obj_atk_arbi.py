@@ -51,23 +51,14 @@ class Phy_obj_atk_arbi(Phy_obj_atk):
         In eval mode the first object position / angle is fixed (7 m, 0 deg).
         """
         images = images.detach().to(self.device)
-        if images.size()[0] != 1 and images.size()[0] != batch_size:
-            raise RuntimeError('Batch size doesn\'t match!')
+        self._check_batch(images, batch_size)
         obj = self.obj_img.detach().to(self.device).contiguous()
         r0, r1, c0, c1 = ops._gauss_region(self.region, int(obj.shape[-2]), int(obj.shape[-1]), "Phy_obj_atk_arbi")
         obj_img_adv = obj.clone()
         obj_img_adv[:, :, r0:r1, c0:c1] = torch.from_numpy(self.draw_fill(tuple(obj.shape))).to(self.device)
-        self.phy_trans_adv.reset_img(obj_img_adv, self.obj_mask)
 
         z0_sample = np.linspace(5, 30, num=batch_size)
         alpha_sample = np.random.RandomState(17).choice(list(range(-30, 31, 2)), batch_size, replace=True)
-        if eval:
-            z0_sample[0] = 7
-            alpha_sample[0] = 0
+        self._eval_pose(z0_sample, alpha_sample, eval)
         coeffs = self._coeffs([(z0_sample, alpha_sample)])
-        pt = self.phy_trans_ben
-        mask = self.obj_mask.to(self.device)
-        with torch.no_grad():
-            adv_scenes, obj_masks_out = ops.eot_paste(images, obj_img_adv, mask, coeffs[0], pt.l_pad, pt.t_pad, self.scene_size)
-            ben_scenes, _ = ops.eot_paste(images, obj, mask, coeffs[0], pt.l_pad, pt.t_pad, self.scene_size)
-        return adv_scenes, ben_scenes, obj_masks_out, obj_img_adv
+        return self._return_scenes(images, obj_img_adv, obj, self.obj_mask.to(self.device), coeffs[0])

@@ -16,10 +16,7 @@ import torch.nn.functional as F
 
 from ... import color_jitter, ops
 from ...my_utils import object_dataset_root, ori_H, ori_W, to_device_async
-from ...physicalTrans import PhysicalTrans
-from ...roi import RoiPlan, common_size_plans
-from ..attack import Attack
-from .phy_obj_atk import Phy_obj_atk
+from .object_attack import ObjectAttack
 
 
 def host_below(counts, stp, thresh):
@@ -29,52 +26,35 @@ def host_below(counts, stp, thresh):
         return bool(np.float32(counts[stp]) / np.float32(counts[0]) <= np.float32(thresh))
 
 
-class Phy_obj_atk_l0(Attack):
+class Phy_obj_atk_l0(ObjectAttack):
     r"""
     Distance Measure : L_0
     """
 
     def __init__(self, model, obj_img, obj_mask, adam_lr=0.5, steps=10, mask_wt=0.1, l0_thresh=1 / 10,
                  dist_range=list(range(5, 31, 2))):
-        super().__init__("PGD", model)
-        self.obj_img = obj_img.clone().detach()
-        self.obj_mask = obj_mask.clone().detach()
+        super().__init__("PGD", model, obj_img.clone().detach(), obj_mask.clone().detach(), dist_range)
         self.steps = steps
-        self.scene_size = [320, 1024]
         self.clip_max = 1
         self.learning_rate = adam_lr
         self.mask_weight_init = mask_wt
         self.mask_weight = self.mask_weight_init
         self.l0_thresh = l0_thresh
         self.l0_clip = self.clip_max / 255.
-        conf = {'path': f'{object_dataset_root}/training/calib/003086.txt'}
-        self.phy_trans_adv = PhysicalTrans(self.obj_img.clone(), self.obj_mask, conf, (1, 3, ori_H, ori_W),
-                                           dist_range=dist_range)
-        self.phy_trans_ben = PhysicalTrans(self.obj_img, self.obj_mask, conf, (1, 3, ori_H, ori_W),
-                                           dist_range=dist_range)
         # ONE random colour transform per attack object, drawn here as the reference does (:41; four random.uniform + one
         # random.shuffle of the global ``random`` generator), applied by forward(..., color_jit=True)
         self.color_aug = color_jitter.get_params((0.8, 1.2), (0.8, 1.2), (0.8, 1.2), (-0.1, 0.1))
-        self.use_roi = True     # evaluate the adversarial cost on windows around the object when the model offers it
-        self.shard = None       # (rank, world, group): data-parallel shared-patch mode, see Phy_obj_atk.shard
         self.trace = None  # set to a list to record (l0, mask_weight, adv_cost, mask_cost) per iteration
         self.grad_trace = None  # set to a list to record the two pattern gradients Adam is handed, per iteration (tests)
         # fused: everything between the model's gradient and the next composed patch is ONE launch (K23, csrc/l0_fused.hip) that
         # reads its decisions from device memory -- no torch.optim.Adam, no torch.where, no autograd node for the mask cost; the
         # trace is read once after the loop from K23's record array (kept in ``records``).  Off by default.
         self.fused = False
-        # use_graph / common_windows: as on Phy_obj_atk -- one set of window sizes for all 2 * steps draws, iteration 0 eager,
+        # use_graph / common_windows (ObjectAttack): one set of window sizes for all 2 * steps draws, iteration 0 eager,
         # iteration 1 captured in a HIP graph, later iterations two small device copies + a replay.  Implies ``fused``.
-        self.use_graph = False
-        self.common_windows = False
+        # _capture_fault makes that capture fail after the whole iteration has been traced.
         self.records = None             # K23's record array [2 * steps, ops.L0_REC] of the last fused attack (device)
         self.graph_replays = 0          # how many iterations of the last attack were graph replays
-        self.graph_failure = None       # why use_graph switched itself off (a failed capture), else None
-        self._capture_fault = False     # test hook: make the capture fail after the whole iteration has been traced
-        self._graph_pool = None
-        self._graph = None              # (graph of the previous attack, event behind its last replay)
-
-    _capture_pool = Phy_obj_atk._capture_pool
 
     def cal_l0(self):
         """Number of pixels whose thresholded pattern is non-zero (:43-52), as a device tensor."""
@@ -110,8 +90,7 @@ class Phy_obj_atk_l0(Attack):
             raise NotImplementedError("Phy_obj_atk_l0: grad_trace belongs to the unfused path (the fused update never "
                                       "materialises the pattern gradients)")
         n_local = batch_size if mine is None else len(mine)
-        if img_B != 1 and img_B != n_local:
-            raise RuntimeError('Batch size doesn\'t match!')
+        self._check_batch(images, n_local)
         scene_imgs = images
 
         # numpy RNG on the host, exactly as the reference (:73-83)
@@ -145,8 +124,7 @@ class Phy_obj_atk_l0(Attack):
         for r in range(self.steps, max_iter + 1):
             random.setstate(rng_states[r])
             z0_f, al_f = sample(pt.dist_range, batch_size), sample(pt.angle_range, batch_size)
-            if eval:                # the override belongs to GLOBAL scene 0 (:165-167): applied before the scenes are dealt out
-                z0_f[0], al_f[0] = 6.1, 0
+            self._eval_pose(z0_f, al_f, eval, dist=6.1)     # GLOBAL scene 0's (:165-167): before the scenes are dealt out
             finals[r], states_after[r] = (z0_f, al_f), random.getstate()
         if mine is not None:        # the job's draws are rank 0's (the final pose draws included); keep the own scenes' poses
             box = [(draws, finals)]
@@ -154,27 +132,17 @@ class Phy_obj_atk_l0(Attack):
             draws = [([z[i] for i in mine], [a[i] for i in mine]) for z, a in box[0][0]]
             finals = {r: ([z[i] for i in mine], [a[i] for i in mine]) for r, (z, a) in box[0][1].items()}
             batch_size = n_local
-        coeffs_host = np.stack([pt.coeffs_for(z0, al) for z0, al in draws], 0)
-        coeffs = to_device_async(coeffs_host, self.device)
+        coeffs = self._coeffs(draws)
         l_pad, t_pad = pt.l_pad, pt.t_pad
         mask = self.obj_mask.to(self.device)
-        # the adversarial cost reads the disparity under the object only: see Phy_obj_atk.forward
+        # the adversarial cost on windows around the object (ObjectAttack._window_plans), one set of sizes for all 2 * steps
+        # draws where a graph or its eager twin asks for it.  Not with color_jit: the whole frame changes with the patch -- the
+        # contrast step blends with the pasted image's mean -- so neither the windows' "unchanged outside the box" nor the
+        # cached clean-frame features hold: whole-frame path
         plans = tabs = clean = None
-        # (with color_jit the whole frame changes with the patch -- the contrast step blends with the pasted image's mean --
-        # so neither the windows' "unchanged outside the box" nor the cached clean-frame features hold: whole-frame path)
-        if (ops.ROI_ENABLED and self.use_roi and not color_jit and hasattr(self.model, "masked_sq_mean")
-                and self.device.type == "cuda"):
-            boxes = [pt.mask_boxes(z0, al, self.scene_size) for z0, al in draws]
-            if self.use_graph or self.common_windows:       # one set of window sizes for all 2 * steps draws (see Phy_obj_atk)
-                plans = common_size_plans(boxes, *self.scene_size, depth=ops.ROI_DEPTH)
-            if plans is None:
-                plans = [RoiPlan(b, *self.scene_size, depth=ops.ROI_DEPTH) for b in boxes]
-            tabs = to_device_async(np.stack([p.table() for p in plans], 0), self.device)
-            for p_, t_ in zip(plans, tabs):     # one H2D copy for all steps; each plan keeps ITS slice (RoiPlan.bind_table)
-                p_.bind_table(t_)
-            with torch.no_grad():       # the frames without the object: see Phy_obj_atk.forward
-                clean, _ = ops.eot_paste(scene_imgs, self.obj_img, torch.zeros_like(mask), coeffs[0], l_pad, t_pad,
-                                         self.scene_size)
+        if not color_jit:
+            plans, tabs, clean = self._window_plans(draws, scene_imgs, mask, coeffs[0],
+                                                    common=self.use_graph or self.common_windows)
         if self.fused or self.use_graph:
             ran, mw = self._fused_loop(scene_imgs, mask, coeffs, l_pad, t_pad, plans, tabs, clean, color_jit, max_iter)
         else:
@@ -230,14 +198,9 @@ class Phy_obj_atk_l0(Attack):
         with torch.no_grad():
             obj_img_adv, _ = ops.l0_compose(self.obj_img, self.pattern_pos_tensor.detach(),
                                             self.pattern_neg_tensor.detach(), self.l0_clip, finalize=True)
-        self.phy_trans_adv.reset_img(obj_img_adv, self.obj_mask)
-        z0_sample, alpha_sample = finals[ran]
-        cf = to_device_async(pt.coeffs_for(z0_sample, alpha_sample), self.device)
-        with torch.no_grad():
-            adv_scenes, obj_masks_out = ops.eot_paste(scene_imgs, obj_img_adv, mask, cf, l_pad, t_pad, self.scene_size)
-            ben_scenes, _ = ops.eot_paste(scene_imgs, self.obj_img, mask, cf, l_pad, t_pad, self.scene_size)
         self.mask_weight = float(mw)
-        return adv_scenes, ben_scenes, obj_masks_out, obj_img_adv
+        cf = to_device_async(pt.coeffs_for(*finals[ran]), self.device)
+        return self._return_scenes(scene_imgs, obj_img_adv, self.obj_img, mask, cf)
 
     # ------------------------------------------------------------------------------------------------ fused path (K23)
     def _fused_loop(self, scene_imgs, mask, coeffs, l_pad, t_pad, plans, tabs, clean, color_jit, max_iter):
@@ -252,7 +215,7 @@ class Phy_obj_atk_l0(Attack):
             adv0, c0 = ops.l0_compose(obj, st.pos, st.neg, self.l0_clip)
             st.adv.copy_(adv0)
             st.count[:1].copy_(c0)
-        one = torch.ones((), device=dev, dtype=torch.float32)
+        self._one = torch.ones((), device=dev, dtype=torch.float32)
         tracing = self.trace is not None
         mask_wt, thresh = float(self.mask_weight_init), float(self.l0_thresh)
 
@@ -265,12 +228,17 @@ class Phy_obj_atk_l0(Attack):
                 if color_jit:
                     adv_scenes = self.color_aug(adv_scenes)
                 adv_cost = ops.masked_sq_mean(self.model(adv_scenes), adv_obj_mask)
-            (g,) = torch.autograd.grad(adv_cost, p, grad_outputs=one if adv_cost.dim() == 0 and adv_cost.dtype == torch.float32 else None)
+            (g,) = torch.autograd.grad(adv_cost, p, grad_outputs=self._grad_seed(adv_cost))
             mask_cost = None
             if tracing:
                 with torch.no_grad():
                     mask_cost = ops.l0_mask_cost(st.pos, st.neg)
             st.step(obj, g.contiguous(), adv_cost.detach(), mask_cost, mask_wt, thresh, self.l0_clip)
+
+        def traced():
+            iteration(coeff_cur, plans[0], tab_cur)
+            if self._capture_fault:     # test hook: a capture that dies after the whole iteration has been traced
+                raise RuntimeError("injected capture fault")
 
         graph_mode = bool(self.use_graph and plans is not None and dev.type == "cuda" and not ops.profiling_every_launch())
         coeff_cur = tab_cur = g = None
@@ -290,12 +258,12 @@ class Phy_obj_atk_l0(Attack):
                 coeff_cur.copy_(coeffs[stp])
                 tab_cur.copy_(tabs[stp])
                 if g is None:
-                    g = self._capture(lambda: iteration(coeff_cur, plans[0], tab_cur))
+                    # restore_head: tracing the iteration runs the Python-side bookkeeping of the incremental encoder head,
+                    # and these windows move from iteration to iteration
+                    g = self._capture_graph(traced, what="the attack iteration", restore_head=True)
                     if g is None:       # the capture failed: the eager loop takes over on the same common-size plans
                         graph_mode = False
-                        plans[0].table_rewritten = False
-                        for p_, t_ in zip(plans, tabs):
-                            p_.bind_table(t_)
+                        self._bind_tables(plans, tabs)
             if graph_mode and stp > 0:
                 g.replay()
                 self.graph_replays += 1
@@ -307,9 +275,7 @@ class Phy_obj_atk_l0(Attack):
                 iteration(coeffs[stp], None, None)
             ran += 1
         if g is not None:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            self._graph = (g, ev)
+            self._keep_graph(g)
         self.records = st.rec
         rec = st.rec[:ran].cpu().numpy() if (tracing or not exited) and ran else None
         if tracing and rec is not None:
@@ -317,46 +283,3 @@ class Phy_obj_atk_l0(Attack):
                 self.trace.append((int(r[0]), float(r[1]), float(r[2]), float(r[3])))
         mw = 0.0 if exited or rec is None else float(rec[ran - 1][1])
         return ran, mw
-
-    def _capture(self, iteration):
-        """One fused iteration as a HIP graph, with Phy_obj_atk's capture discipline (side stream, this object's memory pool,
-        thread_local error mode); None after a failed capture, with ``graph_failure`` set and ``use_graph`` switched off.  A
-        capture executes nothing on the device, but tracing the iteration runs the Python-side bookkeeping of the incremental
-        encoder head (ops.CleanHead: which window is dirty, its generation, its private origin copies) and may add entries to the
-        frozen-weights cache that point at pool memory no kernel ever wrote: both are snapshotted before the capture and put back
-        after a failed one, so that the eager loop continues from the state iteration 0 really left."""
-        dev = self.device
-        if self._graph is not None:     # the previous attack's graph: let its last replay finish before it is destroyed
-            self._graph[1].synchronize()
-            self._graph = None
-        main = torch.cuda.current_stream(dev)
-        pool, side = self._capture_pool(main)
-        side.wait_stream(main)
-        g = torch.cuda.CUDAGraph()
-        snap = ops.clean_head_snapshot()
-        try:
-            with torch.cuda.stream(side):
-                ops._sk_workspace(dev)
-                g.capture_begin(pool=pool, capture_error_mode="thread_local")
-                try:
-                    iteration()
-                    if self._capture_fault:     # test hook: a capture that dies after the whole iteration has been traced
-                        raise RuntimeError("injected capture fault")
-                except BaseException:
-                    try:
-                        g.capture_end()
-                    except Exception:
-                        pass
-                    raise
-                g.capture_end()
-        except RuntimeError as e:
-            main.wait_stream(side)
-            ops.clean_head_restore(snap)
-            self.use_graph = False
-            self.graph_failure = "%s: %s" % (type(e).__name__, str(e).splitlines()[0] if str(e) else "")
-            import warnings
-            warnings.warn("Phy_obj_atk_l0: HIP-graph capture of the attack iteration failed (%s); continuing with eager launches"
-                          % self.graph_failure)
-            return None
-        main.wait_stream(side)
-        return g

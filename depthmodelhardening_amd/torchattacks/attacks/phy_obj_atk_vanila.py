@@ -4,9 +4,6 @@ the first scene batch has run the search, every later batch pastes the patch it 
 Same class name, constructor, call signature and return tuple as the reference's ``torchattacks/attacks/phy_obj_atk_vanila.py``
 (forward :58-94): the given patch and the clean object at ONE shared pose draw, two K3 launches.
 """
-import torch
-
-from ... import ops
 from ...my_utils import object_dataset_root
 from .phy_obj_atk import Phy_obj_atk
 
@@ -28,20 +25,10 @@ class Phy_obj_atk_vanila(Phy_obj_atk):
         In eval mode the first object position / angle is fixed (7 m, 0 deg).
         """
         images = images.detach().to(self.device)
-        if images.size()[0] != 1 and images.size()[0] != batch_size:
-            raise RuntimeError('Batch size doesn\'t match!')
+        self._check_batch(images, batch_size)
         self.obj_img = obj_img
         obj_img_adv = obj_img.clone().detach().to(self.device)
-        self.phy_trans_adv.reset_img(obj_img_adv, self.obj_mask)
         z0_sample, alpha_sample = self._draw(batch_size, explicit=True)
-        if eval:
-            z0_sample[0] = 7
-            alpha_sample[0] = 0
+        self._eval_pose(z0_sample, alpha_sample, eval)
         coeffs = self._coeffs([(z0_sample, alpha_sample)])
-        pt = self.phy_trans_ben
-        mask = self.obj_mask.to(self.device)
-        with torch.no_grad():
-            adv_scenes, obj_masks_out = ops.eot_paste(images, obj_img_adv, mask, coeffs[0], pt.l_pad, pt.t_pad, self.scene_size)
-            ben_scenes, _ = ops.eot_paste(images, self._clean_img.to(self.device), mask, coeffs[0], pt.l_pad, pt.t_pad,
-                                          self.scene_size)
-        return adv_scenes, ben_scenes, obj_masks_out, obj_img_adv
+        return self._return_scenes(images, obj_img_adv, self._clean_img.to(self.device), self.obj_mask.to(self.device), coeffs[0])

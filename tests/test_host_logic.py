@@ -365,3 +365,49 @@ def test_step_log_writes_one_line_per_iteration_one_iteration_late(tmp_path):
     off.end_step(0, 0, 1.0)
     off.close()
     assert not off.marks and off.file is None
+
+
+def test_object_attack_base_host_pieces():
+    """What the attack classes share (torchattacks/attacks/object_attack.py): who derives from whom, the batch check, the
+    eval-mode pose of scene 0 (7 m; the L0 attack's 6.1 m), the pose draws in the reference's order."""
+    from depthmodelhardening_amd import torchattacks as ta
+    from depthmodelhardening_amd.torchattacks.attacks.object_attack import ObjectAttack
+    from depthmodelhardening_amd.torchattacks.attacks.object_search import _ObjectSearch
+    rows = (ta.Phy_obj_atk_APGD, ta.Phy_obj_atk_light, ta.Phy_obj_atk_guassian, ta.Phy_obj_atk_arbi, ta.Phy_obj_atk_vanila)
+    assert all(issubclass(c, ta.Phy_obj_atk) for c in rows) and issubclass(ta.Phy_obj_atk, ObjectAttack)
+    assert issubclass(ta.Phy_obj_atk_l0, ObjectAttack) and not issubclass(ta.Phy_obj_atk_l0, ta.Phy_obj_atk)
+    assert [issubclass(c, _ObjectSearch) for c in rows] == [False, True, True, False, False]
+
+    for n_images, n_scenes, ok in ((1, 5, True), (5, 5, True), (2, 3, False), (0, 3, False), (3, 1, False)):
+        if ok:
+            ObjectAttack._check_batch(torch.zeros(n_images, 3, 4, 4), n_scenes)
+        else:
+            with pytest.raises(RuntimeError, match="Batch size doesn't match!"):
+                ObjectAttack._check_batch(torch.zeros(n_images, 3, 4, 4), n_scenes)
+
+    z0, al = [11, 13, 15], [-4, 2, 6]
+    ObjectAttack._eval_pose(z0, al, False)
+    assert (z0, al) == ([11, 13, 15], [-4, 2, 6])
+    ObjectAttack._eval_pose(z0, al, True)
+    assert (z0, al) == ([7, 13, 15], [0, 2, 6])
+    ObjectAttack._eval_pose(z0, al, True, dist=6.1)
+    assert (z0, al) == ([6.1, 13, 15], [0, 2, 6])
+
+    obj, mask = synth.make_object()
+    dist_range = list(np.arange(5, 10, 0.2))
+    atk = ta.Phy_obj_atk(synth.TinyDepthNet(seed=5), obj, mask, steps=2, dist_range=dist_range)
+    l0 = ta.Phy_obj_atk_l0(synth.TinyDepthNet(seed=5), obj, mask, steps=2, dist_range=dist_range)
+    assert atk.obj_img is obj and l0.obj_img is not obj and torch.equal(l0.obj_img, obj)      # L0 keeps its own copies
+    for a in (atk, l0):
+        assert (a.use_roi, a.shard, a.use_graph, a.common_windows, a.graph_failure, a._graph, a._capture_fault) == (
+            True, None, False, False, None, None, False) and a.scene_size == [320, 1024]
+    pt = atk.phy_trans_ben
+    random.seed(3)
+    want = [pt.draw_samples(4), (random.sample(pt.dist_range, 4), random.sample(pt.angle_range, 4))]
+    want += [pt.draw_samples(3), pt.draw_samples(2)]
+    random.seed(3)
+    got = [atk._draw(4), atk._draw(4, explicit=True)]
+    atk.pose_group = 3
+    grouped = atk._draw(5)
+    assert got == [(list(z), list(a)) for z, a in want[:2]]
+    assert grouped == (list(want[2][0]) + list(want[3][0]), list(want[2][1]) + list(want[3][1]))
