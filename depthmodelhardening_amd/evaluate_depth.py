@@ -17,7 +17,7 @@ from .datasets import make_object
 from .layers import disp_to_depth
 from .my_utils import to_device_async
 from .torchattacks import (PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_arbi, Phy_obj_atk_guassian, Phy_obj_atk_l0,
-                           Phy_obj_atk_light, Phy_obj_atk_vanila)
+                           Phy_obj_atk_light, Phy_obj_atk_Square, Phy_obj_atk_vanila)
 
 STEREO_SCALE_FACTOR = 5.4
 MIN_DEPTH = 1e-3
@@ -42,7 +42,9 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
     benign and the attacked depth (object-masked for the object attacks).  ``scene_source(n)`` yields n scenes
     [n,3,375,1242]; the KITTI-object loader of the reference (:157-170, starting at index 42) is replaced by it.
     The two gradient-free rows "guassian" and "arbi" are served when ``args['gradient_free_attacks']`` is true: without the key
-    they are refused like every unserved ``norm_type``, as they were before the rows existed."""
+    they are refused like every unserved ``norm_type``, as they were before the rows existed.  In the same way the "Square" row
+    is served when ``args['square_attack']`` is true (``query_patch``: "candidate", or "best" for the reference's line
+    phy_obj_atk_square.py:295; ``graph_attack``: replay the query from a HIP graph)."""
     device = next(model2atk.parameters()).device
     obj_tensor, mask_tensor = make_object(device)
     if args['norm_type'] == "l_inf":
@@ -57,6 +59,10 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
         depth_atk = Phy_obj_atk_arbi(model2atk, obj_tensor, mask_tensor)
     elif args['norm_type'] == "guassian" and args.get('gradient_free_attacks'):     # :148-149 (the reference's spelling)
         depth_atk = Phy_obj_atk_guassian(model2atk, obj_tensor, mask_tensor, steps=args['step'])
+    elif args['norm_type'] == "Square" and args.get('square_attack'):               # :142-145
+        depth_atk = Phy_obj_atk_Square(model2atk, obj_tensor, mask_tensor, eps=args['epsilon'], n_queries=args['n_queries'],
+                                       query_patch=args.get('query_patch', 'candidate'))
+        depth_atk.use_graph = bool(args.get('graph_attack', False))
     elif args['norm_type'] == "light":      # :150-151; ``n_init`` / ``n_search``: the reference's literals 200 and 20
         depth_atk = Phy_obj_atk_light(model2atk, obj_tensor, mask_tensor, n_init=args.get('n_init', 200),
                                       n_search=args.get('n_search', 20))

@@ -18,6 +18,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::tube_light_commit    phy_obj_atk_light.py:165-167                      (K24, in place)
     dmh::gauss_blur_windows   phy_obj_atk_guassian.py:96-101 (scipy gaussian_filter + clip, all steps)   (K26)
     dmh::gauss_blur_compose   phy_obj_atk_guassian.py:103                       (K26, writes ``out``)
+    dmh::square_propose       phy_obj_atk_square.py:259-260,284-291,312-313     (K27, in place)
     dmh::l0_fused_step        phy_obj_atk_l0.py:105-111,136-138,94-99           (K23, in place)
     dmh::eigen_gt_stats       MD2/evaluate_depth.py:360-373,377 (ground truth)  (K25)
     dmh::eigen_depth_errors   MD2/evaluate_depth.py:351-384, :102-110, :61-76   (K25)
@@ -316,6 +317,18 @@ def _(windows, index, obj, out, r0, r1, c0, c1):
     return None
 
 
+# ---------------------------------------------------------------------------------------------------------------- K27
+@custom_op("dmh::square_propose", mutates_args=("x_best", "x_new"))
+def square_propose(x0: torch.Tensor, x_best: torch.Tensor, x_new: torch.Tensor, table: torch.Tensor, stripes: torch.Tensor,
+                   state: torch.Tensor, eps: float) -> None:
+    ops.square_propose(x0, x_best, x_new, table, stripes, state, eps)
+
+
+@square_propose.register_fake
+def _(x0, x_best, x_new, table, stripes, state, eps):
+    return None
+
+
 # ----------------------------------------------------------------------------------------------------------------- K5
 @custom_op("dmh::l0_compose", mutates_args=())
 def l0_compose(obj: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, l0_clip: float, finalize: bool) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -600,4 +613,4 @@ smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
-       "gauss_blur_windows", "gauss_blur_compose", "eigen_gt_stats", "eigen_depth_errors")
+       "gauss_blur_windows", "gauss_blur_compose", "square_propose", "eigen_gt_stats", "eigen_depth_errors")

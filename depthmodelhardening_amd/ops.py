@@ -779,6 +779,99 @@ def gauss_blur_compose(windows, index, obj, region=GAUSS_REGION, out=None):
     return out
 
 
+def square_sides(n_queries, c, h, w, p_init=0.8, resc_schedule=True):
+    """Host: the side of the square of every iteration of a Square attack of ``n_queries`` iterations on a c x h x w object, in
+    Python floats as the reference makes it: ``p_selection`` (phy_obj_atk_square.py:222-249, with ``int(it / n_queries *
+    10000)`` under ``resc_schedule``) and ``s = max(int(round(sqrt(p * n_features / c))), 1)`` (:281)."""
+    import math
+    n_queries = int(n_queries)
+    if n_queries < 1:
+        raise RuntimeError("square_sides: need at least one query")
+    n_features, out = c * h * w, []
+    for it in range(n_queries):
+        if resc_schedule:
+            it = int(it / n_queries * 10000)
+        p = p_init
+        for above, div in ((10, 2), (50, 4), (200, 8), (500, 16), (1000, 32), (2000, 64), (4000, 128), (6000, 256), (8000, 512)):
+            if it > above:
+                p = p_init / div
+        out.append(max(int(round(math.sqrt(p * n_features / c))), 1))
+    return out
+
+
+def square_table(n_queries, c, h, w, p_init=0.8, resc_schedule=True):
+    """Host: every draw of a Square attack, from the CPU torch global generator with the reference's expressions in its call
+    order -- the start stripes ``sign(2 rand([1, c, 1, w]) - 1)`` (:259-260, :173-175), then per iteration ``vh``, ``vw`` =
+    ``(0 + (h - s - 0) rand([1])).long()`` (:177-179, :282-283) and the signs ``sign(2 rand([c, 1, 1]) - 1)`` (:286).
+    Returns (table int32 [n_queries + 1, 3 + c] = (vh, vw, s, signs) with row q the square of iteration q - 1 and row 0 zero:
+    query 0 is the stripes; stripes fp32 [c, w]).  A side larger than min(h, w) -- where the reference would slice with a negative
+    bound -- is refused before any draw."""
+    sides = square_sides(n_queries, c, h, w, p_init, resc_schedule)
+    if max(sides) > min(h, w):
+        raise RuntimeError("square_table: the schedule's largest square (%d) exceeds the %d x %d object; lower p_init"
+                           % (max(sides), h, w))
+    stripes = torch.sign(2 * torch.rand([1, c, 1, w]) - 1).reshape(c, w).contiguous()
+    table = np.zeros((len(sides) + 1, 3 + c), dtype=np.int32)
+    for row, s in zip(table[1:], sides):
+        vh = (0 + (h - s - 0) * torch.rand([1])).long()
+        vw = (0 + (w - s - 0) * torch.rand([1])).long()
+        sign = torch.sign(2 * torch.rand([c, 1, 1]) - 1)
+        row[0], row[1], row[2] = int(vh), int(vw), s
+        row[3:] = sign.reshape(c).numpy()
+    return table, stripes
+
+
+def _square_operands(name, x0, x_best, x_new, table, stripes):
+    if x0.dtype != torch.float32 or x0.dim() not in (3, 4) or (x0.dim() == 4 and x0.shape[0] != 1):
+        raise RuntimeError("%s: x0 must be fp32 [1, C, H, W] or [C, H, W]" % name)
+    C_, H, W = (int(v) for v in x0.shape[-3:])
+    for t in (x_best, x_new):
+        if t.dtype != torch.float32 or t.numel() != x0.numel() or tuple(t.shape[-3:]) != (C_, H, W):
+            raise RuntimeError("%s: x_best and x_new must be fp32 of x0's size" % name)
+    ptrs = {x0.data_ptr(), x_best.data_ptr(), x_new.data_ptr()}
+    if len(ptrs) != 3:
+        raise RuntimeError("%s: x0, x_best and x_new must be three different buffers" % name)
+    if table.dtype != torch.int32 or table.dim() != 2 or int(table.shape[0]) < 1 or int(table.shape[1]) != 3 + C_:
+        raise RuntimeError("%s: table must be int32 [n, %d]" % (name, 3 + C_))
+    if stripes.dtype != torch.float32 or tuple(stripes.shape) != (C_, W):
+        raise RuntimeError("%s: stripes must be fp32 [%d, %d]" % (name, C_, W))
+    return C_, H, W
+
+
+def square_propose(x0, x_best, x_new, table, stripes, state, eps):
+    """K27, in place, driven by K24's ``state`` = (cursor q, best query) on the device: if query q - 1 became the best,
+    ``x_best`` <- ``x_new``; then ``x_new`` <- the candidate of query q -- the stripes for q = 0, else ``x_best`` with the square
+    of ``table`` row q pushed by 2 eps sign_c and projected onto [x0 - eps, x0 + eps] and [0, 1] (phy_obj_atk_square.py:284-291),
+    bit-equal to the torch expression.  q = n only absorbs; any other q outside [0, n) does nothing."""
+    C_, H, W = _square_operands("square_propose", x0, x_best, x_new, table, stripes)
+    if state.dtype != torch.int32 or state.numel() < 2:
+        raise RuntimeError("square_propose: state must be int32[2]")
+    if not float(eps) >= 0.0:
+        raise RuntimeError("square_propose: eps must not be negative")
+    N.check(N.lib().dmh_square_propose(N.ptr(x0), N.ptr(x_best), N.ptr(x_new), N.ptr(table), N.ptr(stripes), N.ptr(state),
+                                       int(table.shape[0]), C_, H, W, float(eps), N.stream()))
+    return x_new
+
+
+def square_host(x0, x_best, x_new, table, stripes, q, accept, eps):
+    """Host twin of K27 in torch on the CPU (``Phy_obj_atk_Square(host_chain=True)``): returns the new (x_best, x_new) for query
+    ``q`` after the decision ``accept`` about query q - 1, with the reference's own expressions (:259-260, :284-291)."""
+    C_, H, W = _square_operands("square_host", x0, x_best, x_new, torch.as_tensor(table), stripes)
+    n = len(table)
+    if accept and 0 < q <= n:
+        x_best = x_new.clone()
+    if q == 0:
+        x_new = torch.clamp(x0 + eps * stripes.reshape(1, C_, 1, W), 0., 1.).reshape(x0.shape)
+    elif 0 < q < n:
+        vh, vw, s = (int(v) for v in table[q][:3])
+        new_deltas = torch.zeros([C_, H, W])
+        new_deltas[:, vh:vh + s, vw:vw + s] = 2. * eps * torch.as_tensor(table[q][3:]).float().reshape(C_, 1, 1)
+        x_new = x_best.reshape(C_, H, W) + new_deltas
+        x_new = torch.min(torch.max(x_new, x0.reshape(C_, H, W) - eps), x0.reshape(C_, H, W) + eps)
+        x_new = torch.clamp(x_new, 0., 1.).reshape(x0.shape)
+    return x_best, x_new
+
+
 class _L0Compose(torch.autograd.Function):
     @staticmethod
     def forward(ctx, obj, pos, neg, l0_clip, finalize):

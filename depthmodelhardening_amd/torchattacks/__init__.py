@@ -1,7 +1,7 @@
 """The depth attacks of the reference's patched ``torchattacks`` package that the training path uses
 (torchattacks/__init__.py:6-8), and the evaluation attacks built so far: Auto-PGD on the object patch
 (MD2/evaluate_depth.py:138-141), the tube-light random search with its no-op paste (:150-151, :178-182), the Gaussian-blur search
-(:148-149) and the random-patch baseline (:146-147).  The stock classification attacks and the other evaluation-only physical
+(:148-149), the random-patch baseline (:146-147) and the Square attack (:142-145).  The stock classification attacks and the other evaluation-only physical
 variants are out of scope."""
 from .attack import Attack
 from .attacks.pgd_depth import PGD_depth
@@ -11,6 +11,7 @@ from .attacks.phy_obj_atk_arbi import Phy_obj_atk_arbi
 from .attacks.phy_obj_atk_guassian import Phy_obj_atk_guassian
 from .attacks.phy_obj_atk_l0 import Phy_obj_atk_l0
 from .attacks.phy_obj_atk_light import Phy_obj_atk_light
+from .attacks.phy_obj_atk_square import Phy_obj_atk_Square
 from .attacks.phy_obj_atk_vanila import Phy_obj_atk_vanila
 
-__all__ = ["Attack", "PGD_depth", "Phy_obj_atk", "Phy_obj_atk_APGD", "Phy_obj_atk_arbi", "Phy_obj_atk_guassian", "Phy_obj_atk_l0", "Phy_obj_atk_light", "Phy_obj_atk_vanila"]
+__all__ = ["Attack", "PGD_depth", "Phy_obj_atk", "Phy_obj_atk_APGD", "Phy_obj_atk_arbi", "Phy_obj_atk_guassian", "Phy_obj_atk_l0", "Phy_obj_atk_light", "Phy_obj_atk_Square", "Phy_obj_atk_vanila"]

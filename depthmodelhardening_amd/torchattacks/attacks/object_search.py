@@ -29,9 +29,20 @@ class _ObjectSearch(Phy_obj_atk):
                                         loop, in its own order; compose(cursor, out) writes the patch of query cursor[0] to out
         _host_patches(obj, ctx)         make(q): the patch of query q, made on the host and uploaded
         _trace_fields(ctx, q)           its part of query q's trace dict
+
+    and may replace what a search whose candidates depend on the model's answers (Phy_obj_atk_Square) does differently:
+
+        shared_poses                    True: ONE pose set, window plan and coefficient row for all queries (_pose_draws returns
+                                        one draw) instead of one per query
+        _pose_draws(batch_size, n)      the pose draws of the search (default: one _draw() per query)
+        _pasted(q, patch)               the buffer query q pastes (default: the composed patch)
+        _run_queries(n, query)          the loop over query(q) (default: q = 0 .. n - 1, eagerly)
+        _finish(compose, state, patch, adv_patch)    the best patch into adv_patch (default: recomposed from the best index)
+        _record(costs, best)            bookkeeping of its own from the one copy of the cost array
     """
 
     noun = "query"
+    shared_poses = False
 
     def __init__(self, model, obj_img, obj_mask, host_chain=False, **kw):
         super().__init__(model, obj_img, obj_mask, **kw)
@@ -64,16 +75,18 @@ class _ObjectSearch(Phy_obj_atk):
         # every draw up front, in the reference's order: the subclass's own, one project() per query, the two samples of the
         # returned scenes
         n, ctx = self._prepare(obj)
-        draws = [self._draw(batch_size) for _ in range(n)]
+        draws = self._pose_draws(batch_size, n)
+        pose = (lambda q: 0) if self.shared_poses else (lambda q: q)
         z0_sample, alpha_sample = self._draw(batch_size, explicit=True)
         self._eval_pose(z0_sample, alpha_sample, eval)
         coeffs = self._coeffs(draws + [(z0_sample, alpha_sample)])
         plans, tabs, clean = self._window_plans(draws, scene_imgs, mask, coeffs[0])
 
         def cost_of(patch, q):
-            adv, m = ops.eot_paste(scene_imgs, patch, mask, coeffs[q], l_pad, t_pad, self.scene_size)
+            p = pose(q)
+            adv, m = ops.eot_paste(scene_imgs, patch, mask, coeffs[p], l_pad, t_pad, self.scene_size)
             if plans is not None:
-                return self.model.masked_sq_mean(adv, m, plans[q], tabs[q], clean)
+                return self.model.masked_sq_mean(adv, m, plans[p], tabs[p], clean)
             return ops.masked_sq_mean(self.model(adv), m)        # MSE(adv_depth * mask, 0): minimised
 
         adv_patch = torch.zeros_like(obj)
@@ -86,20 +99,41 @@ class _ObjectSearch(Phy_obj_atk):
                 # a throwaway cost of the clean object at query 0's poses: the first model call of a frozen-weights scope fills
                 # its caches (transformed filters, BatchNorm affines), one-time host work that is no part of any query
                 cost_of(obj, 0)
+
+                def query(q):
+                    compose(state, patch)
+                    ops.tube_light_commit(cost_of(self._pasted(q, patch), q).reshape(1), cost_arr, best_cost, state)
+
                 with self.loop_context():
-                    for q in range(n):
-                        compose(state, patch)
-                        ops.tube_light_commit(cost_of(patch, q).reshape(1), cost_arr, best_cost, state)
-                compose(state[1:], adv_patch)       # the best query's patch, bit for bit
+                    self._run_queries(n, query)
+                self._finish(compose, state, patch, adv_patch)
             costs, best = cost_arr.cpu().numpy(), int(state.cpu()[1])       # the reads of the search: after it
         self.costs, self.best_index = costs, best
+        self._record(costs, best)
         if best < 0:
             raise RuntimeError("%s: no %s had a cost below 1e10 (non-finite model output?)" % (name, self.noun))
         if self.trace is not None:
             for q in range(n):
-                self.trace.append(dict(cost=float(costs[q]), **self._trace_fields(ctx, q), z0=list(draws[q][0]),
-                                       alpha=list(draws[q][1])))
+                self.trace.append(dict(cost=float(costs[q]), **self._trace_fields(ctx, q), z0=list(draws[pose(q)][0]),
+                                       alpha=list(draws[pose(q)][1])))
         return self._return_scenes(scene_imgs, adv_patch, obj, mask, coeffs[-1])
+
+    # ------------------------------------------------------------------------------ hooks: the defaults are the searches above
+    def _pose_draws(self, batch_size, n):
+        return [self._draw(batch_size) for _ in range(n)]
+
+    def _pasted(self, q, patch):
+        return patch
+
+    def _run_queries(self, n, query):
+        for q in range(n):
+            query(q)
+
+    def _finish(self, compose, state, patch, adv_patch):
+        compose(state[1:], adv_patch)       # the best query's patch, bit for bit
+
+    def _record(self, costs, best):
+        pass
 
     def _host_search(self, obj, n, ctx, cost_of, adv_patch):
         """The reference's loop shape on this project's paste and cost: one upload and one host comparison per query.

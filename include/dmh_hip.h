@@ -288,6 +288,26 @@ int dmh_gauss_blur_compose(const float* windows, const int32_t* index, const flo
                            int W, int r0, int r1, int c0, int c1, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K27  Square attack (L_inf) on the object patch: absorb the previous query's decision and make the next candidate, one launch.
+ * Replaces: phy_obj_atk_square.py:259-260 (start stripes), :284-291 (candidate), :312-313 (x_best update); the strict
+ * keep-the-best (:298-301) is dmh_tube_light_commit, which also advances the cursor.
+ *   x0       float [C][H][W]: the clean object.   x_best, x_new: float [C][H][W], updated in place.  Three different buffers.
+ *   table    int32 [n_queries][3 + C]: vh, vw, s, sign_0 .. sign_{C-1} (each -1, 0 or 1) per query; row 0 is not read.
+ *   stripes  float [C][W]: +-1, the start point.
+ *   state    int32[2] of K24: 0 the cursor q, 1 the best query.  Only read.
+ * With accept = (0 < q <= n_queries and state[1] == q - 1), per element:
+ *   xb = accept ? x_new : x_best;  x_best <- xb;
+ *   q == 0:            x_new <- clamp(x0 + eps stripe, 0, 1)
+ *   0 < q < n_queries: x_new <- clamp(min(max(xb + 2 eps sign_c, x0 - eps), x0 + eps), 0, 1) for vh <= y < vh + s and
+ *                      vw <= x < vw + s, xb elsewhere
+ *   q == n_queries:    x_new stays (the absorb-only call after the last query);  any other q: nothing is written.
+ * Every operation is one rounded fp32 operation: bit-equal to the element-wise expression.  16-byte accesses when W % 4 == 0 and
+ * x0, x_best, x_new and stripes are 16-byte aligned, a scalar form otherwise.
+ * ---------------------------------------------------------------------------------- */
+int dmh_square_propose(const float* x0, float* x_best, float* x_new, const int32_t* table, const float* stripes,
+                       const int32_t* state, int n_queries, int C, int H, int W, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K25  Benign depth evaluation (MD2/evaluate_depth.py:351-391): depth at ground-truth resolution, exact medians, eight metrics.
  *   gt       float [gt_len]: the ground-truth maps of a pack, one after the other.
  *   table    int32 [n_images][DMH_EIGEN_REC]: 0 offset into gt, 1 gt_h, 2 gt_w, 3 y0, 4 y1, 5 x0, 6 x1 (crop; the whole map for
