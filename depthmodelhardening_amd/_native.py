@@ -86,6 +86,8 @@ _SIGNATURES = {
     "dmh_gauss_blur_windows": (C.c_int, [_fp] * 5 + [C.c_int] * 9 + [_fp]),
     "dmh_gauss_blur_compose": (C.c_int, [_fp] * 4 + [C.c_int] * 8 + [_fp]),
     "dmh_square_propose": (C.c_int, [_fp] * 6 + [C.c_int] * 4 + [C.c_float, _fp]),
+    "dmh_pgd_l2_workspace_size": (C.c_int64, [C.c_int64]),
+    "dmh_pgd_l2_step": (C.c_int, [_fp, _fp, _fp, C.c_double, C.c_double, _fp, C.c_int64, _fp, C.c_int64, _fp]),
     "dmh_eigen_select_ws_size": (C.c_int64, [C.c_int]),
     "dmh_eigen_partials_size": (C.c_int64, [C.c_int]),
     "dmh_eigen_gt_stats": (C.c_int, [_fp, C.c_int64, _fp, _fp] + [C.c_int] * 7 + [_fp] * 4),

@@ -17,7 +17,7 @@ from .datasets import make_object
 from .layers import disp_to_depth
 from .my_utils import to_device_async
 from .torchattacks import (PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_arbi, Phy_obj_atk_guassian, Phy_obj_atk_l0,
-                           Phy_obj_atk_light, Phy_obj_atk_Square, Phy_obj_atk_vanila)
+                           Phy_obj_atk_l2, Phy_obj_atk_light, Phy_obj_atk_Square, Phy_obj_atk_vanila)
 
 STEREO_SCALE_FACTOR = 5.4
 MIN_DEPTH = 1e-3
@@ -44,7 +44,8 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
     The two gradient-free rows "guassian" and "arbi" are served when ``args['gradient_free_attacks']`` is true: without the key
     they are refused like every unserved ``norm_type``, as they were before the rows existed.  In the same way the "Square" row
     is served when ``args['square_attack']`` is true (``query_patch``: "candidate", or "best" for the reference's line
-    phy_obj_atk_square.py:295; ``graph_attack``: replay the query from a HIP graph)."""
+    phy_obj_atk_square.py:295; ``graph_attack``: replay the query from a HIP graph), and the "l_2" row when ``args['l2_attack']``
+    is true (``epsilon``, ``alpha`` -- which the attack ignores -- and ``step`` as at :134-137; ``graph_attack`` as above)."""
     device = next(model2atk.parameters()).device
     obj_tensor, mask_tensor = make_object(device)
     if args['norm_type'] == "l_inf":
@@ -62,6 +63,10 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
     elif args['norm_type'] == "Square" and args.get('square_attack'):               # :142-145
         depth_atk = Phy_obj_atk_Square(model2atk, obj_tensor, mask_tensor, eps=args['epsilon'], n_queries=args['n_queries'],
                                        query_patch=args.get('query_patch', 'candidate'))
+        depth_atk.use_graph = bool(args.get('graph_attack', False))
+    elif args['norm_type'] == "l_2" and args.get('l2_attack'):                      # :133-137; alpha is passed and ignored
+        depth_atk = Phy_obj_atk_l2(model2atk, obj_tensor, mask_tensor, eps=args['epsilon'], alpha=args['alpha'],
+                                   steps=args['step'])
         depth_atk.use_graph = bool(args.get('graph_attack', False))
     elif args['norm_type'] == "light":      # :150-151; ``n_init`` / ``n_search``: the reference's literals 200 and 20
         depth_atk = Phy_obj_atk_light(model2atk, obj_tensor, mask_tensor, n_init=args.get('n_init', 200),

@@ -19,6 +19,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::gauss_blur_windows   phy_obj_atk_guassian.py:96-101 (scipy gaussian_filter + clip, all steps)   (K26)
     dmh::gauss_blur_compose   phy_obj_atk_guassian.py:103                       (K26, writes ``out``)
     dmh::square_propose       phy_obj_atk_square.py:259-260,284-291,312-313     (K27, in place)
+    dmh::pgd_l2_step          phy_obj_atk_l2.py:110-120, shared-patch form      (K28)
     dmh::l0_fused_step        phy_obj_atk_l0.py:105-111,136-138,94-99           (K23, in place)
     dmh::eigen_gt_stats       MD2/evaluate_depth.py:360-373,377 (ground truth)  (K25)
     dmh::eigen_depth_errors   MD2/evaluate_depth.py:351-384, :102-110, :61-76   (K25)
@@ -201,6 +202,17 @@ def pgd_linf_step(x: torch.Tensor, x0: torch.Tensor, grad: torch.Tensor, alpha: 
 
 
 @pgd_linf_step.register_fake
+def _(x, x0, grad, alpha, eps):
+    return torch.empty_like(x)
+
+
+# ---------------------------------------------------------------------------------------------------------------- K28
+@custom_op("dmh::pgd_l2_step", mutates_args=())
+def pgd_l2_step(x: torch.Tensor, x0: torch.Tensor, grad: torch.Tensor, alpha: float, eps: float) -> torch.Tensor:
+    return ops.pgd_l2_step(_cu(x), _cu(x0), _cu(grad), alpha, eps)
+
+
+@pgd_l2_step.register_fake
 def _(x, x0, grad, alpha, eps):
     return torch.empty_like(x)
 
@@ -613,4 +625,4 @@ smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
-       "gauss_blur_windows", "gauss_blur_compose", "square_propose", "eigen_gt_stats", "eigen_depth_errors")
+       "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors")

@@ -514,6 +514,32 @@ def pgd_linf_step(x, x0, grad, alpha, eps, out=None):
     return out
 
 
+def pgd_l2_workspace(n, device):
+    """The float64 workspace of pgd_l2_step for tensors of ``n`` elements: K28's per-workgroup partial sums."""
+    return torch.empty(int(N.lib().dmh_pgd_l2_workspace_size(int(n))) // 8, device=device, dtype=torch.float64)
+
+
+def pgd_l2_step(x, x0, grad, alpha, eps, out=None, workspace=None):
+    """K28: y = x + alpha grad / (||grad||_2 + 1e-10); out = clamp(x0 + (y - x0) min(eps / ||y - x0||_2, 1), 0, 1), with ONE norm
+    over the whole tensor (phy_obj_atk_l2.py:110-120, shared-patch form).  Two launches, no host read.  ``workspace``:
+    pgd_l2_workspace(x.numel(), x.device), written by every call (one is allocated when none is given: not inside a graph capture
+    that is to be replayed).  ``out`` must be a tensor of its own."""
+    x, x0, grad = _c(x.detach()), _c(x0), _c(grad)
+    if x.shape != x0.shape or x.shape != grad.shape:
+        raise RuntimeError("pgd_l2_step: shape mismatch")
+    if not float(eps) >= 0.0:
+        raise RuntimeError("pgd_l2_step: eps must not be negative")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape:
+        raise RuntimeError("pgd_l2_step: shape mismatch")
+    if workspace is None:
+        workspace = pgd_l2_workspace(x.numel(), x.device)
+    N.check(N.lib().dmh_pgd_l2_step(N.ptr(x), N.ptr(x0), N.ptr(grad), float(alpha), float(eps), N.ptr(out), x.numel(),
+                                    N.ptr_f64(workspace), workspace.numel() * 8, N.stream()))
+    return out
+
+
 APGD_REC = 16       # floats per controller record (DMH_APGD_REC)
 
 

@@ -50,6 +50,18 @@ class Phy_obj_atk(ObjectAttack):
         # use_graph, common_windows, shard, use_roi: see ObjectAttack.  _capture_fault makes the capture of _graph_steps fail
         # after its first launch.
 
+    # the two pieces a subclass with another norm swaps (Phy_obj_atk_l2)
+    def _random_start(self, obj_img_adv):
+        """The noise added to the clean patch before the first step (:83-85), on the attack's device."""
+        noise = self.random_start_noise
+        if noise is None:
+            noise = torch.empty_like(obj_img_adv).uniform_(-self.eps, self.eps)
+        return noise.to(self.device)
+
+    def _step(self, x, grad, out=None):
+        """The patch after one update (:98-101): K4."""
+        return ops.pgd_linf_step(x, self.obj_img, grad, self.alpha, self.eps, out=out)
+
     def forward(self, images, batch_size, cfg_path=f'{object_dataset_root}/training/calib/003086.txt', eval=False):
         r"""
         images: scene image, 1*3*375*1242 (tiled over the batch) or batch_size*3*375*1242.
@@ -68,10 +80,7 @@ class Phy_obj_atk(ObjectAttack):
 
         obj_img_adv = self.obj_img.clone().detach()
         if self.random_start:
-            noise = self.random_start_noise
-            if noise is None:
-                noise = torch.empty_like(obj_img_adv).uniform_(-self.eps, self.eps)
-            noise = noise.to(self.device)
+            noise = self._random_start(obj_img_adv)
             if mine is not None:
                 dist.broadcast(noise, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
             obj_img_adv = torch.clamp(obj_img_adv + noise, min=0, max=1).detach()
@@ -123,7 +132,7 @@ class Phy_obj_atk(ObjectAttack):
                 dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=group)
             if self.trace is not None:
                 self.trace.append((float(cost), grad.detach().clone()))
-            obj_img_adv = ops.pgd_linf_step(obj_img_adv, self.obj_img, grad, self.alpha, self.eps)
+            obj_img_adv = self._step(obj_img_adv, grad)
 
         return self._return_scenes(scene_imgs, obj_img_adv, self.obj_img, mask, coeffs[-1])
 
@@ -143,7 +152,7 @@ class Phy_obj_atk(ObjectAttack):
             adv, m = ops.eot_paste(scene_imgs, p, mask, coeff_cur, l_pad, t_pad, self.scene_size)
             cost = self._neg_cost(adv, m, plan, tab_cur, clean)
             (grad,) = torch.autograd.grad(cost, p, grad_outputs=self._one)
-            ops.pgd_linf_step(p, self.obj_img, grad, self.alpha, self.eps, out=patch_out)
+            self._step(p, grad, out=patch_out)
             patch_in.copy_(patch_out)
 
         step()                                              # step 0, eager
@@ -176,7 +185,7 @@ class Phy_obj_atk(ObjectAttack):
         for _ in range(self.steps):
             grad = torch.zeros_like(obj_img_adv)
             dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=group)
-            obj_img_adv = ops.pgd_linf_step(obj_img_adv, self.obj_img, grad, self.alpha, self.eps)
+            obj_img_adv = self._step(obj_img_adv, grad)
         self.phy_trans_adv.reset_img(obj_img_adv, self.obj_mask)
         empty = obj_img_adv.new_zeros((0, 3) + tuple(self.scene_size))
         return empty, empty.clone(), obj_img_adv.new_zeros((0, 1) + tuple(self.scene_size)), obj_img_adv

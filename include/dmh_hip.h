@@ -308,6 +308,21 @@ int dmh_square_propose(const float* x0, float* x_best, float* x_new, const int32
                        const int32_t* state, int n_queries, int C, int H, int W, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K28  PGD-L2 update on n floats with ONE norm over the whole tensor, two launches, no host read, no atomics:
+ *   y = x + alpha g / (||g||_2 + 1e-10);  d = y - x0;  out = clamp(x0 + d min(eps / ||d||_2, 1), 0, 1)
+ * Replaces: phy_obj_atk_l2.py:110-120 (shared-patch form).
+ *   workspace: dmh_pgd_l2_workspace_size(n) bytes, 8-byte aligned: the per-workgroup double partials of sum(g g),
+ *              sum((x - x0) g), sum((x - x0)^2) that launch 1 writes and every workgroup of launch 2 adds in index order.
+ *              Written by every call: two calls in flight need two workspaces.
+ * ||d||^2 comes from the expansion sum((x-x0)^2) + 2 s sum((x-x0) g) + s^2 sum(g g), s = alpha / (||g|| + 1e-10); eps / 0 gives
+ * the factor 1.  Scalars and the element-wise expression are evaluated in double and rounded to fp32 once; the result is bitwise
+ * reproducible.  out must not alias x, x0 or g.  16-byte accesses when x, x0, g and out are 16-byte aligned, scalar otherwise.
+ * ---------------------------------------------------------------------------------- */
+int64_t dmh_pgd_l2_workspace_size(int64_t n);
+int dmh_pgd_l2_step(const float* x, const float* x0, const float* g, double alpha, double eps, float* out, int64_t n,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * K25  Benign depth evaluation (MD2/evaluate_depth.py:351-391): depth at ground-truth resolution, exact medians, eight metrics.
  *   gt       float [gt_len]: the ground-truth maps of a pack, one after the other.
  *   table    int32 [n_images][DMH_EIGEN_REC]: 0 offset into gt, 1 gt_h, 2 gt_w, 3 y0, 4 y1, 5 x0, 6 x1 (crop; the whole map for
