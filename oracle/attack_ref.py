@@ -193,10 +193,15 @@ def l0_mask_cost(pos_t, neg_t):
 
 
 def phy_obj_atk_l0(model, obj_img, obj_mask, images, batch_size, adam_lr=0.5, steps=10, mask_wt=0.1,
-                   l0_thresh=0.1, dist_range=None, eval=False, P2=KITTI_P2, record=None, color_aug=None):
+                   l0_thresh=0.1, dist_range=None, eval=False, P2=KITTI_P2, record=None, color_aug=None, grad_record=None,
+                   patterns=None):
     """Phy_obj_atk_l0.forward (phy_obj_atk_l0.py:54-174) under Attack.__call__'s eval-mode bracket.  ``color_aug``: the
     callable the constructor got from ColorJitter.get_params (:41; tv082.color_jitter_get_params) when ``color_jit`` is set
-    (:122-124), None otherwise."""
+    (:122-124), None otherwise.  ``record``: optional list that receives (l0, mask_weight, adv_cost, mask_cost) of every
+    iteration; ``grad_record``: one that receives the two pattern gradients Adam is handed (the twin of the HIP class's
+    ``grad_trace``); ``patterns``: one that receives the final (pos_t, neg_t).
+    The arithmetic follows ``obj_img.dtype``: the two start patterns are the reference's fp32 roundings of numpy's float64 draws
+    (``torch.Tensor(init)``, :73-83) in either case, so a float64 run starts where the fp32 one does."""
     dist_range = list(range(5, 31, 2)) if dist_range is None else dist_range
     clip_max = 1
     l0_clip = clip_max / 255.0
@@ -211,13 +216,13 @@ def phy_obj_atk_l0(model, obj_img, obj_mask, images, batch_size, adam_lr=0.5, st
     for _ in range(2):
         init = np.random.random(obj_img.size()) * clip_max
         init = np.clip(init, 0.0, clip_max) / clip_max
-        t = torch.Tensor(init)
+        t = torch.Tensor(init).to(obj_img.dtype)
         t.requires_grad = True
         pats.append(t)
     pos_t, neg_t = pats
     loss = nn.MSELoss()
     opt = torch.optim.Adam([pos_t, neg_t], lr=adam_lr, betas=(0.5, 0.9))
-    target = torch.zeros((batch_size, 1, SCENE_SIZE[0], SCENE_SIZE[1]))
+    target = torch.zeros((batch_size, 1, SCENE_SIZE[0], SCENE_SIZE[1]), dtype=obj_img.dtype)
     l0_init = None
     for stp in range(steps * 2):
         p_pos = torch.clamp(pos_t * clip_max, min=0.0, max=clip_max)
@@ -242,9 +247,13 @@ def phy_obj_atk_l0(model, obj_img, obj_mask, images, batch_size, adam_lr=0.5, st
         total = adv_cost + mw * mask_cost
         opt.zero_grad()
         total.backward()
+        if grad_record is not None:
+            grad_record.append((pos_t.grad.detach().clone(), neg_t.grad.detach().clone()))
         opt.step()
         if record is not None:
             record.append((int(l0), float(mw), float(adv_cost.detach()), float(mask_cost.detach())))
+    if patterns is not None:
+        patterns.append((pos_t.detach().clone(), neg_t.detach().clone()))
     p_pos = torch.clamp(pos_t * clip_max, min=0.0, max=clip_max).detach()
     p_neg = -torch.clamp(neg_t * clip_max, min=0.0, max=clip_max).detach()
     p_pos[p_pos < l0_clip] = 0
@@ -265,8 +274,10 @@ def phy_obj_atk_l0(model, obj_img, obj_mask, images, batch_size, adam_lr=0.5, st
 
 
 def pgd_depth(model, images, eps=0.3, alpha=2 / 255, steps=40, random_start=True, targeted=False,
-              start_noise=None, record=None):
-    """PGD_depth.forward (pgd_depth.py:41-80) under Attack.__call__'s eval bracket."""
+              start_noise=None, record=None, trace=None):
+    """PGD_depth.forward (pgd_depth.py:41-80) under Attack.__call__'s eval bracket.  ``record``: optional list that receives
+    the frames after every step; ``trace``: one that receives (cost, gradient).  The arithmetic follows ``images.dtype``
+    (hand a float64 run its start through ``start_noise``: the draw itself depends on the dtype)."""
     given_training = model.training
     model.eval()
     images = tv082.resize(images, SCENE_SIZE).detach()
@@ -282,6 +293,8 @@ def pgd_depth(model, images, eps=0.3, alpha=2 / 255, steps=40, random_start=True
         out = model(adv)
         cost = -loss(out, depth_target) if targeted else loss(out, depth_gt)
         grad = torch.autograd.grad(cost, adv, retain_graph=False, create_graph=False)[0]
+        if trace is not None:
+            trace.append((float(cost), grad.detach().clone()))
         adv = adv.detach() + alpha * grad.sign()
         delta = torch.clamp(adv - images, min=-eps, max=eps)
         adv = torch.clamp(images + delta, min=0, max=1).detach()

@@ -1,4 +1,35 @@
-"""Attack loops on the HIP kernels vs the CPU oracle and vs golden vectors produced by the reference."""
+"""Attack loops on the HIP kernels vs the CPU oracle and vs golden vectors produced by the reference.
+
+The three attacks of the training path (Phy_obj_atk, Phy_obj_atk_l0, PGD_depth) are also held to the float64 form of the
+oracle on the same inputs, recorded in tests/golden/atk_{linf,l0,pgd}_f64.npz by tools/make_goldens_f64.py.  The rule is the one
+of tests/test_gpu_l2.py: with e_ref = the fp32 oracle's own distance from the float64 trajectory (taken from the fixture, never
+from the HIP run), HIP may be 20 e_ref away; where e_ref is 0, one fp32 rounding (2^-24), or 5 texels for a texel count.
+Distances and bounds: oracle/f64_anchor.py; every test prints e_ref, the HIP figure and the bound side by side.
+
+Measured on one MI355X (e_ref -> HIP; all against float64, on the fixtures' subsamples):
+  L_inf  cost per step 9.7e-8, 5.1e-8, 4.9e-8 -> the same three values; first gradient rel-L2 8.84e-5 -> 8.90e-5, signs differing
+         0 -> 0, non-zero where float64 is zero 0 -> 0; patch texels beyond 1e-5: 0 -> 0 of 58,500.
+  L0     (default and fused alike) adv_cost per iteration 3.9e-9, 3.0e-7, 1.8e-7, 3.1e-6, 1.0e-6, 7.7e-7 -> 3.9e-9, 2.0e-7, 1.3e-6,
+         4.9e-6, 6.0e-7, 4.2e-6; mask_cost 1.0e-8, 8.0e-8, 6.1e-8, 3.6e-7, 1.9e-9, 2.6e-7 -> 1.0e-8, 8.0e-8, 2.9e-7, 7.1e-7,
+         2.4e-7, 1.0e-7 (iteration 4 is the one step anywhere beyond 20 x its own e_ref: oracle/f64_anchor.bound says why an
+         e_ref below one fp32 rounding counts as one); l0 differing by <= 3 -> <= 4; first pattern gradients rel-L2 3.76e-5 /
+         3.15e-5 -> 3.74e-5 / 3.14e-5; texels beyond 2e-3 (1e-2): pos 163 (18) -> 228 (27), neg 72 (19) -> 102 (24), patch 82 (8)
+         -> 119 (16) of 58,500; adv_sum 2.6e-6 -> 3.5e-6.
+  L0, the second case (2 steps): adv_cost 5.8e-8 ... 5.0e-6 -> 5.8e-8 ... 5.0e-6, mask_cost <= 2.7e-7 -> <= 2.7e-7, l0 equal.
+  PGD    rows beyond 1e-6: 0 -> 0 of 15,360, targeted and untargeted; adv_sum 1.1e-8 / 4.9e-7 -> 1.1e-8 / 4.6e-7.
+  Sums of the returned scenes (asserted like the rest): L_inf adv_sum 1.90e-8 -> 1.90e-8, ben_sum 2.23e-8 -> 2.23e-8,
+         mask_out_sum 6.99e-8 -> 6.99e-8; L0 ben_sum 2.53e-8 -> 2.52e-8, mask_out_sum 1.81e-7 -> 1.81e-7.
+  Against the reference's own fp32 run: L_inf patch and PGD rows 0 texels beyond tau; L0 pos / neg / patch 63 / 30 / 35 texels
+         beyond 2e-3 (cap 585), the final l0 count 1 pixel off (cap 5, as before), adv_sum 8.8e-7.
+For the L0 trajectory 20 x e_ref is, in texels, WIDER than the fraction these tests had: pos / neg may have 3260 / 1440 of 58,500
+beyond 2e-3 of float64 (5.6 % / 2.5 %; the old gate was 1 % of them, against the reference's run).  That is the rule applied to
+an e_ref of 163 / 72 texels, not a measurement of HIP (228 / 102).  The tighter gate on the L0 trajectory is therefore the count
+against the reference's own fp32 run, kept at no more than the old 1 % (585 texels) by _vs_reference_cap, beside the float64 one
+at 1e-2 (360 / 380) and the final l0 count (within 5 of the reference's run, as before).
+A cost scaled by 1 + 1e-4, or a step whose sign is flipped on 0.1 % of the texels with |g| > 20 max|g32 - g64|, passes the gates
+these tests had before (99.5 % of texels within 1e-5; costs within 1e-3) and fails these: checked on the fp32 oracle as a stand-in
+(cost distance 1.0e-4 against bounds of 1e-6 ... 2e-6; 112 texels beyond 1e-5 against 5).
+"""
 import random
 
 import numpy as np
@@ -7,6 +38,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from oracle import f64_anchor as A  # noqa: E402
 from tests.util import assert_close_frac, np_t  # noqa: E402
 
 
@@ -23,26 +55,66 @@ def _setup():
     return ta, attack_ref, synth, obj, mask
 
 
+def _vs_reference_cap(n_ref, n, old_frac):
+    """Texels that may lie beyond tau of the REFERENCE's own fp32 run (the older fixtures): those HIP may have against float64
+    plus those the fp32 run itself has (A.texel_cap(n_ref) + n_ref), and never more than the gate these tests had before the
+    float64 fixtures existed (``old_frac`` of the texels: 0.5 % for the sign-step attacks, 1 % for the Adam one -- figures nobody
+    derived; the fp32 oracle itself is 0.005 % / 0.15 % away from float64, tools/make_goldens_f64.py).  For the L0 tensors the old
+    fraction is the one that binds: 585 texels, against 20 x 163 + 163 = 3423 for ``pos``."""
+    return min(A.texel_cap(n_ref) + int(n_ref), int(old_frac * n))
+
+
+def _grad_audit(au, name, d, f):
+    """rel-L2, the sign condition and the zero set of the per-step gradients ``name``: the first step's are asserted (same
+    start, same poses), later ones printed (the trajectories have parted by then)."""
+    steps = len(d["e_%s_rel" % name])
+    au.per_step("%s rel-L2" % name, d["e_%s_rel" % name], f["e_%s_rel" % name], asserted={0})
+    au.per_step("%s max-abs (printed)" % name, d["e_%s_maxabs" % name], f["e_%s_maxabs" % name], asserted=set())
+    for s in range(steps):
+        print("%s[%d]: sign differs from float64 on %d texels (fp32 oracle: %d)" % (
+            name, s, d["n_%s_sign_differ" % name][s], f["n_%s_sign_differ" % name][s]))
+        # a sign may differ only where |g64| <= 20 max|g32 - g64| of that step
+        au.none("%s[%d] sign offenders" % (name, s), d["n_%s_sign_offend" % name][s], asserted=s == 0)
+    if int(f["zero_only32_" + name][0]) + int(f["zero_only64_" + name][0]) == 0:
+        # both oracle forms are exactly zero on the same texels in the first step (outside the object mask): so is HIP
+        au.none("%s[0] non-zero where 0" % name, d["n_%s_zero_breach" % name][0])
+
+
 def test_phy_obj_atk_matches_reference_golden(golden):
-    """Same seeds as oracle/make_goldens.py: the reference's own 3-step attack result."""
+    """Same seeds as oracle/make_goldens.py: the reference's own 3-step attack result, and the float64 form of it."""
     ta, attack_ref, synth, obj, mask = _setup()
-    g = golden("atk_linf")
+    g, f = golden("atk_linf"), golden("atk_linf_f64")
     Ba, steps, seed = [int(v) for v in g["shape"]]
+    assert [Ba, steps, seed] == [int(v) for v in f["shape"]]
     scenes = synth.kitti_like(Ba, 3, 375, 1242, torch.Generator().manual_seed(31))
     model = synth.TinyDepthNet(seed=5).cuda()
     model.train()
     rm = model.bn.running_mean.clone()
     atk = ta.Phy_obj_atk(model, obj.cuda(), mask.cuda(), eps=0.1, alpha=0.02, steps=steps,
                          dist_range=list(np.arange(5, 10, 0.2)))
+    atk.trace = []
     _seed_all(seed)
     atk.random_start_noise = torch.empty_like(obj).uniform_(-0.1, 0.1)   # the reference's first RNG draw
     adv_s, ben_s, m_out, patch = atk(scenes.cuda(), Ba)
     assert model.training and torch.equal(model.bn.running_mean, rm)      # eval() during the attack, restored after
-    ref = np_t(g["patch_sub"])
-    got = patch[:, :, ::2, ::2].cpu()
+    assert len(atk.trace) == steps
+    # ---- against the float64 trajectory
+    run = dict(costs=[c for c, _ in atk.trace], grads=[gr.cpu() for _, gr in atk.trace], patch=patch.cpu(), adv_s=adv_s.cpu(),
+               ben_s=ben_s.cpu(), m_out=m_out.cpu())
+    d = A.linf_distances(run, f, caps=A.MARGIN * f["e_grad_maxabs"])
+    au = A.Audit("L_inf")
+    au.per_step("cost", d["e_cost"], f["e_cost"], fp32_scalar=True)
+    _grad_audit(au, "grad", d, f)
     # a sign() step on a ~0 gradient may flip: such a texel is off by up to 2*alpha, everything else is exact
-    agree = ((got - ref).abs() <= 1e-5).float().mean().item()
-    assert agree > 0.995, agree
+    au.texels("patch", d["n_patch_beyond"], f["n_patch_beyond"], f["tau"])
+    for k in ("adv_sum", "ben_sum", "mask_out_sum"):
+        au.scalar(k, d["e_" + k], f["e_" + k])
+    # ---- against the reference's own run
+    n_ref = int((patch[:, :, ::2, ::2].cpu() - np_t(g["patch_sub"])).abs().gt(float(f["tau"][0])).sum())
+    cap = _vs_reference_cap(f["n_patch_beyond"][0], int(f["n_sub"]), 0.005)
+    print("L_inf patch vs the reference's fp32 run: %d texels beyond %g (cap %d)" % (n_ref, float(f["tau"][0]), cap))
+    assert n_ref <= cap
+    au.finish()
     assert float((patch.cpu() - obj).abs().max()) <= 0.1 + 1e-6
     assert_close_frac(m_out[:, :, 120:300:9, 300:800:5], np_t(g["mask_rows"]), rtol=1e-4, atol=2e-5, max_bad_frac=1e-3,
                       name="mask rows")
@@ -75,48 +147,103 @@ def test_phy_obj_atk_vs_oracle_broadcast_scene_and_eval():
         atk(torch.zeros(2, 3, 375, 1242).cuda(), 3)
 
 
-def test_phy_obj_atk_l0_matches_reference_golden(golden):
+def _same_weight(mw, mw_ref):
+    """The mask weight is a device fp32 scalar here and a Python float in the oracle: equal as fp32 numbers, exactly."""
+    return np.float32(mw) == np.float32(mw_ref)
+
+
+def _l0_trace_audit(au, trace, t64, e, prefix=""):
+    """Per iteration: l0 within max(3, 20 x the recorded difference), mask_weight exact, adv_cost / mask_cost within 20 e_ref."""
+    d = A.l0_trace_distances(trace, t64)
+    for i, (row, row64) in enumerate(zip(trace, t64)):
+        au.count("l0[%d]" % i, abs(row[0] - row64[0]), e[prefix + "e_l0"])
+        assert _same_weight(row[1], row64[1]), (i, row[1], row64[1])
+    au.per_step("adv_cost", d["e_adv_cost"], e[prefix + "e_adv_cost"], fp32_scalar=True)
+    au.per_step("mask_cost", d["e_mask_cost"], e[prefix + "e_mask_cost"], fp32_scalar=True)
+
+
+def _l0_against_float64(golden, fused):
     ta, attack_ref, synth, obj, mask = _setup()
-    g = golden("atk_l0")
+    g, f = golden("atk_l0"), golden("atk_l0_f64")
     Ba, steps, seed = [int(v) for v in g["shape"]]
+    assert [Ba, steps, seed] == [int(v) for v in f["shape"]]
     scenes = synth.kitti_like(Ba, 3, 375, 1242, torch.Generator().manual_seed(31))
     model = synth.TinyDepthNet(seed=5).cuda()
     atk = ta.Phy_obj_atk_l0(model, obj.cuda(), mask.cuda(), adam_lr=0.5, steps=steps, mask_wt=0.06, l0_thresh=0.1,
                             dist_range=list(np.arange(5, 10, 0.2)))
     atk.trace = []
+    if fused:
+        atk.fused = True            # K23: refuses grad_trace -- the trace and the trajectory only
+    else:
+        atk.grad_trace = []
     _seed_all(seed)
     adv_s, ben_s, m_out, patch = atk(scenes.cuda(), Ba)
     assert len(atk.trace) >= steps
-    assert abs(atk.mask_weight - float(g["final_mask_weight"])) < 1e-7   # fp32 device scalar vs python float
-    assert abs(int(atk.cal_l0()) - int(g["l0_final"])) <= 5      # texels sitting on the 1/255 threshold
+    assert _same_weight(atk.mask_weight, float(g["final_mask_weight"]))
+    pos, neg = atk.pattern_pos_tensor.detach().cpu(), atk.pattern_neg_tensor.detach().cpu()
+    l0_final = int(atk.cal_l0())
+    # ---- against the float64 trajectory
+    run = dict(trace=atk.trace, pos=pos, neg=neg, patch=patch.cpu(), adv_s=adv_s.cpu(), ben_s=ben_s.cpu(), m_out=m_out.cpu(),
+               l0_final=l0_final, gpos=None if fused else [p.cpu() for p, _ in atk.grad_trace],
+               gneg=None if fused else [n.cpu() for _, n in atk.grad_trace])
+    caps = {k: A.MARGIN * f["e_%s_maxabs" % k] for k in ("gpos", "gneg")}
+    d = A.l0_distances(run, f, caps=caps)
+    au = A.Audit("L0 fused" if fused else "L0")
+    _l0_trace_audit(au, atk.trace, f["trace64"], f)
+    if not fused:
+        _grad_audit(au, "gpos", d, f)
+        _grad_audit(au, "gneg", d, f)
     # Adam(lr=0.5) on sign-like gradients: trajectories agree except where a ~0 gradient flips sign early on
-    for name, t in (("pattern_pos_sub", atk.pattern_pos_tensor), ("pattern_neg_sub", atk.pattern_neg_tensor)):
-        ref = np_t(g[name])
-        agree = ((t[:, :, ::2, ::2].detach().cpu() - ref).abs() <= 2e-3).float().mean().item()
-        assert agree > 0.99, (name, agree)
-    ref = np_t(g["patch_sub"])
-    assert ((patch[:, :, ::2, ::2].cpu() - ref).abs() <= 2e-3).float().mean().item() > 0.99
+    for name in ("pos", "neg", "patch"):
+        au.texels(name, d["n_%s_beyond" % name], f["n_%s_beyond" % name], f["tau"])
+    au.count("l0 of the final patch", d["e_l0_final"], f["e_l0_final"])     # texels sitting on the 1/255 threshold
+    for k in ("adv_sum", "ben_sum", "mask_out_sum"):
+        au.scalar(k, d["e_" + k], f["e_" + k])
+    # ---- against the reference's own run: what HIP may be from float64 plus what that run is, and never more than before
+    tau = float(f["tau"][0])
+    for name, t, key in (("pattern_pos_sub", pos, "n_pos_beyond"), ("pattern_neg_sub", neg, "n_neg_beyond"),
+                         ("patch_sub", patch.cpu(), "n_patch_beyond")):
+        n_ref = int((t[:, :, ::2, ::2] - np_t(g[name])).abs().gt(tau).sum())
+        cap = _vs_reference_cap(f[key][0], int(f["n_sub"]), 0.01)
+        print("L0 %s vs the reference's fp32 run: %d texels beyond %g (cap %d)" % (name, n_ref, tau, cap))
+        assert n_ref <= cap, (name, n_ref, cap)
+    # the count of the final patch: as above, and never more than the 5 pixels this test allowed before
+    cap = min(A.l0_cap(f["e_l0_final"]) + float(f["e_l0_final"]), 5)
+    print("L0 l0 of the final patch vs the reference's fp32 run: %d (cap %d)" % (abs(l0_final - int(g["l0_final"])), cap))
+    assert abs(l0_final - int(g["l0_final"])) <= cap
+    au.finish()
     torch.testing.assert_close(m_out.double().sum((1, 2, 3)).cpu(), np_t(g["mask_out_sum"]), rtol=1e-5, atol=0)
     torch.testing.assert_close(ben_s.double().sum((2, 3)).cpu(), np_t(g["ben_sum"]), rtol=1e-5, atol=0)
-    torch.testing.assert_close(adv_s.double().sum((2, 3)).cpu(), np_t(g["adv_sum"]), rtol=1e-3, atol=0)
+    e_sum = float(A.rel_scalar(adv_s.double().sum((2, 3)).cpu().numpy(), g["adv_sum"]).max())
+    print("L0 adv_sum vs the reference's fp32 run: %.3g (bound %.3g)" % (e_sum, A.bound(f["e_adv_sum"]) + float(f["e_adv_sum"])))
+    assert e_sum <= A.bound(f["e_adv_sum"]) + float(f["e_adv_sum"])
 
 
-def test_l0_attack_trace_vs_oracle():
+def test_phy_obj_atk_l0_matches_reference_golden(golden):
+    """The default (unfused) path: trace, the pattern gradients Adam is handed, trajectory."""
+    _l0_against_float64(golden, fused=False)
+
+
+def test_phy_obj_atk_l0_fused_matches_float64(golden):
+    """The same attack with K23 as the update (fused=True): trace and trajectory."""
+    _l0_against_float64(golden, fused=True)
+
+
+def test_l0_attack_trace_vs_oracle(golden):
+    """Another pair of scenes and seeds, 2 steps: the per-iteration record against the float64 oracle's (recorded: keys t_*)."""
     ta, attack_ref, synth, obj, mask = _setup()
-    scenes = synth.kitti_like(2, 3, 375, 1242, torch.Generator().manual_seed(8))
-    rec = []
-    _seed_all(21)
-    attack_ref.phy_obj_atk_l0(synth.TinyDepthNet(seed=5), obj, mask, scenes, 2, adam_lr=0.5, steps=2, mask_wt=0.06,
-                              l0_thresh=0.1, dist_range=attack_ref.TRAIN_DIST_RANGE, record=rec)
-    atk = ta.Phy_obj_atk_l0(synth.TinyDepthNet(seed=5).cuda(), obj.cuda(), mask.cuda(), adam_lr=0.5, steps=2,
+    f = golden("atk_l0_f64")
+    Ba, steps, seed, scene_seed = [int(v) for v in f["t_shape"]]
+    scenes = synth.kitti_like(Ba, 3, 375, 1242, torch.Generator().manual_seed(scene_seed))
+    atk = ta.Phy_obj_atk_l0(synth.TinyDepthNet(seed=5).cuda(), obj.cuda(), mask.cuda(), adam_lr=0.5, steps=steps,
                             mask_wt=0.06, l0_thresh=0.1, dist_range=list(np.arange(5, 10, 0.2)))
     atk.trace = []
-    _seed_all(21)
-    atk(scenes.cuda(), 2)
-    assert len(atk.trace) == len(rec)
-    for (l0, mw, ac, mc), (l0r, mwr, acr, mcr) in zip(atk.trace, rec):
-        assert abs(l0 - l0r) <= max(3, 1e-3 * l0r) and abs(mw - mwr) < 1e-7
-        assert abs(ac - acr) <= 1e-3 * abs(acr) + 1e-7 and abs(mc - mcr) <= 1e-4 * abs(mcr)
+    _seed_all(seed)
+    atk(scenes.cuda(), Ba)
+    assert len(atk.trace) == len(f["t_trace64"]) == len(f["t_trace32"])
+    au = A.Audit("L0 trace")
+    _l0_trace_audit(au, atk.trace, f["t_trace64"], f, prefix="t_")
+    au.finish()
 
 
 def test_l0_attack_with_color_jit_vs_oracle():
@@ -160,9 +287,24 @@ def test_pgd_depth_matches_reference_golden(golden, targeted):
     _seed_all(seed)
     atk.random_start_noise = torch.empty_like(imgs).uniform_(-0.03, 0.03)
     adv, clean = atk(imgs.cuda())
-    ref = np_t(g["adv_rows"])
-    agree = ((adv[:, :, ::16, ::8].cpu() - ref).abs() <= 1e-6).float().mean().item()
-    assert agree > 0.995, agree
+    # the class exposes no per-step record: the final frames only, against the float64 form
+    f = golden("atk_pgd_f64")
+    tag = "targeted_" if targeted else "untargeted_"
+    assert [B, steps, seed] == [int(v) for v in f["shape"]]
+    d = A.pgd_distances(dict(adv=adv.cpu(), clean=clean.cpu()), f, tag)
+    au = A.Audit("PGD " + tag[:-1])
+    au.texels("adv rows", d["n_adv_beyond"], f[tag + "n_adv_beyond"], f["tau"])
+    au.scalar("adv_sum", d["e_adv_sum"], f[tag + "e_adv_sum"])
+    # printed only: an absolute difference of fp32 frames with values up to 1, whose spacing there (2^-24) is above
+    # 20 x e_ref = 2.4e-8 -- the fp32 oracle's 1.2e-9 is fp32(eps) - eps, not an accuracy.  The 1e-6 against the reference's
+    # run below stays.
+    au.scalar("delta_absmax", d["e_delta_absmax"], f[tag + "e_delta_absmax"], asserted=False)
+    # and against the reference's own run
+    n_ref = int((adv[:, :, ::16, ::8].cpu() - np_t(g["adv_rows"])).abs().gt(float(f["tau"][0])).sum())
+    cap = _vs_reference_cap(f[tag + "n_adv_beyond"][0], int(f[tag + "n_rows"]), 0.005)
+    print("PGD rows vs the reference's fp32 run: %d beyond %g (cap %d)" % (n_ref, float(f["tau"][0]), cap))
+    assert n_ref <= cap
+    au.finish()
     assert abs(float((adv - clean).abs().max()) - float(g["delta_absmax"])) < 1e-6
 
 
