@@ -176,6 +176,8 @@ _SIGNATURES = {
     "dmh_down_conv_weight_image": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "dmh_down_conv_fwd_img": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp] + [C.c_int] * 6 + [_fp] * 3),
     "dmh_down_conv_bwd_data_img": (C.c_int, [_fp] * 4 + [C.c_int] * 5 + [_fp, _fp]),
+    "dmh_pose_head_fwd": (C.c_int, [_fp] + [C.c_int] * 4 + [C.c_float, C.c_uint32] + [_fp] * 4),
+    "dmh_pose_head_bwd": (C.c_int, [_fp] * 5 + [C.c_int] * 4 + [C.c_float, C.c_uint32, _fp, _fp]),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -15,6 +15,15 @@ trips per sample inside DataLoader workers; camera side ("l"/"r") and do_flip ar
 num_workers=0); ``reference_stale_patch`` reproduces what its forked workers do (patch as of the epoch start,
 SURVEY 3.1).  Not reproduced: the PIL 8-bit round trip and LANCZOS pyramids of ``preprocess`` (the paste resizes
 bilinearly in the same pass; scales > 0 are 2^s box means) and ColorJitter.
+
+Monocular frames: integer ``frame_idxs`` other than 0 (Monodepth2's -1 / +1) get a temporally adjacent view each, built like
+the right view -- the pool rolled by a few pixels, to the right for positive and to the left for negative ids, plus 10 %
+independent texture -- for both camera sides, so that the neighbours of a right-camera frame 0 come from the right pool's
+neighbours; flips apply to all frames of a sample.  ``("color", f, 0)`` and ``("color_aug", f, 0)`` are the same tensor (no
+ColorJitter), and ``("color_aug", "s", 0)`` is then written too (the shared-encoder pose path reads it, MD2/trainer.py:344).
+These pools exist only when such ids are requested and are drawn after every other draw of the constructor: with ``frame_idxs``
+``[0, "s"]`` every tensor stays what it was.  Under adversarial training the neighbour frames carry NO pasted object: the
+reference pastes into frame 0 and "s" only (mono_dataset.py:186-261) and leaves -1 / +1 as loaded.
 """
 import random
 
@@ -59,6 +68,14 @@ class SyntheticKITTIDataset(object):
         # (K3's scene_index) -- no index_select / side-pick copies of 32 full-resolution frames per batch
         self.raw = torch.cat([raw_left, raw_right], 0).contiguous()
         self.raw_left, self.raw_right = self.raw[:self.pool_size], self.raw[self.pool_size:]
+        # temporal neighbours (monocular frame ids): {f: [2 P, 3, 375, 1242]}, laid out like self.raw; drawn last
+        self.neighbour_ids = [f for f in frame_idxs if isinstance(f, int) and not isinstance(f, bool) and f != 0]
+        self.raw_neighbours = {}
+        for f in self.neighbour_ids:
+            step = max(1, int(round(4 * ori_W / 1024.0))) * f
+            texture = kitti_like(self.pool_size, 3, ori_H, ori_W, self.device, self.gen)
+            self.raw_neighbours[f] = torch.cat([0.9 * torch.roll(raw_left, step, 3) + 0.1 * texture,
+                                                0.9 * torch.roll(raw_right, step, 3) + 0.1 * texture], 0).contiguous()
         self.is_adv_train = False
         self.load_ben_color = False
         self.half_no_synthesis = False
@@ -213,12 +230,25 @@ class SyntheticKITTIDataset(object):
                 fl = to_device_async(geo["flip"], dev, torch.bool).view(batch_size, 1, 1, 1)
                 left, right = torch.where(fl, left.flip(3), left), torch.where(fl, right.flip(3), right)
             inputs[("color_aug", 0, 0)] = left
+        views = [(0, left), ("s", right)]
+        if self.neighbour_ids:
+            # the neighbours of frame 0 on its own camera side, object-free, resized and flipped like the other frames
+            P = self.pool_size
+            nidx = to_device_async([p + (0 if sd == "l" else P) for p, sd in zip(picks, geo["side"])], dev, torch.int64)
+            nflip = to_device_async(geo["flip"], dev, torch.bool).view(batch_size, 1, 1, 1) if any(geo["flip"]) else None
+            for f in self.neighbour_ids:
+                img = F.interpolate(self.raw_neighbours[f].index_select(0, nidx), [H, W], mode="bilinear", align_corners=False)
+                if nflip is not None:
+                    img = torch.where(nflip, img.flip(3), img)
+                inputs[("color_aug", f, 0)] = img
+                views.append((f, img))
+            inputs[("color_aug", "s", 0)] = right
         fused = left.is_cuda and self.num_scales == 4 and H % 8 == 0 and W % 8 == 0
-        for view, img in ((0, left), ("s", right)):
+        for view, img in views:
             # the three coarser levels in one pass (ops.avg_pyramid: bit-identical to F.avg_pool2d); the opposite view's levels
             # are read by --v1_multiscale only, so they are built when somebody asks for them
             inputs[("color", view, 0)] = img
-            if view == "s" and not self.right_pyramid:
+            if view != 0 and not self.right_pyramid:
                 continue
             levels = ops.avg_pyramid(img) if fused else [F.avg_pool2d(img, 2 ** s) for s in range(1, self.num_scales)]
             for s in range(1, self.num_scales):

@@ -2,7 +2,8 @@
 
 The training hot path does NOT go through these modules -- Trainer.compute_losses calls the fused HIP
 kernel (ops.photometric_smooth_loss).  They exist so that code written against the reference's
-``layers`` module keeps working (evaluation scripts, notebooks): disp_to_depth :16-25, ConvBlock :106-118,
+``layers`` module keeps working (evaluation scripts, notebooks): disp_to_depth :16-25, transformation_from_parameters :28-45,
+get_translation_matrix :48-61, rot_from_axisangle :64-103 (K29 on CUDA fp32 tensors, the reference's expressions elsewhere), ConvBlock :106-118,
 Conv3x3 :121-136, BackprojectDepth :139-168, Project3D :171-198, upsample :201-204,
 get_smooth_loss :207-220, SSIM :223-253.  Buffers are ``nn.Parameter(requires_grad=False)`` exactly as
 in the reference so that state_dicts keep the same keys.
@@ -19,6 +20,75 @@ def disp_to_depth(disp, min_depth, max_depth):
     max_disp = 1 / min_depth
     scaled_disp = min_disp + (max_disp - min_disp) * disp
     return scaled_disp, 1 / scaled_disp
+
+
+def _pose_head_ok(*tensors):
+    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[1:]) == (1, 3) and 0 < t.shape[0] <= 65535
+               for t in tensors)
+
+
+def _pose_head_T(axisangle, translation, invert):
+    """K29 with h = w = 1 and scale 1: the six numbers per sample are their own means."""
+    from . import ops
+    x = torch.cat([axisangle, translation], 2).reshape(-1, 6, 1, 1)
+    return ops.pose_head(x, invert, scale=1.0)[2][:, 0]
+
+
+def transformation_from_parameters(axisangle, translation, invert=False):
+    """The network's (axisangle, translation) output [B,1,3] -> 4x4 matrices [B,4,4] (MD2/layers.py:28-45): Trans(t) Rot(a), or
+    Rot(a)^T Trans(-t) with ``invert``.  One K29 launch on CUDA fp32 tensors."""
+    if _pose_head_ok(axisangle, translation):
+        return _pose_head_T(axisangle, translation, invert)
+    R = rot_from_axisangle(axisangle)
+    t = translation.clone()
+    if invert:
+        R = R.transpose(1, 2)
+        t *= -1
+    T = get_translation_matrix(t)
+    return torch.matmul(R, T) if invert else torch.matmul(T, R)
+
+
+def get_translation_matrix(translation_vector):
+    """Translation vector -> 4x4 matrix (MD2/layers.py:48-61)."""
+    if _pose_head_ok(translation_vector):
+        return _pose_head_T(torch.zeros_like(translation_vector), translation_vector, False)
+    T = torch.zeros(translation_vector.shape[0], 4, 4, dtype=translation_vector.dtype).to(device=translation_vector.device)
+    t = translation_vector.contiguous().view(-1, 3, 1)
+    T[:, 0, 0] = 1
+    T[:, 1, 1] = 1
+    T[:, 2, 2] = 1
+    T[:, 3, 3] = 1
+    T[:, :3, 3, None] = t
+    return T
+
+
+def rot_from_axisangle(vec):
+    """Axis-angle [B,1,3] -> 4x4 rotation matrix (MD2/layers.py:64-103)."""
+    if _pose_head_ok(vec):
+        return _pose_head_T(vec, torch.zeros_like(vec), False)
+    angle = torch.norm(vec, 2, 2, True)
+    axis = vec / (angle + 1e-7)
+    ca = torch.cos(angle)
+    sa = torch.sin(angle)
+    C = 1 - ca
+    x = axis[..., 0].unsqueeze(1)
+    y = axis[..., 1].unsqueeze(1)
+    z = axis[..., 2].unsqueeze(1)
+    xs, ys, zs = x * sa, y * sa, z * sa
+    xC, yC, zC = x * C, y * C, z * C
+    xyC, yzC, zxC = x * yC, y * zC, z * xC
+    rot = torch.zeros((vec.shape[0], 4, 4), dtype=vec.dtype).to(device=vec.device)
+    rot[:, 0, 0] = torch.squeeze(x * xC + ca)
+    rot[:, 0, 1] = torch.squeeze(xyC - zs)
+    rot[:, 0, 2] = torch.squeeze(zxC + ys)
+    rot[:, 1, 0] = torch.squeeze(xyC + zs)
+    rot[:, 1, 1] = torch.squeeze(y * yC + ca)
+    rot[:, 1, 2] = torch.squeeze(yzC - xs)
+    rot[:, 2, 0] = torch.squeeze(zxC - ys)
+    rot[:, 2, 1] = torch.squeeze(yzC + xs)
+    rot[:, 2, 2] = torch.squeeze(z * zC + ca)
+    rot[:, 3, 3] = 1
+    return rot
 
 
 class Conv3x3(nn.Module):

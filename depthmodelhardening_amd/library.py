@@ -29,6 +29,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
                                                                                        + dmh::photo_smooth_loss_bwd
     dmh::ssim_map             MD2/layers.py:223-253 SSIM.forward                (K1's window sums, stand-alone)
     dmh::smooth_loss          MD2/layers.py:207-220 get_smooth_loss             (K2 on one scale)
+    dmh::pose_head            MD2/networks/pose_decoder.py:47-52 + MD2/layers.py:28-103   (K29) + dmh::pose_head_bwd
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -622,7 +623,46 @@ def _smooth_backward(ctx, g):
 smooth_loss.register_autograd(_smooth_backward, setup_context=_smooth_setup)
 
 
+# ----------------------------------------------------------------------------------------------------------------- K29
+@custom_op("dmh::pose_head", mutates_args=())
+def pose_head(x: torch.Tensor, invert_mask: int, scale: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.pose_head_fwd_launch(_cu(x), invert_mask, scale)
+
+
+@pose_head.register_fake
+def _(x, invert_mask, scale):
+    B, nf = x.shape[0], x.shape[1] // 6
+    return x.new_empty((B, nf, 1, 3)), x.new_empty((B, nf, 1, 3)), x.new_empty((B, nf, 4, 4))
+
+
+@custom_op("dmh::pose_head_bwd", mutates_args=())
+def pose_head_bwd(g_T: Optional[torch.Tensor], g_axisangle: Optional[torch.Tensor], g_translation: Optional[torch.Tensor],
+                  axisangle: torch.Tensor, translation: torch.Tensor, shape: List[int], invert_mask: int,
+                  scale: float) -> torch.Tensor:
+    return ops.pose_head_bwd_launch(g_T, g_axisangle, g_translation, _cu(axisangle), _cu(translation), shape, invert_mask, scale)
+
+
+@pose_head_bwd.register_fake
+def _(g_T, g_axisangle, g_translation, axisangle, translation, shape, invert_mask, scale):
+    return axisangle.new_empty(shape)
+
+
+def _pose_setup(ctx, inputs, output):
+    x, invert_mask, scale = inputs
+    ctx.save_for_backward(output[0], output[1])
+    ctx.cfg = (list(x.shape), invert_mask, scale)
+
+
+def _pose_backward(ctx, g_aa, g_tr, g_T):
+    aa, tr = ctx.saved_tensors
+    shape, invert_mask, scale = ctx.cfg
+    return torch.ops.dmh.pose_head_bwd(g_T, g_aa, g_tr, aa, tr, shape, invert_mask, scale), None, None
+
+
+pose_head.register_autograd(_pose_backward, setup_context=_pose_setup)
+
+
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
-       "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors")
+       "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd")

@@ -1,4 +1,5 @@
 from .depth_decoder import DepthDecoder
+from .pose_decoder import PoseDecoder
 from .resnet_encoder import ResnetEncoder
 
-__all__ = ["ResnetEncoder", "DepthDecoder"]
+__all__ = ["ResnetEncoder", "DepthDecoder", "PoseDecoder"]

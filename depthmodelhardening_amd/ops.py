@@ -1433,6 +1433,22 @@ _wino_ready = {}        # (weight pointer, backward) -> (weight version, U, weig
                         # entry keeps its weight tensor alive, so the pointer cannot come to name another tensor's data
 
 
+_wino_pass = None       # inside wino_pass(): [has this pass emptied the table yet]
+
+
+@contextlib.contextmanager
+def wino_pass():
+    """One train pass with several encoders (the depth and the pose encoder): inside, only the FIRST ``fresh`` prefetch empties
+    the table of ready filters, so that the second encoder's prefetch leaves the first one's backward-data forms where the
+    backward will look for them.  Outside such a scope every ``fresh`` prefetch empties it, as one encoder per pass wants."""
+    global _wino_pass
+    prev, _wino_pass = _wino_pass, [False]
+    try:
+        yield
+    finally:
+        _wino_pass = prev
+
+
 def wino_prefetch(jobs, fresh=False):
     """Transform many K10 filters in ONE launch (dmh_wino_weight_transform_batch) ahead of their use: ``jobs`` = iterable of
     (weight [K, C, 3, 3], backward, scale or None) -- what _wino_filter() will be asked for.  A step needs every filter in its
@@ -1446,7 +1462,10 @@ def wino_prefetch(jobs, fresh=False):
     lib = N.lib()
     todo, keep = [], []
     if fresh and not _wino_frozen:
-        _wino_ready.clear()
+        if _wino_pass is None or not _wino_pass[0]:
+            _wino_ready.clear()
+        if _wino_pass is not None:
+            _wino_pass[0] = True
     for weight, backward, scale in jobs:
         if not (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
             continue
@@ -3026,3 +3045,72 @@ def eigen_depth_errors(pred_disp, pack, first, *, pred_disp_flip=None, scale_fac
         pred_disp, pred_disp_flip, pack.gt, pack.table, pack.blk_img, pack.medians, first, b0, int(pack.blk_first[first + n]) - b0,
         px0, int(pack.offsets[first + n]) - px0, pack.eigen, scale_factor, median_scaling)
     return (errors, ratios, depth, med) if return_pred else (errors, ratios)
+
+
+# ----------------------------------------------------------------------------------------------------------------- K29
+POSE_SCALE = 0.01       # MD2/networks/pose_decoder.py:49
+
+
+def pose_invert_mask(invert, nf):
+    """Bit f set = frame f of the head is inverted (Rot^T Trans(-t): a negative frame id, MD2/trainer.py:408-410).  ``invert``: a
+    bool for all frames or one bool per frame -- host values, they travel to the kernel as an argument."""
+    if torch.is_tensor(invert):
+        raise RuntimeError("pose_head: invert is a bool or a sequence of bools (a kernel argument), not a tensor")
+    flags = [bool(invert)] * nf if isinstance(invert, (bool, int, np.bool_)) else [bool(v) for v in invert]
+    if len(flags) != nf:
+        raise RuntimeError("pose_head: %d invert flags for %d frames" % (len(flags), nf))
+    return sum(1 << f for f, v in enumerate(flags) if v)
+
+
+def _pose_head_shape(x):
+    if x.dim() != 4 or x.shape[1] % 6 or x.shape[1] == 0:
+        raise RuntimeError("pose_head: x must be [B, 6 * nf, h, w]; got %s" % (tuple(x.shape),))
+    B, c6, h, w = x.shape
+    return B, c6 // 6, h, w
+
+
+def pose_head_fwd_launch(x, mask, scale):
+    B, nf, h, w = _pose_head_shape(x)
+    aa = torch.empty((B, nf, 1, 3), device=x.device, dtype=torch.float32)
+    tr = torch.empty((B, nf, 1, 3), device=x.device, dtype=torch.float32)
+    T = torch.empty((B, nf, 4, 4), device=x.device, dtype=torch.float32)
+    N.check(_timed("pose_head_fwd", lambda: N.lib().dmh_pose_head_fwd(N.ptr(x), B, nf, h, w, scale, mask, N.ptr(aa), N.ptr(tr),
+                                                                      N.ptr(T), N.stream())))
+    return aa, tr, T
+
+
+def pose_head_bwd_launch(g_T, g_aa, g_tr, aa, tr, shape, mask, scale):
+    B, c6, h, w = shape
+    g_x = torch.empty(tuple(shape), device=aa.device, dtype=torch.float32)
+    gs = [None if g is None else _c(g.to(torch.float32)) for g in (g_T, g_aa, g_tr)]
+    N.check(_timed("pose_head_bwd", lambda: N.lib().dmh_pose_head_bwd(N.ptr(gs[0]), N.ptr(gs[1]), N.ptr(gs[2]), N.ptr(aa),
+                                                                      N.ptr(tr), B, c6 // 6, h, w, scale, mask, N.ptr(g_x),
+                                                                      N.stream())))
+    return g_x
+
+
+class _PoseHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, scale):
+        aa, tr, T = pose_head_fwd_launch(x, mask, scale)
+        ctx.save_for_backward(aa, tr)
+        ctx.cfg = (tuple(x.shape), mask, scale)
+        return aa, tr, T
+
+    @staticmethod
+    def backward(ctx, g_aa, g_tr, g_T):
+        aa, tr = ctx.saved_tensors
+        shape, mask, scale = ctx.cfg
+        if g_aa is None and g_tr is None and g_T is None:
+            return None, None, None
+        return pose_head_bwd_launch(g_T, g_aa, g_tr, aa, tr, shape, mask, scale), None, None
+
+
+def pose_head(x, invert=False, scale=POSE_SCALE):
+    """K29: the pose decoder's tail and transformation_from_parameters in one launch (MD2/networks/pose_decoder.py:47-52,
+    MD2/layers.py:28-103).  x [B, 6 nf, h, w] -> (axisangle [B, nf, 1, 3], translation [B, nf, 1, 3], T [B, nf, 4, 4]);
+    ``invert``: a bool, or one per frame.  Differentiable w.r.t. x through all three results (one launch)."""
+    if not x.is_cuda:
+        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % x.device)
+    _, nf, _, _ = _pose_head_shape(x)
+    return _PoseHead.apply(_c(x), pose_invert_mask(invert, nf), float(scale))

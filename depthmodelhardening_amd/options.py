@@ -111,6 +111,10 @@ class MonodepthOptions:
                             "do (SURVEY.md section 3.1); default: the freshly attacked patch (its num_workers=0 behaviour)")
         p.add_argument("--no_flip_sides", action="store_true",
                        help="synthetic data: always camera side 'l' and no horizontal flips")
+        p.add_argument("--pose_net", action="store_true",
+                       help="build the pose networks (MD2/trainer.py:97-121) and serve the monocular frame ids of --frame_ids "
+                            "(the default 0 -1 1): --pose_model_type separate_resnet / shared, --pose_model_input pairs / all; "
+                            "the pose head is one HIP launch (K29).  Without it the trainer refuses monocular frame ids")
         p.add_argument("--max_steps", type=int, default=0, help="stop after this many iterations (0 = full epochs)")
         p.add_argument("--graph_attack", action="store_true",
                        help="L_inf attack: one set of window sizes for all steps, step 1 captured in a HIP graph and replayed "

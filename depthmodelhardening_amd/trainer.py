@@ -182,10 +182,20 @@ class Trainer:
         self.use_pose_net = not (self.opt.use_stereo and self.opt.frame_ids == [0])
         if self.opt.use_stereo:
             self.opt.frame_ids.append("s")
-        if self.use_pose_net:
+        self.num_pose_frames = 2 if self.opt.pose_model_input == "pairs" else self.num_input_frames     # MD2/trainer.py:61
+        if self.use_pose_net and not getattr(self.opt, "pose_net", False):
             raise NotImplementedError("pose networks (monocular frames -1/+1) are outside the hot-path scope; "
                                       "train with --frame_ids 0 --use_stereo as the paper's command does "
-                                      "(reference README.md:87-91)")
+                                      "(reference README.md:87-91), or pass --pose_net to build them")
+        if self.use_pose_net and self.opt.pose_model_type == "posecnn":
+            # PoseCNN's translation is scaled by the mean inverse depth of every scale (MD2/trainer.py:497-506): one T per
+            # (frame, scale), where the fused loss takes one T per frame
+            raise NotImplementedError("--pose_model_type posecnn is not served: its per-scale cam_T_cam does not fit the fused "
+                                      "loss's one transform per frame; use separate_resnet or shared")
+        if self.use_pose_net and self.opt.adv_train and not self.opt.use_stereo:
+            # the reference's prep_adv_data reads ("color", "s", -1) and dies with a KeyError (mono_dataset.py:186-261)
+            raise RuntimeError("--adv_train needs --use_stereo: the benign object is pasted into the opposite stereo view "
+                               "(the reference fails with a KeyError on ('color', 's', -1))")
         if self.opt.gt_depth and self.opt.adv_train and self.opt.supervised_adv and self.opt.half_no_synthesis:
             # the reference fails later, with a KeyError on inputs[("color_objmask",0,0)]: --half_no_synthesis samples carry
             # neither the object mask nor its distance (mono_dataset.py:248-250)
@@ -223,6 +233,19 @@ class Trainer:
             self.models["predictive_mask"].to(self.device)
             self.parameters_to_train += list(self.models["predictive_mask"].parameters())
 
+        if self.use_pose_net:       # MD2/trainer.py:97-121
+            if self.opt.pose_model_type == "separate_resnet":
+                self.models["pose_encoder"] = networks.ResnetEncoder(self.opt.num_layers, self.opt.weights_init == "pretrained",
+                                                                     num_input_images=self.num_pose_frames)
+                self.models["pose_encoder"].to(self.device)
+                self.parameters_to_train += list(self.models["pose_encoder"].parameters())
+                self.models["pose"] = networks.PoseDecoder(self.models["pose_encoder"].num_ch_enc, num_input_features=1,
+                                                           num_frames_to_predict_for=2)
+            else:       # "shared": the depth encoder's features of every frame
+                self.models["pose"] = networks.PoseDecoder(self.models["encoder"].num_ch_enc, self.num_pose_frames)
+            self.models["pose"].to(self.device)
+            self.parameters_to_train += list(self.models["pose"].parameters())
+
         if self.opt.adv_train and self.opt.supervised_adv:
             self.gt_model = import_depth_model((1024, 320)).to(self.device)   # frozen teacher, trainer.py:93-95
             for p in self.gt_model.parameters():
@@ -240,6 +263,8 @@ class Trainer:
         # the encoder's ImageNet ``fc`` is in parameters_to_train (trainer.py:85) but never gets a gradient:
         # it is left out of the all-reduce bucket
         fc_ids = {id(p) for p in self.models["encoder"].encoder.fc.parameters()}
+        if "pose_encoder" in self.models:
+            fc_ids |= {id(p) for p in self.models["pose_encoder"].encoder.fc.parameters()}
         self.bucket = GradBucket([p for p in self.parameters_to_train if id(p) not in fc_ids], self.world_size)
 
         if self.opt.load_weights_folder is not None and not self.opt.fine_tune:
@@ -415,16 +440,72 @@ class Trainer:
         """Pass a minibatch through the network and generate images and losses (MD2/trainer.py:335-375)."""
         for key, ipt in inputs.items():
             inputs[key] = ipt.to(self.device)
-        features = self.models["encoder"](inputs["color_aug", 0, 0])
-        outputs = LazyOutputs(self.models["depth"](features))
-        outputs["middle_features_aug"] = features
+        if "pose_encoder" in self.models:
+            # two encoders in one pass: the second one's filter prefetch must not drop the first one's backward-data forms
+            with ops.wino_pass():
+                return self._process_batch(inputs)
+        return self._process_batch(inputs)
+
+    def _process_batch(self, inputs):
+        if self.use_pose_net and self.opt.pose_model_type == "shared":
+            # a shared encoder for depth and pose: every frame goes through the depth encoder, as one batch (MD2/trainer.py:341-353)
+            all_features = self.models["encoder"](torch.cat([inputs[("color_aug", i, 0)] for i in self.opt.frame_ids]))
+            all_features = [torch.split(f, self.opt.batch_size) for f in all_features]
+            features = {k: [f[i] for f in all_features] for i, k in enumerate(self.opt.frame_ids)}
+            depth_features = features[0]
+        else:
+            features = depth_features = self.models["encoder"](inputs["color_aug", 0, 0])
+        outputs = LazyOutputs(self.models["depth"](depth_features))
+        outputs["middle_features_aug"] = depth_features
         if self.opt.contrastive_learning:
             outputs["middle_features_ben"] = self.models["encoder"](inputs["color_ben", 0, 0])
         if self.opt.predictive_mask:
-            outputs["predictive_mask"] = self.models["predictive_mask"](features)       # MD2/trainer.py:362-363
+            outputs["predictive_mask"] = self.models["predictive_mask"](depth_features)       # MD2/trainer.py:362-363
+        if self.use_pose_net:
+            outputs.update(self.predict_poses(inputs, features))
         self.generate_images_pred(inputs, outputs)
         losses = self.compute_losses(inputs, outputs)
         return outputs, losses
+
+    def predict_poses(self, inputs, features):
+        """Predict poses between input frames for monocular sequences (MD2/trainer.py:377-433).  The pose decoder's tail and
+        transformation_from_parameters are one K29 launch inside ``models["pose"]``, which keeps the matrices it computed
+        (``PoseDecoder.T``): cam_T_cam is read from there.  In ``pairs`` mode every source frame is a pass of its own through the
+        pose networks, in train and eval mode alike, as in the reference -- one batch of 2B would change the train-mode BatchNorm
+        statistics (DESIGN.md)."""
+        outputs = {}
+        pose = self.models["pose"]
+        shared = self.opt.pose_model_type == "shared"
+        if self.num_pose_frames == 2:
+            if shared:
+                pose_feats = {f_i: features[f_i] for f_i in self.opt.frame_ids}
+            else:
+                pose_feats = {f_i: inputs["color_aug", f_i, 0] for f_i in self.opt.frame_ids if f_i != "s"}
+            for f_i in self.opt.frame_ids[1:]:
+                if f_i == "s":
+                    continue
+                # frames are passed in temporal order; the matrix is inverted when the frame id is negative
+                pose_inputs = [pose_feats[f_i], pose_feats[0]] if f_i < 0 else [pose_feats[0], pose_feats[f_i]]
+                if not shared:
+                    pose_inputs = [self.models["pose_encoder"](torch.cat(pose_inputs, 1))]
+                axisangle, translation = pose(pose_inputs, invert=f_i < 0)
+                outputs[("axisangle", 0, f_i)] = axisangle
+                outputs[("translation", 0, f_i)] = translation
+                outputs[("cam_T_cam", 0, f_i)] = pose.T[:, 0]
+        else:
+            # all frames go to the pose net (and all poses are predicted) together
+            if shared:
+                pose_inputs = [features[i] for i in self.opt.frame_ids if i != "s"]
+            else:
+                pose_inputs = [self.models["pose_encoder"](
+                    torch.cat([inputs[("color_aug", i, 0)] for i in self.opt.frame_ids if i != "s"], 1))]
+            axisangle, translation = pose(pose_inputs)
+            for i, f_i in enumerate(self.opt.frame_ids[1:]):
+                if f_i != "s":
+                    outputs[("axisangle", 0, f_i)] = axisangle
+                    outputs[("translation", 0, f_i)] = translation
+                    outputs[("cam_T_cam", 0, f_i)] = pose.T[:, i]
+        return outputs
 
     # ------------------------------------------------------------------ the hot path
     def _frame_T(self, inputs, outputs, frame_id):

@@ -778,6 +778,23 @@ int dmh_down_conv_fwd_img(const float* x, const float* image, int has_down, cons
 int dmh_down_conv_bwd_data_img(const float* g3, const float* gd, const float* image, const float* g_add, int B, int Cin, int Cout,
                                int H, int W, float* g_x, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K29 the pose head: the tail of the pose decoder (MD2/networks/pose_decoder.py:47-52: out.mean(3).mean(2), 0.01 *, view, split)
+ *     and transformation_from_parameters (MD2/layers.py:28-103), one launch per direction.
+ *     fwd:  x[B][6 nf][h][w] -> axisangle[B][nf][1][3], translation[B][nf][1][3] = scale * channel means (scale = 0.01 in the
+ *           decoder), T[B][nf][4][4] = Trans(t) Rot(a), or Rot(a)^T Trans(-t) for the frames whose bit of invert_mask is set
+ *           (negative frame ids, MD2/trainer.py:408-410).  Fixed-order sums, precise sinf / cosf, the angle + 1e-7 of the axis.
+ *     bwd:  g_x[B][6 nf][h][w] = (d / d (scale * mean)) * scale / (h w), broadcast, from g_T and the optional g_axisangle /
+ *           g_translation (any may be NULL, not all three) and the forward's axisangle / translation.  At a zero axis-angle the
+ *           gradient of the norm is taken as 0 (torch's norm backward); the output is finite.
+ *     B <= 65535, nf <= 32, h w < 2^24.  Bitwise reproducible; the invert flags travel as a kernel argument.
+ * ---------------------------------------------------------------------------------- */
+int dmh_pose_head_fwd(const float* x, int B, int nf, int h, int w, float scale, uint32_t invert_mask, float* axisangle,
+                      float* translation, float* T, void* stream);
+int dmh_pose_head_bwd(const float* g_T, const float* g_axisangle, const float* g_translation, const float* axisangle,
+                      const float* translation, int B, int nf, int h, int w, float scale, uint32_t invert_mask, float* g_x,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
