@@ -176,6 +176,14 @@ _SIGNATURES = {
     "dmh_down_conv_weight_image": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "dmh_down_conv_fwd_img": (C.c_int, [_fp, _fp, C.c_int, _fp, _fp] + [C.c_int] * 6 + [_fp] * 3),
     "dmh_down_conv_bwd_data_img": (C.c_int, [_fp] * 4 + [C.c_int] * 5 + [_fp, _fp]),
+    # host-only launch-form queries of K12 / K13 / K14 (no launch)
+    "dmh_conv3x3_head_fwd_form": (C.c_int, [C.c_int] * 5),
+    "dmh_conv3x3_head_bwd_data_nsplit": (C.c_int, [C.c_int] * 4),
+    "dmh_conv3x3_head_wrw_strips": (C.c_int64, [C.c_int] * 5),
+    "dmh_conv3x3_head_wrw_channel_groups": (C.c_int, [C.c_int] * 5),
+    "dmh_conv7x7s2_bwd_data_ksplit": (C.c_int, [C.c_int] * 3),
+    "dmh_stem_conv_norm_fwd_tiles": (C.c_int64, [C.c_int] * 3),
+    "dmh_stem_conv_norm_fwd_workgroups": (C.c_int, [C.c_int] * 3),
     "dmh_pose_head_fwd": (C.c_int, [_fp] + [C.c_int] * 4 + [C.c_float, C.c_uint32] + [_fp] * 4),
     "dmh_pose_head_bwd": (C.c_int, [_fp] * 5 + [C.c_int] * 4 + [C.c_float, C.c_uint32, _fp, _fp]),
 }

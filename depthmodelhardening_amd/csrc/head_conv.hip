@@ -365,6 +365,17 @@ inline WrwGeo wrw_geo(int B, int C, int Ho, int Wo) {
     return g;
 }
 
+// ---- launch forms: ONE host function per decision, called by the launcher and returned by the dmh_*_form queries below
+// forward: the strip kernel at pad 0 while the byte offsets of an image fit 32 bits, the LDS-tile kernel otherwise
+inline bool head_fwd_strips(int C, int H, int W, int pad) {
+    return pad == 0 && (int64_t)C * H * W < ((int64_t)1 << 29) && !force_tile_kernel();
+}
+// backward-data: waves that share a strip of 62 x BR pixels of g_x (channel split); few strips: four, to fill the chip
+inline long long head_bwd_strips(int B, int H, int W) {
+    return (long long)B * ((W + FCOLS - 1) / FCOLS) * ((H + BR - 1) / BR);
+}
+inline int head_bwd_nsplit(int B, int H, int W) { return head_bwd_strips(B, H, W) >= 2048 ? 1 : 4; }
+
 }  // namespace
 
 extern "C" {
@@ -385,13 +396,37 @@ int dmh_conv3x3_head_bwd_data(const float* g, const float* w, int B, int C, int 
     a.Wo = W - 2;
     a.sx = (W + FCOLS - 1) / FCOLS;
     a.sy = (H + BR - 1) / BR;
-    const long long strips = (long long)B * a.sx * a.sy;
-    a.nsplit = strips >= 2048 ? 1 : 4;          // few strips: split the channels over four waves to fill the chip
+    const long long strips = head_bwd_strips(B, H, W);
+    a.nsplit = head_bwd_nsplit(B, H, W);
     DMH_REQUIRE(strips * a.nsplit < (1ll << 31), "grid too large");
     a.nwaves = (int)(strips * a.nsplit);
     hipLaunchKernelGGL(head_bwd_strip_kernel, dim3((unsigned)((a.nwaves + NT / 64 - 1) / (NT / 64))), dim3(NT), 0,
                        (hipStream_t)stream, a);
     return check_launch("dmh_conv3x3_head_bwd_data");
+}
+
+int dmh_conv3x3_head_fwd_form(int B, int C, int H, int W, int pad) {
+    if (B <= 0 || C <= 0 || pad < 0 || pad > 2 || H + 2 * pad - 2 < 1 || W + 2 * pad - 2 < 1 ||
+        (int64_t)C * H * W >= ((int64_t)1 << 31))
+        return -1;
+    const bool strips = head_fwd_strips(C, H, W, pad);
+    if (C % (strips ? 4 : KC) != 0) return -1;
+    return strips ? 1 : 0;
+}
+
+int dmh_conv3x3_head_bwd_data_nsplit(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || C % 4 != 0 || H < 3 || W < 3) return -1;
+    return head_bwd_nsplit(B, H, W);
+}
+
+int dmh_conv3x3_head_wrw_channel_groups(int B, int C, int H, int W, int pad) {
+    if (B <= 0 || C <= 0 || pad < 0 || pad > 2 || H + 2 * pad - 2 < 1 || W + 2 * pad - 2 < 1) return -1;
+    return wrw_geo(B, C, H + 2 * pad - 2, W + 2 * pad - 2).cg;
+}
+
+int64_t dmh_conv3x3_head_wrw_strips(int B, int C, int H, int W, int pad) {
+    if (B <= 0 || C <= 0 || pad < 0 || pad > 2 || H + 2 * pad - 2 < 1 || W + 2 * pad - 2 < 1) return -1;
+    return wrw_geo(B, C, H + 2 * pad - 2, W + 2 * pad - 2).strips;
 }
 
 int64_t dmh_conv3x3_head_wrw_partials_size(int B, int C, int H, int W, int pad) {
@@ -437,12 +472,13 @@ int dmh_conv3x3_head(const float* x, const float* w, const float* bias, int B, i
                      void* stream) {
     DMH_REQUIRE(x && w && y, "null pointer");
     DMH_REQUIRE(pad >= 0 && pad <= 2, "pad must be 0, 1 or 2");
-    DMH_REQUIRE(B > 0 && C > 0 && (C % KC == 0 || (pad == 0 && C % 4 == 0 && !force_tile_kernel())),
-                "input channels must be a multiple of 16 (pad 0: of 4)");
     const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
+    DMH_REQUIRE(B > 0 && C > 0, "batch and channel count must be positive");
     DMH_REQUIRE(Ho >= 1 && Wo >= 1, "image smaller than the filter");
     DMH_REQUIRE((int64_t)C * H * W < ((int64_t)1 << 31), "image too large");
-    if (pad == 0 && (int64_t)C * H * W < ((int64_t)1 << 29) && !force_tile_kernel()) {     // the strip kernel
+    // by the form the shape takes: a pad-0 image beyond the strip kernel's 32-bit byte offsets runs the tile kernel too
+    DMH_REQUIRE(C % (head_fwd_strips(C, H, W, pad) ? 4 : KC) == 0, "input channels must be a multiple of 16 (pad 0: of 4)");
+    if (head_fwd_strips(C, H, W, pad)) {
         HFArgs a;
         a.x = x;
         a.w = w;

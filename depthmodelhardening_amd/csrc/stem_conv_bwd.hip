@@ -147,6 +147,12 @@ __global__ __launch_bounds__(NT) void stem_conv_bwd_kernel(const float* __restri
     }
 }
 
+// launch form: few workgroups (a window, a small batch) run KS = 4, four channel groups per workgroup on a quarter of the
+// rows; ONE host function, called by the launcher and returned by dmh_conv7x7s2_bwd_data_ksplit.  wh x ww: 2x2 blocks covered
+inline int stem_bwd_ksplit(int B, int wh, int ww) {
+    return (long long)B * ((ww + BX - 1) / BX) * ((wh + BY - 1) / BY) < 2048 ? 4 : 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -154,9 +160,8 @@ extern "C" {
 static int launch_stem_bwd(const float* g_y, const float* w, int B, int K, int Cin, int H, int W, const StemWin& sw_,
                            float* g_x, void* stream, const char* fn) {
     const int Ho = H / 2, Wo = W / 2;
-    // few workgroups (a window): four channel groups per workgroup, a quarter of the rows
     const int gx = (sw_.ww + BX - 1) / BX;
-    const bool split = (long long)B * gx * ((sw_.wh + BY - 1) / BY) < 2048;
+    const bool split = stem_bwd_ksplit(B, sw_.wh, sw_.ww) == 4;
     const int by = split ? BY / 4 : BY, gyb = (sw_.wh + by - 1) / by;
     const long long blocks = (long long)B * gx * gyb;
     if (blocks >= (1ll << 31)) return fail(DMH_EINVAL, "%s: grid too large", fn);
@@ -189,6 +194,11 @@ int dmh_conv7x7s2_bwd_data(const float* g_y, const float* w, int B, int K, int C
     StemWin sw_;
     sw_.win_org = nullptr; sw_.gy_org = nullptr; sw_.wh = Ho; sw_.ww = Wo; sw_.sh = Ho; sw_.sw = Wo;
     return launch_stem_bwd(g_y, w, B, K, Cin, H, W, sw_, g_x, stream, "dmh_conv7x7s2_bwd_data");
+}
+
+int dmh_conv7x7s2_bwd_data_ksplit(int B, int H, int W) {
+    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1)) return -1;
+    return stem_bwd_ksplit(B, H / 2, W / 2);
 }
 
 int dmh_conv7x7s2_bwd_data_win(const float* g_y, const float* w, const int* img_org, const int* gy_org, int B, int K, int Cin,

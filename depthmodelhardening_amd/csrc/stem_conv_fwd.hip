@@ -126,6 +126,13 @@ __global__ __launch_bounds__(NT, 2) void stem_conv_fwd_kernel(const SArgs a) {
     }
 }
 
+// launch geometry: tiles of TR x TC outputs on at most 512 workgroups (2 per CU), persistent over the tiles beyond that; ONE
+// host function each, called by the launcher and returned by dmh_stem_conv_norm_fwd_tiles / _workgroups
+inline long long stem_fwd_tiles(int B, int hw, int ww) {
+    return (long long)B * ((ww + TC - 1) / TC) * ((hw + TR - 1) / TR);
+}
+inline int stem_fwd_workgroups(long long tiles) { return (int)(tiles < 512 ? tiles : 512); }
+
 }  // namespace
 
 extern "C" {
@@ -146,12 +153,12 @@ static int launch_stem_fwd(const float* x, const float* w, const int* org, int B
     a.ww = ww;
     a.gx = (ww + TC - 1) / TC;
     a.gy = (hw + TR - 1) / TR;
-    const long long tiles = (long long)B * a.gx * a.gy;
+    const long long tiles = stem_fwd_tiles(B, hw, ww);
     if (tiles >= (1ll << 31)) return fail(DMH_EINVAL, "%s: grid too large", fn);
     a.ntiles = (int)tiles;
     a.mean = mean;
     a.inv_std = 1.0f / std;
-    const int blocks = (int)(tiles < 512 ? tiles : 512);        // 2 workgroups per CU, persistent over the tiles
+    const int blocks = stem_fwd_workgroups(tiles);
     hipLaunchKernelGGL(stem_conv_fwd_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a);
     return check_launch(fn);
 }
@@ -163,6 +170,16 @@ int dmh_stem_conv_norm_fwd(const float* x, const float* w, int B, int H, int W, 
     DMH_REQUIRE(std > 0.f, "std must be positive");
     DMH_REQUIRE((int64_t)B * 64 * (H / 2) * (W / 2) < ((int64_t)1 << 40), "tensor too large");
     return launch_stem_fwd(x, w, nullptr, B, H, W, H / 2, W / 2, mean, std, y, stream, "dmh_stem_conv_norm_fwd");
+}
+
+int64_t dmh_stem_conv_norm_fwd_tiles(int B, int H, int W) {
+    if (B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1)) return -1;
+    return stem_fwd_tiles(B, H / 2, W / 2);
+}
+
+int dmh_stem_conv_norm_fwd_workgroups(int B, int H, int W) {
+    const int64_t tiles = dmh_stem_conv_norm_fwd_tiles(B, H, W);
+    return tiles < 0 || tiles >= ((int64_t)1 << 31) ? -1 : stem_fwd_workgroups(tiles);
 }
 
 int dmh_stem_conv_norm_fwd_win(const float* x, const float* w, const int* org, int B, int H, int W, int hw, int ww, float mean,

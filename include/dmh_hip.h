@@ -694,6 +694,9 @@ int dmh_conv3x3_small(const float* x, const float* w, const float* bias, int B, 
  * ---------------------------------------------------------------------------------- */
 int dmh_conv7x7s2_bwd_data(const float* g_y, const float* w, int B, int K, int Cin, int H, int W, float* g_x,
                            void* stream);
+/* Launch form of dmh_conv7x7s2_bwd_data for this shape (host only, no launch): 4 = four channel groups per workgroup on a
+ * quarter of the rows (fewer than 2048 workgroups of 16 x 64 pixels), 1 = one group per workgroup; -1: bad shape. */
+int dmh_conv7x7s2_bwd_data_ksplit(int B, int H, int W);
 /* Window form (K19): only the hwin x wwin window of g_x at the per-sample, even pixel origin img_org [B,2] is written (at its
  * place in the whole [B,Cin,H,W] tensor); g_y is a compact [B,K,sh,sw] window of the H/2 x W/2 frame at origin gy_org [B,2]
  * that must hold rows / columns (img_org / 2 - 1) .. ((img_org + hwin) / 2 + 1) of that frame as far as they lie inside it. */
@@ -708,13 +711,23 @@ int dmh_conv7x7s2_bwd_data_win(const float* g_y, const float* w, const int* img_
  * ---------------------------------------------------------------------------------- */
 int dmh_conv3x3_head(const float* x, const float* w, const float* bias, int B, int C, int H, int W, int pad, float* y,
                      void* stream);
+/* Which kernel dmh_conv3x3_head launches for this shape (host only, no launch): 1 = strips, 0 = LDS tile, -1 = a shape it
+ * rejects. */
+int dmh_conv3x3_head_fwd_form(int B, int C, int H, int W, int pad);
 /* gradient w.r.t. the input of the same layer at pad 0: g_x[B,C,H,W] from g[B,1,H-2,W-2] (full correlation with the
  * flipped filter); C a multiple of 4.  One gradient plane in registers, C planes streamed out. */
 int dmh_conv3x3_head_bwd_data(const float* g, const float* w, int B, int C, int H, int W, float* g_x, void* stream);
+/* Waves that share a strip of g_x in dmh_conv3x3_head_bwd_data (channel split; host only): 1 from 2048 strips of 62 x 20
+ * pixels on, 4 below; -1: bad shape. */
+int dmh_conv3x3_head_bwd_data_nsplit(int B, int C, int H, int W);
 /* weight and bias gradient of the same layer (train pass): g_w[1][C][3][3] = sum_{b,y,x} g[b,0,y,x] * zero_pad(x)[b,c,y+ky,x+kx],
  * g_b[0] = sum g (g_b may be NULL).  `partials`: dmh_conv3x3_head_wrw_partials_size(...) floats of workspace (per-strip
  * sums, added in a fixed order: deterministic).  Any C. */
 int64_t dmh_conv3x3_head_wrw_partials_size(int B, int C, int H, int W, int pad);
+/* Launch form of dmh_conv3x3_head_wrw (host only): strips of 62 x 40 outputs, and the waves per strip that share its
+ * channels (doubled while strips x groups < 4096 and the groups divide C); -1: bad shape. */
+int64_t dmh_conv3x3_head_wrw_strips(int B, int C, int H, int W, int pad);
+int dmh_conv3x3_head_wrw_channel_groups(int B, int C, int H, int W, int pad);
 int dmh_conv3x3_head_wrw(const float* x, const float* g, int B, int C, int H, int W, int pad, float* partials, float* g_w,
                          float* g_b, void* stream);
 
@@ -737,6 +750,10 @@ int dmh_conv3x3_small_wrw(const float* x, const float* g, int B, int C, int H, i
  * ---------------------------------------------------------------------------------- */
 int dmh_stem_conv_norm_fwd(const float* x, const float* w, int B, int H, int W, float mean, float std, float* y,
                            void* stream);
+/* Launch geometry of dmh_stem_conv_norm_fwd (host only): tiles of 4 x 32 outputs and the workgroups that run them (at most
+ * 512: persistent over the tiles beyond that); -1: bad shape. */
+int64_t dmh_stem_conv_norm_fwd_tiles(int B, int H, int W);
+int dmh_stem_conv_norm_fwd_workgroups(int B, int H, int W);
 /* Window form (K19): only the hw x ww window of the H/2 x W/2 output at the per-sample origin org [B,2] is computed, into a
  * compact y[B,64,hw,ww]; x stays the whole image (zero padding outside it as above). */
 int dmh_stem_conv_norm_fwd_win(const float* x, const float* w, const int* org, int B, int H, int W, int hw, int ww, float mean,

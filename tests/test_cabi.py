@@ -145,3 +145,45 @@ def test_strided_and_stem_weight_gradient_entry_points_without_gpu():
     assert lib.dmh_stem_wrw_workspace_size(2, 37, 72) == -1 and lib.dmh_stem_wrw_workspace_size(2, 38, 76) == -1
     assert lib.dmh_stem_wrw(one, one, 2, 38, 76, 0.45, 0.225, one, one, None) != 0 and b"multiple of 8" in lib.dmh_last_error()
     assert lib.dmh_stem_wrw(one, one, 2, 38, 72, 0.45, 0.0, one, one, None) != 0 and b"std" in lib.dmh_last_error()
+
+
+def test_launch_forms_of_the_stem_and_head_convolutions_without_gpu():
+    """K12 / K13 / K14 switch kernel form by grid size; the launchers and these host-only queries share ONE function per
+    decision.  The forms at the workload's shapes: tests/test_gpu_stem_head_anchor.py asserts through the same
+    queries which form each of its cases reached, so a threshold change cannot quietly uncover a form."""
+    from depthmodelhardening_amd import _native as N
+    lib = N.lib()
+    # K12, image gradient: 16 x 64-pixel workgroups, KS = 4 below 2048 of them
+    assert lib.dmh_conv7x7s2_bwd_data_ksplit(12, 320, 1024) == 1            # 12 x 20 x 16 = 3840
+    assert lib.dmh_conv7x7s2_bwd_data_ksplit(2, 320, 1024) == 4             # 640
+    assert lib.dmh_conv7x7s2_bwd_data_ksplit(12, 192, 640) == 4             # 12 x 12 x 10 = 1440
+    assert lib.dmh_conv7x7s2_bwd_data_ksplit(40, 74, 660) == 1              # 40 x 5 x 11 = 2200
+    assert lib.dmh_conv7x7s2_bwd_data_ksplit(12, 321, 1024) == -1
+    # K13 backward-data: strips of 62 x 20 pixels of g_x, one wave per strip from 2048 strips on
+    assert lib.dmh_conv3x3_head_bwd_data_nsplit(12, 16, 322, 1026) == 1     # 12 x 17 x 17 = 3468
+    assert lib.dmh_conv3x3_head_bwd_data_nsplit(2, 16, 322, 1026) == 4      # 578
+    assert lib.dmh_conv3x3_head_bwd_data_nsplit(128, 4, 44, 330) == 1       # 128 x 3 x 6 = 2304
+    assert lib.dmh_conv3x3_head_bwd_data_nsplit(12, 18, 322, 1026) == -1
+    # K13 weight gradient: strips of 62 x 40 outputs, channel groups doubled while strips x groups < 4096
+    assert lib.dmh_conv3x3_head_wrw_strips(32, 16, 322, 1026, 0) == 32 * 8 * 17 == 4352
+    assert lib.dmh_conv3x3_head_wrw_channel_groups(32, 16, 322, 1026, 0) == 1
+    assert lib.dmh_conv3x3_head_wrw_strips(12, 16, 322, 1026, 0) == 1632
+    assert lib.dmh_conv3x3_head_wrw_channel_groups(12, 16, 322, 1026, 0) == 4
+    assert lib.dmh_conv3x3_head_wrw_channel_groups(2, 5, 87, 132, 0) == 1   # odd C: no split however few the strips
+    assert lib.dmh_conv3x3_head_wrw_partials_size(32, 16, 322, 1026, 0) == 4352 * (16 * 9 + 1)
+    assert lib.dmh_conv3x3_head_wrw_strips(0, 16, 322, 1026, 0) == -1
+    # K13 forward: strips at pad 0 (C a multiple of 4), the LDS tile otherwise (C a multiple of 16)
+    assert lib.dmh_conv3x3_head_fwd_form(12, 16, 322, 1026, 0) == 1
+    assert lib.dmh_conv3x3_head_fwd_form(12, 20, 42, 64, 0) == 1
+    assert lib.dmh_conv3x3_head_fwd_form(12, 16, 320, 1024, 1) == 0
+    assert lib.dmh_conv3x3_head_fwd_form(12, 20, 42, 64, 1) == -1
+    assert lib.dmh_conv3x3_head_fwd_form(1, 16, 8192, 4100, 0) == 0         # 2^29 elements: beyond the strips' byte offsets
+    assert lib.dmh_conv3x3_head_fwd_form(1, 20, 8192, 4100, 0) == -1
+    one = ctypes.c_void_p(16)       # rejected by the channel check, before any launch
+    assert lib.dmh_conv3x3_head(one, one, None, 1, 20, 8192, 4100, 0, one, None) != 0 and b"multiple of 16" in lib.dmh_last_error()
+    # K14: tiles of 4 x 32 outputs on at most 512 persistent workgroups
+    assert lib.dmh_stem_conv_norm_fwd_tiles(12, 320, 1024) == 12 * 40 * 16
+    assert lib.dmh_stem_conv_norm_fwd_workgroups(12, 320, 1024) == 512
+    assert lib.dmh_stem_conv_norm_fwd_tiles(30, 46, 130) == 540 and lib.dmh_stem_conv_norm_fwd_workgroups(30, 46, 130) == 512
+    assert lib.dmh_stem_conv_norm_fwd_tiles(3, 46, 130) == 54 and lib.dmh_stem_conv_norm_fwd_workgroups(3, 46, 130) == 54
+    assert lib.dmh_stem_conv_norm_fwd_tiles(3, 45, 130) == -1

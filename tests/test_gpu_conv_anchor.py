@@ -15,6 +15,12 @@ known exception lives in tests/test_gpu_conv_epilogue.py: K10's whole-item form 
 output's C transformed products in one accumulator, and at C = 512 and batch 2 its chain rounding (6.7e-7) is 3x the library's
 non-Winograd algorithm there (2.2e-7; MIOpen's F(2,3) measures 6.6e-7 at batch 12).  It is held to that chain's estimate.  The direct MFMA kernels (K11 / K15 / K16) sum an output's products in ONE accumulator
 chain where the library's implicit GEMMs split it: they get the chain's own rounding (0.5 sqrt(n) 2^-24) beside that bound.
+
+The anchored kernels: K10, K11, K15, K16, K17, K18 here, K10's fused epilogues, K20 and K21 here and in
+tests/test_gpu_conv_epilogue.py, and the stem and head convolutions -- K12 (image gradient of conv1), K13 (the disparity heads:
+tile and strip forward, backward-data, weight and bias gradient) and K14 (normalisation + conv1) -- in
+tests/test_gpu_stem_head_anchor.py: every launch form of theirs at the workload's shapes under this bound, and at ragged
+tile / strip edges element by element under a derived rounding bound (tests/util.py: assert_round_bound).
 """
 import pytest
 import torch

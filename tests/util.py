@@ -160,3 +160,37 @@ def conv_data(B, C, K, H, W, seed):
     x = torch.randn(B, C, H, W, generator=g).cuda()
     w = (torch.randn(K, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).cuda()
     return x, w
+
+
+# ---- element-wise rounding bound (tests/test_round_bound.py, tests/test_gpu_stem_head_anchor.py) ---------------------------------
+
+U32 = 2.0 ** -24        # unit roundoff of fp32 (round to nearest)
+
+
+def round_bound_violations(got, ref64, S, n_round, extra=None):
+    """Boolean mask of the elements that break  |got - ref64| <= n_round * 2^-24 * S (+ extra).
+
+    ``ref64``: the operation in float64.  ``S``: the same operation on absolute values in float64 (conv(|x|, |w|) + |b|, or
+    sum |g * x| per tap): the sum of the magnitudes every rounding acts on.  ``n_round``: the number of fp32 roundings on the
+    longest path one product takes to the output, read from the kernel -- each rounding of a partial sum p errs by at most
+    2^-24 |p| <= 2^-24 S, so n of them by n 2^-24 S to first order (the second-order term is n 2^-24 / 2 of that).
+    ``extra``: a separately derived float64 term of the same shape (K14's input normalisation), never a measured number.
+    An element that is NaN or infinite is a violation: nothing here is an outlier share or an additive slack."""
+    got, ref64, S = got.detach().double(), ref64.detach().double(), S.detach().double()
+    assert got.shape == ref64.shape == S.shape, (got.shape, ref64.shape, S.shape)
+    bound = float(n_round) * U32 * S
+    if extra is not None:
+        bound = bound + extra.detach().double()
+    return ~((got - ref64).abs() <= bound)
+
+
+def assert_round_bound(name, got, ref64, S, n_round, extra=None):
+    """Every element inside the derived bound of round_bound_violations; prints and returns the largest share of it used."""
+    bad = round_bound_violations(got, ref64, S, n_round, extra)
+    bound = float(n_round) * U32 * S.detach().double() + (0 if extra is None else extra.detach().double())
+    err = (got.detach().double() - ref64.detach().double()).abs()
+    used = float(torch.nan_to_num(err / bound.clamp_min(1e-300), nan=float("inf")).max()) if err.numel() else 0.0
+    print("%-52s n_round %6d  worst |err| / bound %.3f" % (name, n_round, used))
+    assert not bool(bad.any()), "%s: %d of %d elements beyond n_round * 2^-24 * S (n_round %d, worst share %.3g)" % (
+        name, int(bad.sum()), bad.numel(), n_round, used)
+    return used
