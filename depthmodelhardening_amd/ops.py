@@ -83,6 +83,13 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _need_cuda(t):
+    """A CPU operand (``t``: a tensor or a torch.device) is an error, never another code path."""
+    device = t if isinstance(t, torch.device) else t.device
+    if device.type != "cuda":
+        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % device)
+
+
 def _photo_args(cfg, target, sources, Ts, K, inv_K, disps, noises, hint=None):
     a = N.PhotoArgs()
     B, _, H, W = target.shape
@@ -550,8 +557,7 @@ def apgd_controller(steps, eps, loss0, rho=0.75):
     steps = int(steps)
     if steps < 1 or steps >= 1 << 24:
         raise RuntimeError("apgd_controller: steps must lie in [1, 2^24)")
-    if not loss0.is_cuda:
-        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % loss0.device)
+    _need_cuda(loss0)
     k0, steps_min, size_decr = max(int(0.22 * steps), 1), max(int(0.06 * steps), 1), max(int(0.03 * steps), 1)
     host = torch.zeros((steps + 1, APGD_REC), dtype=torch.float32)
     host[0, 0], host[0, 1], host[0, 4], host[0, 7] = 2.0 * float(torch.tensor(eps, dtype=torch.float32)), 1.0, k0, 1.0
@@ -981,8 +987,7 @@ class L0FusedState(object):
         steps = int(steps)
         if steps < 1 or steps >= 1 << 24:
             raise RuntimeError("L0FusedState: steps must lie in [1, 2^24)")
-        if not pos.is_cuda:
-            raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % pos.device)
+        _need_cuda(pos)
         dev = pos.device
         self.steps = steps
         self.pos, self.neg = _c(pos.detach()), _c(neg.detach())
@@ -1268,18 +1273,22 @@ def bn_act_train(bn, x, residual=None, relu=True):
     return _BnActTrain.apply(_c(x), bn.weight, bn.bias, None if residual is None else _c(residual), bool(relu), bn)
 
 
+def _stem_pool_fwd(x, scale, shift):
+    """K9 stem: (feat = relu(x * scale + shift), maxpool3x3/2(feat), the pool's argmax bytes) in one launch."""
+    B, Cc, H, W = x.shape
+    feat = torch.empty_like(x)
+    pooled = torch.empty((B, Cc, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    arg = torch.empty((B, Cc, H // 2, W // 2), device=x.device, dtype=torch.uint8)
+    nb = 4 * (2 * x.numel() + pooled.numel()) + arg.numel()
+    N.check(_timed("stem_fwd", lambda: N.lib().dmh_stem_bn_relu_pool_fwd(N.ptr(x), N.ptr(scale), N.ptr(shift), B, Cc, H, W,
+                                                                        N.ptr(feat), N.ptr(pooled), N.ptr(arg), N.stream()), nb))
+    return feat, pooled, arg
+
+
 class _StemBnReluPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, scale, shift):
-        lib = N.lib()
-        B, Cc, H, W = x.shape
-        feat = torch.empty_like(x)
-        pooled = torch.empty((B, Cc, H // 2, W // 2), device=x.device, dtype=torch.float32)
-        arg = torch.empty((B, Cc, H // 2, W // 2), device=x.device, dtype=torch.uint8)
-        nb = 4 * (2 * x.numel() + pooled.numel()) + arg.numel()
-        N.check(_timed("stem_fwd", lambda: lib.dmh_stem_bn_relu_pool_fwd(N.ptr(x), N.ptr(scale), N.ptr(shift), B, Cc, H, W,
-                                                                        N.ptr(feat), N.ptr(pooled), N.ptr(arg),
-                                                                        N.stream()), nb))
+        feat, pooled, arg = _stem_pool_fwd(x, scale, shift)
         ctx.save_for_backward(feat, arg, scale)
         ctx.mark_non_differentiable(arg)
         ctx.set_materialize_grads(False)    # an unused output hands None to backward: the kernel skips that read
@@ -1309,16 +1318,8 @@ class _StemTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn):
-        lib = N.lib()
         scale, shift, mean, invstd = _bn_train_stats(x, bn)
-        B, Cc, H, W = x.shape
-        feat = torch.empty_like(x)
-        pooled = torch.empty((B, Cc, H // 2, W // 2), device=x.device, dtype=torch.float32)
-        arg = torch.empty((B, Cc, H // 2, W // 2), device=x.device, dtype=torch.uint8)
-        nb = 4 * (2 * x.numel() + pooled.numel()) + arg.numel()
-        N.check(_timed("stem_fwd", lambda: lib.dmh_stem_bn_relu_pool_fwd(N.ptr(x), N.ptr(scale), N.ptr(shift), B, Cc, H, W,
-                                                                        N.ptr(feat), N.ptr(pooled), N.ptr(arg),
-                                                                        N.stream()), nb))
+        feat, pooled, arg = _stem_pool_fwd(x, scale, shift)
         ctx.save_for_backward(x, weight, mean, invstd, feat, arg)
         ctx.eps, ctx.bn = float(bn.eps), bn
         ctx.mark_non_differentiable(arg)
@@ -1592,18 +1593,6 @@ def _wino32_filter(weight, backward):
     return U
 
 
-def _wino32_conv(x, U, bias, K, pad):
-    lib = N.lib()
-    B, Cc, H, W = x.shape
-    y = torch.empty((B, K, H + 2 * pad - 2, W + 2 * pad - 2), device=x.device, dtype=torch.float32)
-    nb = 4 * (x.numel() + y.numel()) + 4 * U.numel()
-    ws = _sk_workspace(x.device) if WINO_SK else None
-    N.check(_timed("wino32_conv3x3", lambda: lib.dmh_wino32_conv3x3_ws(
-        N.ptr(x), N.ptr(U), N.ptr(bias), B, Cc, K, H, W, pad, N.ptr(y), N.ptr(ws), 0 if ws is None else ws.numel(), N.stream()),
-        nb, 18 * Cc * y.numel()))
-    return y
-
-
 _sk_ws = {}         # (device, stream) -> workspace of the stream-K launches (caller-owned: the library keeps nothing)
 _SK_SLOT_FLOATS = 16384         # one partial work item: 16 output channels x 256 threads x float4
 
@@ -1625,24 +1614,51 @@ def _sk_workspace(device):
     return ws
 
 
-def _k10_act(lib, x, U, bias, res, relu, B, Cc, K, H, W, pad, y, stream):
-    """dmh_wino_conv3x3_act with the stream-K workspace of the current device (the library takes the decomposed form only for
-    launches of few tile regions: layer4 at the attack batch)."""
-    if not WINO_SK:
+def _k10_act(lib, x, U, bias, res, relu, B, Cc, K, H, W, pad, y, stream, workspace=True):
+    """K10 with the fused epilogue.  ``workspace``: hand the library the stream-K workspace of the current device (it takes the
+    decomposed form only for launches of few tile regions: layer4 at the attack batch); without one it runs whole items."""
+    if not (workspace and WINO_SK):
         return lib.dmh_wino_conv3x3_act(x, U, bias, res, relu, B, Cc, K, H, W, pad, y, stream)
     ws = _sk_workspace(torch.device("cuda", torch.cuda.current_device()))
     return lib.dmh_wino_conv3x3_act_ws(x, U, bias, res, relu, B, Cc, K, H, W, pad, y, N.ptr(ws), ws.numel(), stream)
 
 
-def _wino_conv(x, U, bias, K, pad):
+def _k10(x, w, scale, *, backward, bias=None, res=None, flag, workspace, pad=1, count_filter=False):
+    """One K10 launch with the fused epilogue: conv3x3(x) with the filter ``w`` (``backward``: its backward-data pass on a
+    gradient x), ``scale`` folded into the filter, + ``bias``, then by ``flag``: 0 = + res, 1 = ReLU(. + res), 2 = masked by
+    [res > 0].  ``workspace``: see _k10_act -- the block nodes pass True; the encoder heads' window launches pass False, since a
+    workspace lets the library choose the stream-K form, which sums in another order.  ``count_filter``: the profile's byte
+    count includes the filter image."""
+    B, Cc, H, W = x.shape
+    K = w.shape[1] if backward else w.shape[0]
+    y = torch.empty((B, K, H + 2 * pad - 2, W + 2 * pad - 2), device=x.device, dtype=torch.float32)
+    U = _wino_filter(w, backward, scale)
+    nb = 4 * (x.numel() + y.numel() * (1 if res is None else 2)) + (4 * U.numel() if count_filter else 0)
+    N.check(_timed("wino_conv3x3", lambda: _k10_act(N.lib(), N.ptr(x), N.ptr(U), N.ptr(bias), N.ptr(res), int(flag), B, Cc, K, H, W,
+                                                    pad, N.ptr(y), N.stream(), workspace), nb, 18 * Cc * y.numel()))
+    return y
+
+
+def _relu_mask_bwd(y, g):
+    """g * [y > 0] on whole tensors: the K9 backward kernel with a unit scale."""
+    B, Cc = g.shape[0], g.shape[1]
+    ones = frozen_memo(("ones", Cc, g.device), lambda: torch.ones(Cc, device=g.device, dtype=torch.float32))
+    g_pre = torch.empty_like(g)
+    N.check(_timed("bn_act_bwd", lambda: N.lib().dmh_bn_act_bwd(N.ptr(y), N.ptr(g), N.ptr(ones), B, Cc, g.numel() // (B * Cc), 1,
+                                                               N.ptr(g_pre), None, N.stream()), 12 * g.numel()))
+    return g_pre
+
+
+def _wino_conv(x, U, bias, K, pad, k17=False):
+    """The plain K10 launch, or (``k17``) K17's, on a transformed filter U."""
     lib = N.lib()
+    launch, name = (lib.dmh_wino32_conv3x3_ws, "wino32_conv3x3") if k17 else (lib.dmh_wino_conv3x3_ws, "wino_conv3x3")
     B, Cc, H, W = x.shape
     y = torch.empty((B, K, H + 2 * pad - 2, W + 2 * pad - 2), device=x.device, dtype=torch.float32)
     nb = 4 * (x.numel() + y.numel()) + 4 * U.numel()
     ws = _sk_workspace(x.device) if WINO_SK else None
-    N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_ws(
-        N.ptr(x), N.ptr(U), N.ptr(bias), B, Cc, K, H, W, pad, N.ptr(y), N.ptr(ws), 0 if ws is None else ws.numel(), N.stream()),
-        nb, 18 * Cc * y.numel()))
+    N.check(_timed(name, lambda: launch(N.ptr(x), N.ptr(U), N.ptr(bias), B, Cc, K, H, W, pad, N.ptr(y), N.ptr(ws),
+                                        0 if ws is None else ws.numel(), N.stream()), nb, 18 * Cc * y.numel()))
     return y
 
 
@@ -1668,6 +1684,24 @@ def _small_conv(x, weight, bias, pad, backward):
     return y
 
 
+def _head_conv(x, weight, bias, pad):
+    """K13: the 3x3 convolution to ONE output channel (the disparity heads)."""
+    B, Cc, H, W = x.shape
+    y = torch.empty((B, 1, H + 2 * pad - 2, W + 2 * pad - 2), device=x.device, dtype=torch.float32)
+    N.check(_timed("conv3x3_head", lambda: N.lib().dmh_conv3x3_head(N.ptr(x), N.ptr(_c(weight.detach())), N.ptr(bias), B, Cc, H, W,
+                                                                   pad, N.ptr(y), N.stream()), 4 * (x.numel() + y.numel())))
+    return y
+
+
+def _head_conv_bwd(g, weight):
+    """K13's backward-data pass at forward padding 0: one gradient plane in registers, C planes streamed out."""
+    B, Cc, H, W = g.shape[0], weight.shape[1], g.shape[2] + 2, g.shape[3] + 2
+    g_x = torch.empty((B, Cc, H, W), device=g.device, dtype=torch.float32)
+    N.check(_timed("conv3x3_head_bwd", lambda: N.lib().dmh_conv3x3_head_bwd_data(
+        N.ptr(g), N.ptr(_c(weight.detach())), B, Cc, H, W, N.ptr(g_x), N.stream()), 4 * (g_x.numel() + g.numel())))
+    return g_x
+
+
 class _Conv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, pad):
@@ -1680,15 +1714,10 @@ class _Conv3x3(torch.autograd.Function):
         if _wino_ok(B, Cc, K, H + 2 * pad - 2, W + 2 * pad - 2):
             return _wino_conv(x, _wino_filter(weight, False), None if bias is None else _c(bias.detach()), K, pad)
         if _wino32_ok(B, Cc, K, H + 2 * pad - 2, W + 2 * pad - 2):
-            return _wino32_conv(x, _wino32_filter(weight, False), None if bias is None else _c(bias.detach()), K, pad)
+            return _wino_conv(x, _wino32_filter(weight, False), None if bias is None else _c(bias.detach()), K, pad, k17=True)
         if WINO_ENABLED and K == 1 and ((pad == 0 and Cc % 4 == 0) or (      # disparity head: K13 (strip kernel at pad 0)
                 Cc % 16 == 0 and Cc >= 32 and B * -(-(H + 2 * pad - 2) // 8) * -(-(W + 2 * pad - 2) // 64) >= 512)):
-            lib = N.lib()
-            y = torch.empty((B, 1, H + 2 * pad - 2, W + 2 * pad - 2), device=x.device, dtype=torch.float32)
-            N.check(_timed("conv3x3_head", lambda: lib.dmh_conv3x3_head(
-                N.ptr(x), N.ptr(_c(weight.detach())), N.ptr(None if bias is None else _c(bias.detach())), B, Cc, H, W, pad,
-                N.ptr(y), N.stream()), 4 * (x.numel() + y.numel())))
-            return y
+            return _head_conv(x, weight, None if bias is None else _c(bias.detach()), pad)
         if _small_ok(Cc, K):
             return _small_conv(x, weight, None if bias is None else _c(bias.detach()), pad, False)
         return torch.conv2d(x, weight, bias, 1, pad)
@@ -1709,13 +1738,10 @@ class _Conv3x3(torch.autograd.Function):
             g_x = _wino_conv(g, _wino_filter(weight, True), None, Cc, 2 - pad)
             need_x = False
         elif need_x and _wino32_ok(B, K, Cc, H, W):
-            g_x = _wino32_conv(g, _wino32_filter(weight, True), None, Cc, 2 - pad)
+            g_x = _wino_conv(g, _wino32_filter(weight, True), None, Cc, 2 - pad, k17=True)
             need_x = False
         elif need_x and K == 1 and pad == 0 and Cc % 4 == 0 and Cc <= 64 and H >= 3 and W >= 3 and WINO_ENABLED:
-            lib = N.lib()           # disparity head: one gradient plane in registers, C planes streamed out
-            g_x = torch.empty_like(x)
-            N.check(_timed("conv3x3_head_bwd", lambda: lib.dmh_conv3x3_head_bwd_data(
-                N.ptr(g), N.ptr(_c(weight.detach())), B, Cc, H, W, N.ptr(g_x), N.stream()), 4 * (g_x.numel() + g.numel())))
+            g_x = _head_conv_bwd(g, weight)         # disparity head
             need_x = False
         elif need_x and _small_ok(K, Cc):
             g_x = _small_conv(g, weight, None, 2 - pad, True)
@@ -1767,15 +1793,8 @@ class _ConvBnAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, scale, shift, residual, relu, pad):
-        K = weight.shape[0]
-        lib = N.lib()
-        B, Cc, H, W = x.shape
-        y = torch.empty((B, K, H + 2 * pad - 2, W + 2 * pad - 2), device=x.device, dtype=torch.float32)
-        U = _wino_filter(weight, False, scale)
-        nb = 4 * (x.numel() + y.numel() * (1 if residual is None else 2)) + 4 * U.numel()
-        N.check(_timed("wino_conv3x3", lambda: _k10_act(lib, N.ptr(x), N.ptr(U), N.ptr(shift), N.ptr(residual),
-                                                                       int(relu), B, Cc, K, H, W, pad, N.ptr(y),
-                                                                       N.stream()), nb, 18 * Cc * y.numel()))
+        y = _k10(x, weight, scale, backward=False, bias=shift, res=residual, flag=int(relu), workspace=True, pad=pad,
+                 count_filter=True)
         ctx.save_for_backward(x, weight, scale, y if relu else None)
         ctx.pad, ctx.relu = pad, bool(relu)
         ctx.res_grad = residual is not None and residual.requires_grad
@@ -1785,17 +1804,10 @@ class _ConvBnAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, scale, y = ctx.saved_tensors
-        lib = N.lib()
         B, Cc, H, W = x.shape
         K = weight.shape[0]
         g = _c(g)
-        if ctx.relu:        # g_pre = g * [y > 0] (K9 kernel with a unit scale); it is also the residual's gradient
-            ones = frozen_memo(("ones", K, g.device), lambda: torch.ones(K, device=g.device, dtype=torch.float32))
-            g_pre = torch.empty_like(g)
-            N.check(_timed("bn_act_bwd", lambda: lib.dmh_bn_act_bwd(N.ptr(y), N.ptr(g), N.ptr(ones), B, K, g.numel() // (B * K),
-                                                                   1, N.ptr(g_pre), None, N.stream()), 12 * g.numel()))
-        else:
-            g_pre = g
+        g_pre = _relu_mask_bwd(y, g) if ctx.relu else g         # it is also the residual's gradient
         g_x = g_w = None
         need_w = ctx.needs_input_grad[1] and not ctx.params_const
         if ctx.needs_input_grad[0]:
@@ -1832,8 +1844,7 @@ def conv3x3(x, weight, bias=None, padding=1):
     remaining shapes are ATen/MIOpen."""
     if padding not in (0, 1, 2) or weight.shape[2:] != (3, 3):
         raise RuntimeError("conv3x3: 3x3 kernel with padding 0, 1 or 2 expected")
-    if not x.is_cuda:
-        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % x.device)
+    _need_cuda(x)
     return _Conv3x3.apply(_c(x), weight, bias, int(padding))
 
 
@@ -1895,19 +1906,43 @@ def stem_conv(x, weight):
     return _StemConv.apply(_c(x), weight)
 
 
+def _stem_conv_norm_fwd(x, weight, mean, std):
+    """K14 on the whole frame: conv1((x - mean) / std), 3 -> 64 channels."""
+    B, _, H, W = x.shape
+    y = torch.empty((B, 64, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    N.check(_timed("stem_conv_fwd", lambda: N.lib().dmh_stem_conv_norm_fwd(N.ptr(x), N.ptr(_c(weight.detach())), B, H, W, mean, std,
+                                                                          N.ptr(y), N.stream()), 4 * (x.numel() + y.numel()),
+                   2 * 147 * y.numel()))
+    return y
+
+
+def _stem_w_over_std(weight, std):
+    """d/dx of conv((x - mean) / std, w) = conv_bwd_data(g, w / std): the 1/std goes into the 9,408 filter taps (once per attack
+    inside frozen_weights()) instead of a pass over the image gradient."""
+    return frozen_memo(("stem_w_over_std", weight.data_ptr(), weight._version, std), lambda: _c(weight.detach() * (1.0 / std)))
+
+
+def _stem_window_bwd(g_z, w_stem, org_z, org_d, size_d, H, W):
+    """K12's window form, the tail of the windowed encoder heads' backward: d / d image [B,3,H,W] of conv1((x - 0.45) / 0.225)
+    from the gradient ``g_z`` of a compact window of its output (origins ``org_z`` on the 1/2 map), written inside the image
+    window (``org_d``, ``size_d``) and zero elsewhere."""
+    B, _, hs, ws = g_z.shape
+    hd, wd = size_d
+    w_s = _stem_w_over_std(w_stem, 0.225)
+    g_x = torch.zeros((B, 3, H, W), device=g_z.device, dtype=torch.float32)
+    N.check(_timed("stem_conv_bwd_win", lambda: N.lib().dmh_conv7x7s2_bwd_data_win(
+        N.ptr(g_z), N.ptr(w_s), N.ptr(org_d), N.ptr(org_z), B, 64, 3, H, W, hd, wd, hs, ws, N.ptr(g_x), N.stream()),
+        4 * (g_z.numel() + B * 3 * hd * wd), 2 * 147 * 64 * B * (hd // 2) * (wd // 2)))
+    return g_x
+
+
 class _StemConvNorm(torch.autograd.Function):
     """K14 forward (normalisation + 7x7/2 convolution on the fp32 MFMA); backward: image gradient by K12 (scaled by 1/std),
     weight gradient by K21 (train pass only; ATen on the re-normalised image for widths that are not multiples of 8)."""
 
     @staticmethod
     def forward(ctx, x, weight, mean, std):
-        lib = N.lib()
-        B, _, H, W = x.shape
-        y = torch.empty((B, 64, H // 2, W // 2), device=x.device, dtype=torch.float32)
-        nb = 4 * (x.numel() + y.numel())
-        N.check(_timed("stem_conv_fwd", lambda: lib.dmh_stem_conv_norm_fwd(N.ptr(x), N.ptr(_c(weight.detach())), B, H, W, mean,
-                                                                          std, N.ptr(y), N.stream()), nb,
-                       2 * 147 * y.numel()))
+        y = _stem_conv_norm_fwd(x, weight, mean, std)
         ctx.save_for_backward(x, weight)
         ctx.norm = (mean, std)
         ctx.params_const = _wino_frozen > 0
@@ -1924,10 +1959,7 @@ class _StemConvNorm(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             g_x = torch.empty_like(x)
             nb = 4 * (g.numel() + g_x.numel())
-            # d/dx of conv((x - mean) / std, w) = conv_bwd_data(g, w / std): the 1/std goes into the 9,408 filter taps
-            # (once per attack inside frozen_weights()) instead of a pass over the image gradient
-            w_s = frozen_memo(("stem_w_over_std", weight.data_ptr(), weight._version, std),
-                              lambda: _c(weight.detach() * (1.0 / std)))
+            w_s = _stem_w_over_std(weight, std)
             N.check(_timed("stem_conv_bwd", lambda: lib.dmh_conv7x7s2_bwd_data(N.ptr(g), N.ptr(w_s), B, 64, Cin, H, W,
                                                                               N.ptr(g_x), N.stream()), nb, 2 * 147 * g.numel()))
         if ctx.needs_input_grad[1] and not ctx.params_const:
@@ -1944,8 +1976,7 @@ def stem_conv_norm(x, weight, mean=0.45, std=0.225):
     ResNet.conv1 (3 -> 64 channels, 7x7, stride 2, padding 3, no bias) -- as ONE launch of the K14 MFMA kernel: the
     normalisation is applied while the input tile is staged, so neither the normalised image nor a layout transpose
     ever exists in memory."""
-    if not x.is_cuda:
-        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % x.device)
+    _need_cuda(x)
     if tuple(weight.shape) != (64, 3, 7, 7) or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 2 or x.shape[3] % 2:
         raise RuntimeError("stem_conv_norm: x must be [B,3,H,W] with even H, W and weight [64,3,7,7]")
     return _StemConvNorm.apply(_c(x), weight, float(mean), float(std))
@@ -2058,11 +2089,22 @@ def down_convs(x, w3, wd):
     """(conv2d(x, w3, stride=2, padding=1), conv2d(x, wd, stride=2)): the first 3x3 convolution and the 1x1 shortcut of a
     down-sampling torchvision BasicBlock (layer2.0 / layer3.0 / layer4.0 under MD2/networks/resnet_encoder.py:94-98), which
     read the same input -- one K15 MFMA launch forward, one for the summed input gradient."""
-    if not x.is_cuda:
-        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % x.device)
+    _need_cuda(x)
     if not down_convs_ok(x, w3, wd):
         raise RuntimeError("down_convs: x [B,C,H,W] (C %% 64 == 0, even H, W), w3 [K,C,3,3], wd [K,C,1,1] (K %% 64 == 0) expected")
     return _DownConvs.apply(_c(x), w3, wd)
+
+
+def _block_fwd(x, w1, s1, b1, w2, s2, b2, workspace):
+    """A stride-1 BasicBlock in eval() as two K10 launches: (out1, y) = (relu(bn1(conv1(x))), relu(bn2(conv2(out1)) + x))."""
+    out1 = _k10(x, w1, s1, backward=False, bias=b1, flag=1, workspace=workspace)
+    return out1, _k10(out1, w2, s2, backward=False, bias=b2, res=x, flag=1, workspace=workspace)
+
+
+def _block_bwd(g2, out1, w1, s1, w2, s2, workspace):
+    """The block's input gradient from ``g2`` = g * [y > 0] (the caller's masking pass), as two K10 launches."""
+    g1 = _k10(g2, w2, s2, backward=True, res=out1, flag=2, workspace=workspace)        # conv2's backward-data * [out1 > 0]
+    return _k10(g1, w1, s1, backward=True, res=g2, flag=0, workspace=workspace)        # conv1's + the identity branch's gradient
 
 
 class _BasicBlockEval(torch.autograd.Function):
@@ -2074,40 +2116,15 @@ class _BasicBlockEval(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, s1, b1, w2, s2, b2):
-        lib = N.lib()
-        B, Cc, H, W = x.shape
-        out1, y = torch.empty_like(x), torch.empty_like(x)
-        nb = 4 * 2 * x.numel()
-        N.check(_timed("wino_conv3x3", lambda: _k10_act(lib, 
-            N.ptr(x), N.ptr(_wino_filter(w1, False, s1)), N.ptr(b1), None, 1, B, Cc, Cc, H, W, 1, N.ptr(out1), N.stream()),
-            nb, 18 * Cc * x.numel()))
-        N.check(_timed("wino_conv3x3", lambda: _k10_act(lib, 
-            N.ptr(out1), N.ptr(_wino_filter(w2, False, s2)), N.ptr(b2), N.ptr(x), 1, B, Cc, Cc, H, W, 1, N.ptr(y), N.stream()),
-            nb + 4 * x.numel(), 18 * Cc * x.numel()))
+        out1, y = _block_fwd(x, w1, s1, b1, w2, s2, b2, True)
         ctx.save_for_backward(out1, y, w1, s1, w2, s2)
         return y
 
     @staticmethod
     def backward(ctx, g):
         out1, y, w1, s1, w2, s2 = ctx.saved_tensors
-        lib = N.lib()
-        B, Cc, H, W = y.shape
-        g = _c(g)
-        ones = frozen_memo(("ones", Cc, g.device), lambda: torch.ones(Cc, device=g.device, dtype=torch.float32))
-        g2 = torch.empty_like(g)            # g * [y > 0]: gradient of conv2's BatchNorm output and of the identity branch
-        N.check(_timed("bn_act_bwd", lambda: lib.dmh_bn_act_bwd(N.ptr(y), N.ptr(g), N.ptr(ones), B, Cc, H * W, 1, N.ptr(g2),
-                                                               None, N.stream()), 12 * g.numel()))
-        g1, g_x = torch.empty_like(g), torch.empty_like(g)
-        nb = 4 * 3 * g.numel()
-        # conv2's backward-data, masked by [out1 > 0] in the epilogue (flag 2)
-        N.check(_timed("wino_conv3x3", lambda: _k10_act(lib, 
-            N.ptr(g2), N.ptr(_wino_filter(w2, True, s2)), None, N.ptr(out1), 2, B, Cc, Cc, H, W, 1, N.ptr(g1), N.stream()),
-            nb, 18 * Cc * g.numel()))
-        # conv1's backward-data + the identity branch's gradient in the epilogue
-        N.check(_timed("wino_conv3x3", lambda: _k10_act(lib, 
-            N.ptr(g1), N.ptr(_wino_filter(w1, True, s1)), None, N.ptr(g2), 0, B, Cc, Cc, H, W, 1, N.ptr(g_x), N.stream()),
-            nb, 18 * Cc * g.numel()))
-        return g_x, None, None, None, None, None, None
+        g2 = _relu_mask_bwd(y, _c(g))       # gradient of conv2's BatchNorm output and of the identity branch
+        return _block_bwd(g2, out1, w1, s1, w2, s2, True), None, None, None, None, None, None
 
 
 def basic_block_eval_ok(x, w1, w2):
@@ -2135,29 +2152,50 @@ def basic_block_eval(x, w1, scale1, shift1, w2, scale2, shift2):
                                  _c(scale2.detach()), _c(shift2.detach()))
 
 
+def _down_block_fwd(x, w3, s1, b1, wd, sd, bd, w2, s2, b2, workspace, count_filters):
+    """A down-sampling BasicBlock in eval(): (out1, y) = (relu(bn1(conv1_s2(x))), relu(bn2(conv2(out1)) + bn_d(conv1x1_s2(x)))) as
+    ONE K15 launch (both BatchNorm scales folded into the filters, shifts and the ReLU in its epilogue) + one K10 launch.
+    ``count_filters``: the profile's byte count of the K15 launch includes the two filters."""
+    B, Cin, H, W = x.shape
+    Co = w3.shape[0]
+    w3s = frozen_memo(("down_w3s", w3.data_ptr(), w3._version, s1.data_ptr()), lambda: _c(w3 * s1.view(-1, 1, 1, 1)))
+    wds = frozen_memo(("down_wds", wd.data_ptr(), wd._version, sd.data_ptr()), lambda: _c(wd * sd.view(-1, 1, 1, 1)))
+    out1 = torch.empty((B, Co, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    idt = torch.empty_like(out1)
+    nb = 4 * (x.numel() + 2 * out1.numel() + (w3.numel() + wd.numel() if count_filters else 0))
+    N.check(_timed("down_conv_fwd", lambda: _k15_fwd(N.lib(), x, w3s, wds, b1, bd, 1, B, Cin, Co, H, W, out1, idt, N.stream()),
+                   nb, 20 * Cin * out1.numel()))
+    return out1, _k10(out1, w2, s2, backward=False, bias=b2, res=idt, flag=1, workspace=workspace)
+
+
+def _down_block_bwd(g1, g2, g_skip, in_shape, w3, s1, wd, sd):
+    """The block's input gradient [``in_shape``] as one K15 launch on the transposed, scaled filters: from ``g1`` (bn1's output:
+    conv2's masked backward-data, the caller's K10 launch), ``g2`` = g * [y > 0] (the shortcut's BatchNorm output) and
+    ``g_skip`` (optional: the gradient of the input's other consumer, added in the epilogue)."""
+    B, Cin, H, W = in_shape
+    Co = w3.shape[0]
+    w3ts = frozen_memo(("down_w3ts", w3.data_ptr(), w3._version, s1.data_ptr()),
+                       lambda: _c((w3 * s1.view(-1, 1, 1, 1)).transpose(0, 1)))
+    wdts = frozen_memo(("down_wdts", wd.data_ptr(), wd._version, sd.data_ptr()),
+                       lambda: _c((wd * sd.view(-1, 1, 1, 1)).reshape(Co, Cin).t()))
+    g_x = torch.empty((B, Cin, H, W), device=g1.device, dtype=torch.float32)
+    N.check(_timed("down_conv_bwd", lambda: _k15_bwd(N.lib(), g1, g2, w3ts, wdts, g_skip, B, Cin, Co, H, W, g_x, N.stream()),
+                   4 * (g_x.numel() * (1 if g_skip is None else 2) + 2 * g1.numel()), 20 * Cin * g1.numel()))
+    return g_x
+
+
 class _DownBlockEval(torch.autograd.Function):
     """A down-sampling torchvision BasicBlock in eval() with constant parameters (inside an attack), as one autograd node:
         out1 = relu(bn1(conv1_s2(x)));  idt = bn_d(conv1x1_s2(x));  y = relu(bn2(conv2(out1)) + idt)
-    forward = ONE K15 launch (both BatchNorm scales folded into the filters, shifts and the ReLU in its epilogue) + one K10
-    launch; backward = one K9 pass (mask by y), one K10 launch (conv2's backward-data masked by [out1 > 0] in the
-    epilogue) and one K15 launch on the transposed, scaled filters -- no separate BatchNorm / ReLU passes."""
+    forward = ONE K15 launch + one K10 launch (_down_block_fwd); backward = one K9 pass (mask by y), one K10 launch (conv2's
+    backward-data masked by [out1 > 0] in the epilogue) and one K15 launch on the transposed, scaled filters -- no separate
+    BatchNorm / ReLU passes."""
 
     @staticmethod
     def forward(ctx, x, w3, s1, b1, wd, sd, bd, w2, s2, b2, want_skip):
-        lib = N.lib()
-        B, Cin, H, W = x.shape
-        Co = w3.shape[0]
-        w3s = frozen_memo(("down_w3s", w3.data_ptr(), w3._version, s1.data_ptr()), lambda: _c(w3 * s1.view(-1, 1, 1, 1)))
-        wds = frozen_memo(("down_wds", wd.data_ptr(), wd._version, sd.data_ptr()), lambda: _c(wd * sd.view(-1, 1, 1, 1)))
-        out1 = torch.empty((B, Co, H // 2, W // 2), device=x.device, dtype=torch.float32)
-        idt, y = torch.empty_like(out1), torch.empty_like(out1)
-        N.check(_timed("down_conv_fwd", lambda: _k15_fwd(lib, x, w3s, wds, b1, bd, 1, B, Cin, Co, H, W, out1, idt, N.stream()),
-                       4 * (x.numel() + 2 * out1.numel() + w3.numel() + wd.numel()), 20 * Cin * out1.numel()))
-        N.check(_timed("wino_conv3x3", lambda: _k10_act(lib, 
-            N.ptr(out1), N.ptr(_wino_filter(w2, False, s2)), N.ptr(b2), N.ptr(idt), 1, B, Co, Co, H // 2, W // 2, 1, N.ptr(y),
-            N.stream()), 4 * 3 * out1.numel(), 18 * Co * out1.numel()))
+        out1, y = _down_block_fwd(x, w3, s1, b1, wd, sd, bd, w2, s2, b2, True, True)
         ctx.save_for_backward(out1, y, w3, s1, wd, sd, w2, s2)
-        ctx.in_shape = (B, Cin, H, W)
+        ctx.in_shape = tuple(x.shape)
         ctx.set_materialize_grads(False)
         # want_skip: x is handed back as a second output (an alias).  A caller that feeds THAT tensor to x's other consumer
         # (the decoder's skip connection) makes its gradient an input of this node's backward, where K15's epilogue adds it:
@@ -2167,29 +2205,13 @@ class _DownBlockEval(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, g_skip=None):
         out1, y, w3, s1, wd, sd, w2, s2 = ctx.saved_tensors
-        lib = N.lib()
-        B, Cin, H, W = ctx.in_shape
-        Co = w3.shape[0]
         if g is None:           # only the alias was used
             return (g_skip,) + (None,) * 10
         g = _c(g)
         g_skip = None if g_skip is None else _c(g_skip)
-        ones = frozen_memo(("ones", Co, g.device), lambda: torch.ones(Co, device=g.device, dtype=torch.float32))
-        g2 = torch.empty_like(g)            # g * [y > 0]: gradient of bn2's output and of the shortcut's BatchNorm output
-        N.check(_timed("bn_act_bwd", lambda: lib.dmh_bn_act_bwd(N.ptr(y), N.ptr(g), N.ptr(ones), B, Co, (H // 2) * (W // 2), 1,
-                                                               N.ptr(g2), None, N.stream()), 12 * g.numel()))
-        g1 = torch.empty_like(g)            # gradient of bn1's output: conv2's backward-data masked by [out1 > 0]
-        N.check(_timed("wino_conv3x3", lambda: _k10_act(lib, 
-            N.ptr(g2), N.ptr(_wino_filter(w2, True, s2)), None, N.ptr(out1), 2, B, Co, Co, H // 2, W // 2, 1, N.ptr(g1),
-            N.stream()), 4 * 3 * g.numel(), 18 * Co * g.numel()))
-        w3ts = frozen_memo(("down_w3ts", w3.data_ptr(), w3._version, s1.data_ptr()),
-                           lambda: _c((w3 * s1.view(-1, 1, 1, 1)).transpose(0, 1)))
-        wdts = frozen_memo(("down_wdts", wd.data_ptr(), wd._version, sd.data_ptr()),
-                           lambda: _c((wd * sd.view(-1, 1, 1, 1)).reshape(Co, Cin).t()))
-        g_x = torch.empty((B, Cin, H, W), device=g.device, dtype=torch.float32)
-        N.check(_timed("down_conv_bwd", lambda: _k15_bwd(lib, g1, g2, w3ts, wdts, g_skip, B, Cin, Co, H, W, g_x, N.stream()),
-                       4 * (g_x.numel() * (1 if g_skip is None else 2) + 2 * g.numel()), 20 * Cin * g.numel()))
-        return (g_x,) + (None,) * 10
+        g2 = _relu_mask_bwd(y, g)           # gradient of bn2's output and of the shortcut's BatchNorm output
+        g1 = _k10(g2, w2, s2, backward=True, res=out1, flag=2, workspace=True)      # of bn1's output
+        return (_down_block_bwd(g1, g2, g_skip, ctx.in_shape, w3, s1, wd, sd),) + (None,) * 10
 
 
 DOWN_NODE_ENABLED = os.environ.get("DMH_DOWN_NODE", "1") != "0"     # timing comparisons
@@ -2235,26 +2257,19 @@ ROI_ENABLED = os.environ.get("DMH_ROI", "1") != "0"      # A/B switch: 0 = the a
 def _conv_any(x, weight, bias, pad, backward=False):
     """conv2d(x, weight, padding=pad) -- or, with ``backward``, the same filter's backward-data pass on a gradient x with
     pad' = 2 - pad_forward -- on whichever hand-written kernel takes the channel counts; ATen otherwise."""
-    B, n_in, H, W = x.shape
+    _, n_in, H, W = x.shape
     n_out = weight.shape[1] if backward else weight.shape[0]
     Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
     if WINO_ENABLED and x.numel() < (1 << 30):
         if not backward and n_out == 1 and pad == 0 and n_in % 4 == 0:
-            y = torch.empty((B, 1, Ho, Wo), device=x.device, dtype=torch.float32)
-            N.check(_timed("conv3x3_head", lambda: N.lib().dmh_conv3x3_head(
-                N.ptr(x), N.ptr(_c(weight.detach())), N.ptr(bias), B, n_in, H, W, 0, N.ptr(y), N.stream()),
-                4 * (x.numel() + y.numel())))
-            return y
+            return _head_conv(x, weight, bias, 0)
         if backward and n_in == 1 and pad == 2 and n_out % 4 == 0 and n_out <= 64 and Ho >= 3 and Wo >= 3:
-            y = torch.empty((B, n_out, Ho, Wo), device=x.device, dtype=torch.float32)
-            N.check(_timed("conv3x3_head_bwd", lambda: N.lib().dmh_conv3x3_head_bwd_data(
-                N.ptr(x), N.ptr(_c(weight.detach())), B, n_out, Ho, Wo, N.ptr(y), N.stream()), 4 * (x.numel() + y.numel())))
-            return y
+            return _head_conv_bwd(x, weight)
         if _small_ok(n_in, n_out):
             return _small_conv(x, weight, bias, pad, backward)
         if n_in % 8 == 0 and n_in >= 24 and Ho % 2 == 0 and Wo % 2 == 0 and Ho >= 2 and Wo >= 2:
             if n_out % 32 == 0 and n_out % 64 and n_out <= 96:
-                return _wino32_conv(x, _wino32_filter(weight, backward), bias, n_out, pad)
+                return _wino_conv(x, _wino32_filter(weight, backward), bias, n_out, pad, k17=True)
             if n_out >= 64:
                 return _wino_conv(x, _wino_filter(weight, backward), bias, n_out, pad)
     if backward:
@@ -2439,13 +2454,16 @@ def roi_tail_cost(x_top, feats, mask, plan, tab, convs, negate=False):
     return _RoiTail.apply(plan, (depth, -1.0) if negate else depth, _c(x_top), *[_c(f) for f in feats], _c(mask), _c(tab), *wb)
 
 
-def _roi_crop(src, gate, g, org, size):
-    """Compact [B, C, h, w] window of a whole-frame tensor (roi_crop / roi_mask of csrc/roi_encoder.hip)."""
+def _roi_crop(src, gate, g, org, size, frame=None, gate_compact=False):
+    """Compact [B, C, h, w] window (origins ``org``, ``size``) of ``src``, a tensor on a frame of ``frame`` = (H, W) (default: its
+    own size), times [gate > 0] where a gate is given (whole-frame, or ``gate_compact``: itself that window); or, with ``g``
+    (compact) instead of src, g * [gate window > 0]  (roi_crop / roi_mask of csrc/roi_encoder.hip)."""
     ref = src if src is not None else gate
-    B, Cc, H, W = ref.shape
+    B, Cc = ref.shape[:2]
+    H, W = frame if frame is not None else ref.shape[2:]
     out = torch.empty((B, Cc) + tuple(size), device=ref.device, dtype=torch.float32)
     N.check(_timed("roi_crop", lambda: N.lib().dmh_roi_crop(N.ptr(src), N.ptr(gate), N.ptr(g), N.ptr(org), B, Cc, H, W, size[0],
-                                                           size[1], 0, N.ptr(out), N.stream()),
+                                                           size[1], int(gate_compact), N.ptr(out), N.stream()),
                    4 * out.numel() * (2 + (gate is not None))))
     return out
 
@@ -2460,35 +2478,11 @@ class _EncHeadEval(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, plan, tab, w_stem, s0, b0, w1a, s1a, b1a, w2a, s2a, b2a, w1b, s1b, b1b, w2b, s2b, b2b):
-        lib = N.lib()
-        B, _, H, W = x.shape
-        dev = x.device
-        st = N.stream()
-        z = torch.empty((B, 64, H // 2, W // 2), device=dev, dtype=torch.float32)
-        N.check(_timed("stem_conv_fwd", lambda: lib.dmh_stem_conv_norm_fwd(N.ptr(x), N.ptr(_c(w_stem)), B, H, W, 0.45, 0.225,
-                                                                          N.ptr(z), st), 4 * (x.numel() + z.numel()),
-                       2 * 147 * z.numel()))
-        f0 = torch.empty_like(z)
-        pooled = torch.empty((B, 64, H // 4, W // 4), device=dev, dtype=torch.float32)
-        arg = torch.empty((B, 64, H // 4, W // 4), device=dev, dtype=torch.uint8)
-        N.check(_timed("stem_fwd", lambda: lib.dmh_stem_bn_relu_pool_fwd(N.ptr(z), N.ptr(s0), N.ptr(b0), B, 64, H // 2, W // 2,
-                                                                        N.ptr(f0), N.ptr(pooled), N.ptr(arg), st),
-                       4 * (2 * z.numel() + pooled.numel()) + arg.numel()))
-        del z
-
-        def conv_act(inp, w, s, b, res):
-            y = torch.empty_like(inp)
-            N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_act(
-                N.ptr(inp), N.ptr(_wino_filter(w, False, s)), N.ptr(b), N.ptr(res), 1, B, 64, 64, H // 4, W // 4, 1, N.ptr(y), st),
-                4 * (2 + (res is not None)) * inp.numel(), 18 * 64 * inp.numel()))
-            return y
-
-        o1a = conv_act(pooled, w1a, s1a, b1a, None)
-        ya = conv_act(o1a, w2a, s2a, b2a, pooled)
-        o1b = conv_act(ya, w1b, s1b, b1b, None)
-        f1 = conv_act(o1b, w2b, s2b, b2b, ya)
+        f0, pooled, arg = _stem_pool_fwd(_stem_conv_norm_fwd(x, w_stem, 0.45, 0.225), s0, b0)
+        o1a, ya = _block_fwd(pooled, w1a, s1a, b1a, w2a, s2a, b2a, False)
+        o1b, f1 = _block_fwd(ya, w1b, s1b, b1b, w2b, s2b, b2b, False)
         ctx.save_for_backward(f0, arg, s0, o1a, ya, o1b, f1, tab, w_stem, w1a, s1a, w2a, s2a, w1b, s1b, w2b, s2b)
-        ctx.plan, ctx.img = plan, (H, W)
+        ctx.plan, ctx.img = plan, tuple(x.shape[2:])
         ctx.set_materialize_grads(False)
         return f0, f1
 
@@ -2496,42 +2490,23 @@ class _EncHeadEval(torch.autograd.Function):
     def backward(ctx, g_f0, g_f1):
         f0, arg, s0, o1a, ya, o1b, f1, tab, w_stem, w1a, s1a, w2a, s2a, w1b, s1b, w2b, s2b = ctx.saved_tensors
         plan, (H, W) = ctx.plan, ctx.img
-        lib = N.lib()
-        dev = f0.device
         B = f0.shape[0]
-        st = N.stream()
         org = {n: tab[k] for k, n in enumerate(_ROI_NAMES)}
         sz = plan.size
         hq, wq = sz["l1"]
         if g_f1 is None:
-            g_pool = torch.zeros((B, 64, hq, wq), device=dev, dtype=torch.float32)
+            g_pool = torch.zeros((B, 64, hq, wq), device=f0.device, dtype=torch.float32)
         else:
-            def conv_bwd(g, w, s, res, flag):
-                y = torch.empty_like(g)
-                N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_act(
-                    N.ptr(g), N.ptr(_wino_filter(w, True, s)), None, N.ptr(res), flag, B, 64, 64, hq, wq, 1, N.ptr(y), st),
-                    4 * 3 * g.numel(), 18 * 64 * g.numel()))
-                return y
-
             g2b = _roi_crop(_c(g_f1), f1, None, org["l1"], (hq, wq))                    # g * [y_b > 0] on the window
-            g1b = conv_bwd(g2b, w2b, s2b, _roi_crop(o1b, None, None, org["l1"], (hq, wq)), 2)      # ... * [out1_b > 0]
-            g_ya = conv_bwd(g1b, w1b, s1b, g2b, 0)                                      # + the identity branch
+            g_ya = _block_bwd(g2b, _roi_crop(o1b, None, None, org["l1"], (hq, wq)), w1b, s1b, w2b, s2b, False)
             g2a = _roi_crop(None, ya, g_ya, org["l1"], (hq, wq))                        # * [y_a > 0]
-            g1a = conv_bwd(g2a, w2a, s2a, _roi_crop(o1a, None, None, org["l1"], (hq, wq)), 2)
-            g_pool = conv_bwd(g1a, w1a, s1a, g2a, 0)
+            g_pool = _block_bwd(g2a, _roi_crop(o1a, None, None, org["l1"], (hq, wq)), w1a, s1a, w2a, s2a, False)
         hs, ws = sz["gz"]
-        g_z = torch.empty((B, 64, hs, ws), device=dev, dtype=torch.float32)
-        N.check(_timed("stem_bwd_win", lambda: lib.dmh_stem_bn_relu_pool_bwd_win(
+        g_z = torch.empty((B, 64, hs, ws), device=f0.device, dtype=torch.float32)
+        N.check(_timed("stem_bwd_win", lambda: N.lib().dmh_stem_bn_relu_pool_bwd_win(
             N.ptr(f0), N.ptr(arg), N.ptr(None if g_f0 is None else _c(g_f0)), N.ptr(g_pool), N.ptr(s0), N.ptr(org["gz"]),
-            N.ptr(org["l1"]), B, 64, H // 2, W // 2, hs, ws, hq, wq, N.ptr(g_z), st), 4 * 4 * g_z.numel()))
-        w_s = frozen_memo(("stem_w_over_std", w_stem.data_ptr(), w_stem._version, 0.225),
-                          lambda: _c(w_stem.detach() * (1.0 / 0.225)))
-        g_x = torch.zeros((B, 3, H, W), device=dev, dtype=torch.float32)
-        hd, wd = sz["d"]
-        N.check(_timed("stem_conv_bwd_win", lambda: lib.dmh_conv7x7s2_bwd_data_win(
-            N.ptr(g_z), N.ptr(w_s), N.ptr(org["d"]), N.ptr(org["gz"]), B, 64, 3, H, W, hd, wd, hs, ws, N.ptr(g_x), st),
-            4 * (g_z.numel() + B * 3 * hd * wd), 2 * 147 * 64 * B * (hd // 2) * (wd // 2)))
-        return (g_x,) + (None,) * 17
+            N.ptr(org["l1"]), B, 64, H // 2, W // 2, hs, ws, hq, wq, N.ptr(g_z), N.stream()), 4 * 4 * g_z.numel()))
+        return (_stem_window_bwd(g_z, w_stem, org["gz"], org["d"], sz["d"], H, W),) + (None,) * 17
 
 
 def encoder_head_ok(x, conv1_weight, blocks):
@@ -2545,6 +2520,23 @@ def encoder_head_ok(x, conv1_weight, blocks):
             and _wino_ok(B, 64, 64, H // 4, W // 4, allow_split=False) and B * 64 * (H // 4) * (W // 4) < (1 << 30))
 
 
+def _head_plan_ok(x, plan, tab):
+    """The plan and its device table of origins (int32 [len(roi.TABLE), B, 2]) belong to the image batch x."""
+    return (tab.dtype == torch.int32 and tuple(tab.shape) == (len(_ROI_NAMES), x.shape[0], 2) and plan.B == x.shape[0]
+            and (plan.H, plan.W) == tuple(x.shape[2:]))
+
+
+def _head_args(conv1_weight, aff0, *blocks):
+    """The tensor arguments of the head nodes: the stem's (weight, scale, shift), then (weight, scale, shift) per convolution of
+    the blocks, each given as (w, (scale, shift), w, (scale, shift), ...)."""
+    d = lambda t: _c(t.detach())        # noqa: E731
+    args = [d(conv1_weight), d(aff0[0]), d(aff0[1])]
+    for blk in blocks:
+        for w, aff in zip(blk[0::2], blk[1::2]):
+            args += [w.detach(), d(aff[0]), d(aff[1])]
+    return args
+
+
 def encoder_head_eval(x, plan, tab, conv1_weight, aff0, blocks):
     """(feature 0, feature 1) of the ResNet-18 encoder in eval() -- MD2/networks/resnet_encoder.py:88-95: relu(bn1(conv1((x -
     0.45) / 0.225))) and layer1(maxpool(.)) -- as one node whose backward runs on the windows of ``plan`` (see _EncHeadEval):
@@ -2554,15 +2546,10 @@ def encoder_head_eval(x, plan, tab, conv1_weight, aff0, blocks):
     ws = [(b[0], b[2]) for b in blocks]
     if not encoder_head_ok(x, conv1_weight, ws):
         raise RuntimeError("encoder_head_eval: needs ops.frozen_weights() and the ResNet-18 head (ops.encoder_head_ok)")
-    if tab.dtype != torch.int32 or tuple(tab.shape) != (len(_ROI_NAMES), x.shape[0], 2) or plan.B != x.shape[0] or \
-            (plan.H, plan.W) != tuple(x.shape[2:]):
+    if not _head_plan_ok(x, plan, tab):
         raise RuntimeError("encoder_head_eval: plan / origin table do not match the image batch")
-    d = lambda t: _c(t.detach())        # noqa: E731
-    args = [d(conv1_weight), d(aff0[0]), d(aff0[1])]
-    for w1, a1, w2, a2 in blocks:
-        args += [w1.detach(), d(a1[0]), d(a1[1]), w2.detach(), d(a2[0]), d(a2[1])]
     plan.head_windowed = True
-    return _EncHeadEval.apply(_c(x), plan, _c(tab), *args)
+    return _EncHeadEval.apply(_c(x), plan, _c(tab), *_head_args(conv1_weight, aff0, *blocks))
 
 
 class CleanHead(object):
@@ -2644,34 +2631,18 @@ class _EncHeadInc(torch.autograd.Function):
         block (w1, s1, b1, w2, s2, b2) -- evaluated on the plan's "h3" window and returned as a third output."""
         lib = N.lib()
         B, _, H, W = x.shape
-        dev = x.device
         st = N.stream()
         org = {n: tab[k] for k, n in enumerate(_ROI_NAMES)}
         hl, wl = plan.size["hl"]
         hz, wz = 2 * hl, 2 * wl
-        z = torch.empty((B, 64, hz, wz), device=dev, dtype=torch.float32)
+        z = torch.empty((B, 64, hz, wz), device=x.device, dtype=torch.float32)
         N.check(_timed("stem_conv_fwd", lambda: lib.dmh_stem_conv_norm_fwd_win(
             N.ptr(x), N.ptr(_c(w_stem)), N.ptr(org["hz"]), B, H, W, hz, wz, 0.45, 0.225, N.ptr(z), st),
             4 * (z.numel() + 12 * B * hz * wz), 2 * 147 * z.numel()))
-        f0 = torch.empty_like(z)
-        pooled = torch.empty((B, 64, hl, wl), device=dev, dtype=torch.float32)
-        arg = torch.empty((B, 64, hl, wl), device=dev, dtype=torch.uint8)
-        N.check(_timed("stem_fwd", lambda: lib.dmh_stem_bn_relu_pool_fwd(N.ptr(z), N.ptr(s0), N.ptr(b0), B, 64, hz, wz, N.ptr(f0),
-                                                                        N.ptr(pooled), N.ptr(arg), st),
-                       4 * (2 * z.numel() + pooled.numel()) + arg.numel()))
+        f0, pooled, arg = _stem_pool_fwd(z, s0, b0)
         del z
-
-        def conv_act(inp, w, s, b, res):
-            y = torch.empty_like(inp)
-            N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_act(
-                N.ptr(inp), N.ptr(_wino_filter(w, False, s)), N.ptr(b), N.ptr(res), 1, B, 64, 64, hl, wl, 1, N.ptr(y), st),
-                4 * (2 + (res is not None)) * inp.numel(), 18 * 64 * inp.numel()))
-            return y
-
-        o1a = conv_act(pooled, w1a, s1a, b1a, None)
-        ya = conv_act(o1a, w2a, s2a, b2a, pooled)
-        o1b = conv_act(ya, w1b, s1b, b1b, None)
-        f1c = conv_act(o1b, w2b, s2b, b2b, ya)
+        o1a, ya = _block_fwd(pooled, w1a, s1a, b1a, w2a, s2a, b2a, False)
+        o1b, f1c = _block_fwd(ya, w1b, s1b, b1b, w2b, s2b, b2b, False)
         # feature 1 = the clean scenes' feature with the changed cells written in (the clean values return before the next step)
         clean.restore()
         clean.generation += 1
@@ -2690,27 +2661,10 @@ class _EncHeadInc(torch.autograd.Function):
         # ---- layer2 on the "h3" window of the 1/8 map: its input is the "h3in" window of feature 1 as just assembled
         w3, sc1, sh1, wd, scd, shd, w2, sc2, sh2, v1, t1, u1, v2, t2, u2 = l2
         h3, w3_ = plan.size["h3"]
-        x2 = torch.empty((B, 64, 2 * h3, 2 * w3_), device=dev, dtype=torch.float32)
-        N.check(_timed("roi_crop", lambda: lib.dmh_roi_crop(N.ptr(clean.work), None, None, N.ptr(org["h3in"]), B, 64, H // 4,
-                                                           W // 4, 2 * h3, 2 * w3_, 0, N.ptr(x2), st), 8 * x2.numel()))
-        w3s = frozen_memo(("down_w3s", w3.data_ptr(), w3._version, sc1.data_ptr()), lambda: _c(w3 * sc1.view(-1, 1, 1, 1)))
-        wds = frozen_memo(("down_wds", wd.data_ptr(), wd._version, scd.data_ptr()), lambda: _c(wd * scd.view(-1, 1, 1, 1)))
         Co = w3.shape[0]
-        q1 = torch.empty((B, Co, h3, w3_), device=dev, dtype=torch.float32)
-        idt = torch.empty_like(q1)
-        N.check(_timed("down_conv_fwd", lambda: _k15_fwd(lib, x2, w3s, wds, sh1, shd, 1, B, 64, Co, 2 * h3, 2 * w3_, q1, idt, st),
-                       4 * (x2.numel() + 2 * q1.numel()), 20 * 64 * q1.numel()))
-
-        def conv_act2(inp, w, sc, sh, res):
-            y = torch.empty_like(inp)
-            N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_act(
-                N.ptr(inp), N.ptr(_wino_filter(w, False, sc)), N.ptr(sh), N.ptr(res), 1, B, Co, Co, h3, w3_, 1, N.ptr(y), st),
-                4 * (2 + (res is not None)) * inp.numel(), 18 * Co * inp.numel()))
-            return y
-
-        y2a = conv_act2(q1, w2, sc2, sh2, idt)
-        q2 = conv_act2(y2a, v1, t1, u1, None)
-        f2c = conv_act2(q2, v2, t2, u2, y2a)
+        x2 = _roi_crop(clean.work, None, None, org["h3in"], (2 * h3, 2 * w3_), frame=(H // 4, W // 4))
+        q1, y2a = _down_block_fwd(x2, w3, sc1, sh1, wd, scd, shd, w2, sc2, sh2, False, False)
+        q2, f2c = _block_fwd(y2a, v1, t1, u1, v2, t2, u2, False)
         hf, wf = plan.size["f2s"]
         N.check(_timed("roi_paste", lambda: lib.dmh_roi_paste(N.ptr(f2c), N.ptr(org["h3"]), h3, w3_, N.ptr(org["f2s"]), B, Co,
                                                              H // 8, W // 8, hf, wf, N.ptr(clean.work2), st), 8 * B * Co * hf * wf))
@@ -2726,85 +2680,38 @@ class _EncHeadInc(torch.autograd.Function):
         sv = ctx.saved_tensors
         f0, arg, s0, o1a, ya, o1b, f1c, tab, w_stem, w1a, s1a, w2a, s2a, w1b, s1b, w2b, s2b = sv[:17]
         plan, (H, W) = ctx.plan, ctx.img
-        lib = N.lib()
-        dev = f0.device
-        B = f0.shape[0]
-        st = N.stream()
+        B, _, hz, wz = f0.shape
         org = {n: tab[k] for k, n in enumerate(_ROI_NAMES)}
         hl, wl = plan.size["hl"]
-        hz, wz = 2 * hl, 2 * wl
         g_pool = None
         f1_frame, f1_org = (H // 4, W // 4), org["hl"]          # where feature 1's gradient lives: the whole 1/4 map ...
         if ctx.l2 and g_f2 is not None:
             # ---- layer2's backward on "h3": feature 1's gradient comes out as the "h3in" window (which holds "hl")
             q1, y2a, q2, f2c, w3, sc1, wd, scd, w2, sc2, v1, t1, v2, t2 = sv[17:]
             h3, w3_ = plan.size["h3"]
-            Co = w3.shape[0]
-
-            def conv_bwd2(g, w, sc, res, flag):
-                y = torch.empty_like(g)
-                N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_act(
-                    N.ptr(g), N.ptr(_wino_filter(w, True, sc)), None, N.ptr(res), flag, B, Co, Co, h3, w3_, 1, N.ptr(y), st),
-                    4 * 3 * g.numel(), 18 * Co * g.numel()))
-                return y
-
-            gb = torch.empty_like(f2c)                                     # g * [f2 > 0] on the window
-            N.check(_timed("roi_crop", lambda: lib.dmh_roi_crop(N.ptr(_c(g_f2)), N.ptr(f2c), None, N.ptr(org["h3"]), B, Co, H // 8,
-                                                               W // 8, h3, w3_, 1, N.ptr(gb), st), 12 * gb.numel()))
-            g1b = conv_bwd2(gb, v2, t2, q2, 2)
-            g_y2a = conv_bwd2(g1b, v1, t1, gb, 0)
-            g2 = torch.empty_like(g_y2a)                                   # * [y2a > 0]: bn2's output and the shortcut's
-            N.check(_timed("roi_crop", lambda: lib.dmh_roi_crop(None, N.ptr(y2a), N.ptr(g_y2a), N.ptr(org["h3"]), B, Co, H // 8,
-                                                               W // 8, h3, w3_, 1, N.ptr(g2), st), 12 * g2.numel()))
-            g1 = conv_bwd2(g2, w2, sc2, q1, 2)
+            gb = _roi_crop(_c(g_f2), f2c, None, org["h3"], (h3, w3_), frame=(H // 8, W // 8), gate_compact=True)  # g * [f2 > 0]
+            g_y2a = _block_bwd(gb, q2, v1, t1, v2, t2, False)
+            # * [y2a > 0]: bn2's output and the shortcut's
+            g2 = _roi_crop(None, y2a, g_y2a, org["h3"], (h3, w3_), frame=(H // 8, W // 8), gate_compact=True)
+            g1 = _k10(g2, w2, sc2, backward=True, res=q1, flag=2, workspace=False)
             gskip = None
             if g_f1 is not None:            # the decoder's skip gradient, on the same window: added in K15's epilogue
-                gskip = torch.empty((B, 64, 2 * h3, 2 * w3_), device=dev, dtype=torch.float32)
-                N.check(_timed("roi_crop", lambda: lib.dmh_roi_crop(N.ptr(_c(g_f1)), None, None, N.ptr(org["h3in"]), B, 64, H // 4,
-                                                                   W // 4, 2 * h3, 2 * w3_, 0, N.ptr(gskip), st),
-                               8 * gskip.numel()))
-            w3ts = frozen_memo(("down_w3ts", w3.data_ptr(), w3._version, sc1.data_ptr()),
-                               lambda: _c((w3 * sc1.view(-1, 1, 1, 1)).transpose(0, 1)))
-            wdts = frozen_memo(("down_wdts", wd.data_ptr(), wd._version, scd.data_ptr()),
-                               lambda: _c((wd * scd.view(-1, 1, 1, 1)).reshape(Co, 64).t()))
-            g_f1 = torch.empty((B, 64, 2 * h3, 2 * w3_), device=dev, dtype=torch.float32)
-            N.check(_timed("down_conv_bwd", lambda: _k15_bwd(lib, g1, g2, w3ts, wdts, gskip, B, 64, Co, 2 * h3, 2 * w3_, g_f1, st),
-                           4 * (g_f1.numel() * (1 if gskip is None else 2) + 2 * g1.numel()), 20 * 64 * g1.numel()))
+                gskip = _roi_crop(_c(g_f1), None, None, org["h3in"], (2 * h3, 2 * w3_), frame=(H // 4, W // 4))
+            g_f1 = _down_block_bwd(g1, g2, gskip, (B, 64, 2 * h3, 2 * w3_), w3, sc1, wd, scd)
             f1_frame, f1_org = (2 * h3, 2 * w3_), org["hl_rel"]             # ... or that window, "hl" at its relative origin
         if g_f1 is not None:
-            def conv_bwd(g, w, s, res, flag):
-                y = torch.empty_like(g)
-                N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_act(
-                    N.ptr(g), N.ptr(_wino_filter(w, True, s)), None, N.ptr(res), flag, B, 64, 64, hl, wl, 1, N.ptr(y), st),
-                    4 * 3 * g.numel(), 18 * 64 * g.numel()))
-                return y
-
-            g_f1 = _c(g_f1)
-            g2b = torch.empty_like(f1c)                                     # g * [y_b > 0] on the window
-            N.check(_timed("roi_crop", lambda: lib.dmh_roi_crop(N.ptr(g_f1), N.ptr(f1c), None, N.ptr(f1_org), B, 64, f1_frame[0],
-                                                               f1_frame[1], hl, wl, 1, N.ptr(g2b), st), 12 * g2b.numel()))
-            g1b = conv_bwd(g2b, w2b, s2b, o1b, 2)                           # ... * [out1_b > 0]
-            g_ya = conv_bwd(g1b, w1b, s1b, g2b, 0)                          # + the identity branch
-            g2a = torch.empty_like(g_ya)                                    # * [y_a > 0]
-            N.check(_timed("roi_crop", lambda: lib.dmh_roi_crop(None, N.ptr(ya), N.ptr(g_ya), N.ptr(org["hl"]), B, 64, H // 4,
-                                                               W // 4, hl, wl, 1, N.ptr(g2a), st), 12 * g2a.numel()))
-            g1a = conv_bwd(g2a, w2a, s2a, o1a, 2)
-            g_pool = conv_bwd(g1a, w1a, s1a, g2a, 0)
+            g2b = _roi_crop(_c(g_f1), f1c, None, f1_org, (hl, wl), frame=f1_frame, gate_compact=True)   # g * [y_b > 0]
+            g_ya = _block_bwd(g2b, o1b, w1b, s1b, w2b, s2b, False)
+            g2a = _roi_crop(None, ya, g_ya, org["hl"], (hl, wl), frame=(H // 4, W // 4), gate_compact=True)     # * [y_a > 0]
+            g_pool = _block_bwd(g2a, o1a, w1a, s1a, w2a, s2a, False)
         n_in = 19 + (15 if ctx.l2 else 0)
         if g_pool is None and g_f0 is None:
             return (None,) * n_in
         g_z = torch.empty_like(f0)
-        N.check(_timed("stem_bwd", lambda: lib.dmh_stem_bn_relu_pool_bwd(
+        N.check(_timed("stem_bwd", lambda: N.lib().dmh_stem_bn_relu_pool_bwd(
             N.ptr(f0), N.ptr(arg), N.ptr(None if g_f0 is None else _c(g_f0)), N.ptr(g_pool), N.ptr(s0), B, 64, hz, wz, N.ptr(g_z),
-            st), 4 * 4 * g_z.numel()))
-        w_s = frozen_memo(("stem_w_over_std", w_stem.data_ptr(), w_stem._version, 0.225),
-                          lambda: _c(w_stem.detach() * (1.0 / 0.225)))
-        g_x = torch.zeros((B, 3, H, W), device=dev, dtype=torch.float32)
-        hd, wd = plan.size["d"]
-        N.check(_timed("stem_conv_bwd_win", lambda: lib.dmh_conv7x7s2_bwd_data_win(
-            N.ptr(g_z), N.ptr(w_s), N.ptr(org["d"]), N.ptr(org["hz"]), B, 64, 3, H, W, hd, wd, hz, wz, N.ptr(g_x), st),
-            4 * (g_z.numel() + B * 3 * hd * wd), 2 * 147 * 64 * B * (hd // 2) * (wd // 2)))
-        return (g_x,) + (None,) * (n_in - 1)
+            N.stream()), 4 * 4 * g_z.numel()))
+        return (_stem_window_bwd(g_z, w_stem, org["hz"], org["d"], plan.size["d"], H, W),) + (None,) * (n_in - 1)
 
 
 def clean_head(x_clean, conv1_weight, aff0, blocks, layer2=None):
@@ -2846,22 +2753,13 @@ def encoder_head_incremental(x, plan, tab, clean, conv1_weight, aff0, blocks, la
     if not encoder_head_ok(x, conv1_weight, ws) or not plan.head_incremental_ok:
         raise RuntimeError("encoder_head_incremental: needs ops.frozen_weights(), the ResNet-18 head and a plan whose \"hz\" "
                            "window holds what is read of feature 0")
-    if tab.dtype != torch.int32 or tuple(tab.shape) != (len(_ROI_NAMES), x.shape[0], 2) or plan.B != x.shape[0] or \
-            (plan.H, plan.W) != tuple(x.shape[2:]) or tuple(clean.work.shape) != (x.shape[0], 64, x.shape[2] // 4, x.shape[3] // 4):
+    if not _head_plan_ok(x, plan, tab) or tuple(clean.work.shape) != (x.shape[0], 64, x.shape[2] // 4, x.shape[3] // 4):
         raise RuntimeError("encoder_head_incremental: plan / origin table / clean feature do not match the image batch")
-    d = lambda t: _c(t.detach())        # noqa: E731
-    args = [d(conv1_weight), d(aff0[0]), d(aff0[1])]
-    for w1, a1, w2, a2 in blocks:
-        args += [w1.detach(), d(a1[0]), d(a1[1]), w2.detach(), d(a2[0]), d(a2[1])]
-    if layer2 is not None:
-        if not (layer2_incremental_ok(x, layer2) and plan.layer2_incremental_ok and clean.work2 is not None):
-            raise RuntimeError("encoder_head_incremental: layer2 given, but its shapes / the plan's \"h3\" window / the clean "
-                               "feature 2 do not allow the incremental form")
-        (w3, a1, wd, ad, w2, a2), (v1, c1, v2, c2) = layer2
-        args += [w3.detach(), d(a1[0]), d(a1[1]), wd.detach(), d(ad[0]), d(ad[1]), w2.detach(), d(a2[0]), d(a2[1]),
-                 v1.detach(), d(c1[0]), d(c1[1]), v2.detach(), d(c2[0]), d(c2[1])]
+    if layer2 is not None and not (layer2_incremental_ok(x, layer2) and plan.layer2_incremental_ok and clean.work2 is not None):
+        raise RuntimeError("encoder_head_incremental: layer2 given, but its shapes / the plan's \"h3\" window / the clean "
+                           "feature 2 do not allow the incremental form")
     plan.head_windowed = plan.f0_compact = True
-    return _EncHeadInc.apply(_c(x), plan, _c(tab), clean, *args)
+    return _EncHeadInc.apply(_c(x), plan, _c(tab), clean, *_head_args(conv1_weight, aff0, *blocks, *(layer2 or ())))
 
 
 def masked_depth_errors(disp_gt, disp_pred, mask=None, min_depth=0.1, max_depth=100.0, scale=5.4, clamp_lo=1e-3,
@@ -2993,8 +2891,7 @@ def eigen_gt_pack(gt_list, eval_split, device):
     (crop bounds of MD2/evaluate_depth.py:363-364 for split ``eigen``, the whole map otherwise), and per map the number of valid
     pixels and the median of the valid values."""
     device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % device)
+    _need_cuda(device)
     maps = [np.ascontiguousarray(np.asarray(g), dtype=np.float32) for g in gt_list]
     if not maps or any(m.ndim != 2 or m.size == 0 for m in maps):
         raise RuntimeError("eigen_gt_pack: need at least one ground-truth map, all of them 2-D and not empty")
@@ -3110,7 +3007,6 @@ def pose_head(x, invert=False, scale=POSE_SCALE):
     """K29: the pose decoder's tail and transformation_from_parameters in one launch (MD2/networks/pose_decoder.py:47-52,
     MD2/layers.py:28-103).  x [B, 6 nf, h, w] -> (axisangle [B, nf, 1, 3], translation [B, nf, 1, 3], T [B, nf, 4, 4]);
     ``invert``: a bool, or one per frame.  Differentiable w.r.t. x through all three results (one launch)."""
-    if not x.is_cuda:
-        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % x.device)
+    _need_cuda(x)
     _, nf, _, _ = _pose_head_shape(x)
     return _PoseHead.apply(_c(x), pose_invert_mask(invert, nf), float(scale))
