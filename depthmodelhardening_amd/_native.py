@@ -186,6 +186,7 @@ _SIGNATURES = {
     "dmh_stem_conv_norm_fwd_workgroups": (C.c_int, [C.c_int] * 3),
     "dmh_pose_head_fwd": (C.c_int, [_fp] + [C.c_int] * 4 + [C.c_float, C.c_uint32] + [_fp] * 4),
     "dmh_pose_head_bwd": (C.c_int, [_fp] * 5 + [C.c_int] * 4 + [C.c_float, C.c_uint32, _fp, _fp]),
+    "dmh_cost_volume_fwd": (C.c_int, [_fp] * 6 + [C.c_int] * 9 + [_fp] * 7),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

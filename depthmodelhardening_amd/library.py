@@ -30,6 +30,8 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::ssim_map             MD2/layers.py:223-253 SSIM.forward                (K1's window sums, stand-alone)
     dmh::smooth_loss          MD2/layers.py:207-220 get_smooth_loss             (K2 on one scale)
     dmh::pose_head            MD2/networks/pose_decoder.py:47-52 + MD2/layers.py:28-103   (K29) + dmh::pose_head_bwd
+    dmh::cost_volume          manydepth2/networks/resnet_encoder.py:157-236,258-265,294-296   (K30, forward only)
+    dmh::cost_volume_into     the same, cost_volume * confidence written into channels 64 .. of ``buffer``   (K30, in place)
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -662,7 +664,37 @@ def _pose_backward(ctx, g_aa, g_tr, g_T):
 pose_head.register_autograd(_pose_backward, setup_context=_pose_setup)
 
 
+# ----------------------------------------------------------------------------------------------------------------- K30
+# No autograd formula: the reference computes the volume under torch.no_grad(); the outputs carry no gradient.
+@custom_op("dmh::cost_volume", mutates_args=())
+def cost_volume(current_feats: torch.Tensor, lookup_feats: torch.Tensor, poses: torch.Tensor, K: torch.Tensor, invK: torch.Tensor,
+                depth_bins: torch.Tensor, set_missing_to_max: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return ops.cost_volume(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max)
+
+
+@cost_volume.register_fake
+def _(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True):
+    B, _, H, W = current_feats.shape
+    D = depth_bins.shape[0]
+    return (current_feats.new_empty((B, D, H, W)), current_feats.new_empty((B, D, H, W)), current_feats.new_empty((B, H, W)),
+            current_feats.new_empty((B, H, W), dtype=torch.int32))
+
+
+@custom_op("dmh::cost_volume_into", mutates_args=("buffer",))
+def cost_volume_into(current_feats: torch.Tensor, lookup_feats: torch.Tensor, poses: torch.Tensor, K: torch.Tensor,
+                     invK: torch.Tensor, depth_bins: torch.Tensor, buffer: torch.Tensor,
+                     set_missing_to_max: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    return ops.cost_volume(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max, into=buffer)[2:]
+
+
+@cost_volume_into.register_fake
+def _(current_feats, lookup_feats, poses, K, invK, depth_bins, buffer, set_missing_to_max=True):
+    B, _, H, W = current_feats.shape
+    return current_feats.new_empty((B, H, W)), current_feats.new_empty((B, H, W), dtype=torch.int32)
+
+
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
-       "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd")
+       "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
+       "cost_volume", "cost_volume_into")

@@ -3010,3 +3010,70 @@ def pose_head(x, invert=False, scale=POSE_SCALE):
     _need_cuda(x)
     _, nf, _, _ = _pose_head_shape(x)
     return _PoseHead.apply(_c(x), pose_invert_mask(invert, nf), float(scale))
+
+
+# ----------------------------------------------------------------------------------------------------------------- K30
+COST_VOLUME_BANDED = True       # workgroups that share an XCD take a contiguous band of tiles (speed only: same bits either way)
+
+
+def _cost_volume_shapes(current_feats, lookup_feats, poses, K, invK, depth_bins, into=None):
+    """(B, L, Bp, C, H, W, D) of a cost-volume call; every shape mistake is a RuntimeError here, on the host (the reference raises
+    IndexError from its batch loop for the pose ones)."""
+    if current_feats.dim() != 4 or lookup_feats.dim() != 5:
+        raise RuntimeError("cost_volume: current_feats must be [B,C,H,W] and lookup_feats [B,L,C,H,W]; got %s and %s" % (
+            tuple(current_feats.shape), tuple(lookup_feats.shape)))
+    B, C, H, W = current_feats.shape
+    L = lookup_feats.shape[1]
+    if tuple(lookup_feats.shape) != (B, L, C, H, W) or L < 1:
+        raise RuntimeError("cost_volume: lookup_feats %s does not match current_feats %s" % (
+            tuple(lookup_feats.shape), tuple(current_feats.shape)))
+    if poses.dim() != 4 or tuple(poses.shape[2:]) != (4, 4):
+        raise RuntimeError("cost_volume: poses must be [Bp,L,4,4]; got %s" % (tuple(poses.shape),))
+    Bp = poses.shape[0]
+    if poses.shape[1] != L:
+        raise RuntimeError("cost_volume: poses name %d lookup frames, lookup_feats holds %d" % (poses.shape[1], L))
+    if not 1 <= Bp <= B:
+        raise RuntimeError("cost_volume: poses has %d rows for a batch of %d (1 .. B rows; samples beyond them have no lookups)" % (Bp, B))
+    for name, t in (("K", K), ("invK", invK)):
+        if tuple(t.shape) != (B, 4, 4):
+            raise RuntimeError("cost_volume: %s must be [%d,4,4]; got %s" % (name, B, tuple(t.shape)))
+    if depth_bins.dim() != 1 or not 1 <= depth_bins.numel() <= 128:
+        raise RuntimeError("cost_volume: depth_bins must be a vector of 1 .. 128 depths; got %s" % (tuple(depth_bins.shape),))
+    D = depth_bins.numel()
+    if C != 64:
+        raise RuntimeError("cost_volume: %d feature channels; the kernel takes 64 (the layer-1 width of ResNet-18/34)" % C)
+    if H < 5 or W < 5:
+        raise RuntimeError("cost_volume: the matching grid must be at least 5 x 5; got %d x %d" % (H, W))
+    if into is not None and (tuple(into.shape) != (B, C + D, H, W) or not into.is_contiguous() or into.dtype != torch.float32):
+        raise RuntimeError("cost_volume: the buffer must be a contiguous fp32 [%d,%d,%d,%d]" % (B, C + D, H, W))
+    return B, L, Bp, C, H, W, D
+
+
+def cost_volume_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True, into=None, volume=True):
+    B, L, Bp, C, H, W, D = _cost_volume_shapes(current_feats, lookup_feats, poses, K, invK, depth_bins, into)
+    dev = current_feats.device
+    cur, look, poses, K, invK, bins = (_c(t.detach().to(torch.float32)) for t in (current_feats, lookup_feats, poses, K, invK,
+                                                                                   depth_bins))
+    nhwc = torch.empty((B, L, H, W, C), device=dev, dtype=torch.float32)
+    cost = torch.empty((B, D, H, W), device=dev, dtype=torch.float32) if volume else None
+    miss = torch.empty((B, D, H, W), device=dev, dtype=torch.float32) if volume else None
+    conf = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+    idx = torch.empty((B, H, W), device=dev, dtype=torch.int32)
+    nbytes = 4 * (cur.numel() + 3 * look.numel() + (2 * B * D * H * W if volume else 0) + (B * D * H * W if into is not None else 0))
+    N.check(_timed("cost_volume", lambda: N.lib().dmh_cost_volume_fwd(
+        N.ptr(cur), N.ptr(look), N.ptr(poses), N.ptr(K), N.ptr(invK), N.ptr(bins), B, L, Bp, C, H, W, D, int(bool(set_missing_to_max)),
+        int(COST_VOLUME_BANDED), N.ptr(nhwc), N.ptr(cost), N.ptr(miss), N.ptr(conf), N.ptr(idx), N.ptr(into), N.stream()), nbytes))
+    return cost, miss, conf, idx
+
+
+def cost_volume(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True, into=None):
+    """K30: ManyDepth's plane-sweep matching cost volume (manydepth2/networks/resnet_encoder.py:157-236, :258-265, :294-296) as
+    one transposing pass plus one launch, forward only -- the reference computes it under no_grad, and so the results carry no
+    gradient.  current_feats [B,64,H,W], lookup_feats [B,L,64,H,W], poses [Bp,L,4,4] with 1 <= Bp <= B, K / invK [B,4,4],
+    depth_bins [D] (a device vector, D <= 128).  A lookup whose pose sums to exactly 0, and every lookup of a sample b >= Bp, is
+    missing; that is read on the device.  Returns (cost_volume [B,D,H,W], missing_mask [B,D,H,W], confidence_mask [B,H,W],
+    argmin [B,H,W] int32).  ``into`` [B,64+D,H,W]: its channels 64 .. 64+D-1 receive cost_volume * confidence (reduce_conv's
+    input, without the cat and the in-place multiply); the volume and the mask are then not written and come back as None."""
+    for t in (current_feats, lookup_feats, poses, K, invK, depth_bins) + (() if into is None else (into,)):
+        _need_cuda(t)
+    return cost_volume_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max, into, volume=into is None)

@@ -812,6 +812,26 @@ int dmh_pose_head_bwd(const float* g_T, const float* g_axisangle, const float* g
                       const float* translation, int B, int nf, int h, int w, float scale, uint32_t invert_mask, float* g_x,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K30 ManyDepth's matching cost volume, forward only (manydepth2/networks/resnet_encoder.py:157-236 match_features, :258-265
+ *     compute_confidence_mask, :294-296 the argmin of forward).  No backward: the reference computes it under no_grad.
+ *     current[B][C][H][W], lookup[B][L][C][H][W] (layer-1 features), poses[Bp][L][4][4], K / invK[B][4][4], bins[D] (depths).
+ *     Per (b, d, h, w, l): the reference's fp32 position arithmetic without contraction, bilinear sample (zero padding,
+ *     align_corners), mean over channels of |warped - current| times the edge mask and the current frame's border mask; summed
+ *     over the lookups and divided by (count of positive diffs + 1e-7).  Lookup l of sample b is skipped when the 16 entries of
+ *     poses[b][l] sum to exactly 0 or b >= Bp: decided on the device, no host read.
+ *     cost_volume / missing[B][D][H][W] (missing = cost == 0; with set_missing_to_max those entries take the maximum over the
+ *     bins), confidence[B][H][W] (all D bins observed), argmin[B][H][W] (int32; zeros read as 100, first minimum).  cost_volume,
+ *     missing and buffer may be NULL; buffer[B][C + D][H][W] receives cost_volume * confidence in channels C .. C + D - 1.
+ *     nhwc: workspace of B L C H W floats (the lookup features channels-last).  banded != 0: workgroups that share an XCD take a
+ *     contiguous band of tiles (speed only).  C = 64, D <= 128, L <= 16, 1 <= Bp <= B, H, W >= 5, H W C < 2^31.  Two launches,
+ *     no atomics: bitwise reproducible.
+ * ---------------------------------------------------------------------------------- */
+int dmh_cost_volume_fwd(const float* current, const float* lookup, const float* poses, const float* K, const float* invK,
+                        const float* bins, int B, int L, int Bp, int C, int H, int W, int D, int set_missing_to_max, int banded,
+                        float* nhwc, float* cost_volume, float* missing, float* confidence, int32_t* argmin, float* buffer,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
