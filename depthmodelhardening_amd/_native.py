@@ -14,6 +14,7 @@ MAX_FRAMES = 4
 VARIANT_MD2, VARIANT_DH = 0, 1
 NOISE_NONE, NOISE_TENSOR, NOISE_PHILOX = 0, 1, 2
 PASTE_COMPOSITE, PASTE_WARP_ONLY = 0, 1
+PIL_LANCZOS, PIL_BILINEAR, PIL_TILE_ROWS = 1, 2, 8      # PIL.Image.LANCZOS / BILINEAR; DMH_PIL_TILE_ROWS
 FIN_LOSS, FIN_LOSS_S, FIN_REPROJ_S, FIN_COUNT_S, FIN_SMOOTH_S, FIN_HINT_S, FIN_HINTCOUNT_S, FIN_SIZE = 0, 1, 5, 9, 13, 20, 24, 28
 
 LIB_PATH = os.environ.get("DMH_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
@@ -187,6 +188,9 @@ _SIGNATURES = {
     "dmh_pose_head_fwd": (C.c_int, [_fp] + [C.c_int] * 4 + [C.c_float, C.c_uint32] + [_fp] * 4),
     "dmh_pose_head_bwd": (C.c_int, [_fp] * 5 + [C.c_int] * 4 + [C.c_float, C.c_uint32, _fp, _fp]),
     "dmh_cost_volume_fwd": (C.c_int, [_fp] * 6 + [C.c_int] * 9 + [_fp] * 7),
+    "dmh_pil_resample_tables_size": (C.c_int64, [C.c_int] * 3),
+    "dmh_pil_resample": (C.c_int, [_fp, C.c_int] + [C.c_int64] * 4 + [C.c_int, C.c_int, _fp, C.c_int64, _fp, _fp] + [C.c_int] * 5
+                         + [_fp] * 3),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

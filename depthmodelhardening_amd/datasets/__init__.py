@@ -1,3 +1,4 @@
+from .kitti import KITTIRAWDataset, KittiSceneFeed
 from .synthetic import SyntheticEvalSet, SyntheticKITTIDataset, kitti_like, make_object
 
-__all__ = ["SyntheticEvalSet", "SyntheticKITTIDataset", "kitti_like", "make_object"]
+__all__ = ["KITTIRAWDataset", "KittiSceneFeed", "SyntheticEvalSet", "SyntheticKITTIDataset", "kitti_like", "make_object"]

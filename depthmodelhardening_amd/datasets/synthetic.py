@@ -52,30 +52,15 @@ def make_object(device, seed=7, h=260, w=300):
 
 
 class SyntheticKITTIDataset(object):
-    def __init__(self, height, width, frame_idxs, num_scales, length, device, seed=1234, pool=None):
+    def _init_common(self, height, width, frame_idxs, num_scales, length, device, seed):
+        """What every dataset of this interface carries, whatever its frames come from (datasets/kitti.py reads files): sizes,
+        the generator of the per-sample draws, the switches the Trainer sets, the camera.  Draws nothing."""
         self.height, self.width = height, width
         self.frame_idxs, self.num_scales = frame_idxs, num_scales
         self.length, self.device = length, torch.device(device)
         self.ori_H, self.ori_W = ori_H, ori_W
-        self.gen = torch.Generator(device=self.device).manual_seed(seed)
         self.rng = random.Random(seed)
-        self.pool_size = pool or 48
-        raw_left = kitti_like(self.pool_size, 3, ori_H, ori_W, self.device, self.gen)
-        # right view = left rolled 8 px (at 1024 wide) plus independent texture, so photometric error is non-trivial
-        shift = max(2, int(round(8 * ori_W / 1024.0)))
-        raw_right = 0.9 * torch.roll(raw_left, shift, 3) + 0.1 * kitti_like(self.pool_size, 3, ori_H, ori_W, self.device, self.gen)
-        # ONE pool [2 P, 3, 375, 1242]: left frames, then right frames.  The synthesis reads its frames out of it by index
-        # (K3's scene_index) -- no index_select / side-pick copies of 32 full-resolution frames per batch
-        self.raw = torch.cat([raw_left, raw_right], 0).contiguous()
-        self.raw_left, self.raw_right = self.raw[:self.pool_size], self.raw[self.pool_size:]
-        # temporal neighbours (monocular frame ids): {f: [2 P, 3, 375, 1242]}, laid out like self.raw; drawn last
         self.neighbour_ids = [f for f in frame_idxs if isinstance(f, int) and not isinstance(f, bool) and f != 0]
-        self.raw_neighbours = {}
-        for f in self.neighbour_ids:
-            step = max(1, int(round(4 * ori_W / 1024.0))) * f
-            texture = kitti_like(self.pool_size, 3, ori_H, ori_W, self.device, self.gen)
-            self.raw_neighbours[f] = torch.cat([0.9 * torch.roll(raw_left, step, 3) + 0.1 * texture,
-                                                0.9 * torch.roll(raw_right, step, 3) + 0.1 * texture], 0).contiguous()
         self.is_adv_train = False
         self.load_ben_color = False
         self.half_no_synthesis = False
@@ -91,6 +76,26 @@ class SyntheticKITTIDataset(object):
         stereo_T = np.eye(4, dtype=np.float32)
         stereo_T[0, 3] = -1 * 1 * 0.54   # side "l", mono_dataset.py:112-117
         self.stereo_T = stereo_T
+
+    def __init__(self, height, width, frame_idxs, num_scales, length, device, seed=1234, pool=None):
+        self._init_common(height, width, frame_idxs, num_scales, length, device, seed)
+        self.gen = torch.Generator(device=self.device).manual_seed(seed)
+        self.pool_size = pool or 48
+        raw_left = kitti_like(self.pool_size, 3, ori_H, ori_W, self.device, self.gen)
+        # right view = left rolled 8 px (at 1024 wide) plus independent texture, so photometric error is non-trivial
+        shift = max(2, int(round(8 * ori_W / 1024.0)))
+        raw_right = 0.9 * torch.roll(raw_left, shift, 3) + 0.1 * kitti_like(self.pool_size, 3, ori_H, ori_W, self.device, self.gen)
+        # ONE pool [2 P, 3, 375, 1242]: left frames, then right frames.  The synthesis reads its frames out of it by index
+        # (K3's scene_index) -- no index_select / side-pick copies of 32 full-resolution frames per batch
+        self.raw = torch.cat([raw_left, raw_right], 0).contiguous()
+        self.raw_left, self.raw_right = self.raw[:self.pool_size], self.raw[self.pool_size:]
+        # temporal neighbours (monocular frame ids): {f: [2 P, 3, 375, 1242]}, laid out like self.raw; drawn last
+        self.raw_neighbours = {}
+        for f in self.neighbour_ids:
+            step = max(1, int(round(4 * ori_W / 1024.0))) * f
+            texture = kitti_like(self.pool_size, 3, ori_H, ori_W, self.device, self.gen)
+            self.raw_neighbours[f] = torch.cat([0.9 * torch.roll(raw_left, step, 3) + 0.1 * texture,
+                                                0.9 * torch.roll(raw_right, step, 3) + 0.1 * texture], 0).contiguous()
 
     def __len__(self):
         return self.length
@@ -140,17 +145,25 @@ class SyntheticKITTIDataset(object):
         if self.is_adv_train:
             self._epoch_patch = self.obj_img_adv.clone()
 
-    def draw_batch_geometry(self, batch_size):
+    def _draw_first(self, geo):
+        """Draws of a sample that precede do_flip: none here; a file-backed set draws do_color_aug's coin (mono_dataset.py:297)."""
+
+    def _draw_last(self, geo):
+        """Draws of a sample that follow (z0, alpha): none here; a file-backed set draws ColorJitter's parameters (:344-346)."""
+
+    def draw_batch_geometry(self, batch_size, sides=None):
         """Per-sample draws of one batch, in the order ``__getitem__`` makes them (mono_dataset.py:287-288, :297-304,
         then :190-215 inside prep_adv_data): side of the split line, do_flip, synthesis on/off (half_no_synthesis),
-        (z0, alpha)."""
+        (z0, alpha).  ``sides``: the sides of the split lines, where the items come from a list; drawn otherwise."""
         geo = {"side": [], "flip": [], "synth": [], "z0": [], "alpha": []}
-        for _ in range(batch_size):
+        for i in range(batch_size):
+            self._draw_first(geo)
             geo["flip"].append(self.rng.random() > 0.5 if self.flip_augmentation else False)
-            geo["side"].append(self.rng.choice("lr") if self.both_sides else "l")
+            geo["side"].append(sides[i] if sides is not None else (self.rng.choice("lr") if self.both_sides else "l"))
             geo["synth"].append(not self.half_no_synthesis or self.rng.random() > 0.5)
             geo["z0"].append(self.rng.choice(self.adv_trans.dist_range) if self.is_adv_train else 0.0)
             geo["alpha"].append(self.rng.choice(self.adv_trans.angle_range) if self.is_adv_train else 0)
+            self._draw_last(geo)
         return geo
 
     def synthesize(self, raw_l, raw_r, geo, out_size, pool_index=None):

@@ -240,12 +240,19 @@ def main(argv=None):
     else:
         gt_depths = opt.eval_gt_path
         if opt.ext_disp_to_eval is None:
-            if opt.eval_frames_path is None:
-                raise RuntimeError("no KITTI loader here: give --eval_frames_path (an .npy of [N, 3, 320, 1024] frames in [0, 1]) or "
-                                   "--ext_disp_to_eval, or use --dataset synthetic")
-            images = np.load(opt.eval_frames_path, mmap_mode="r")
-            frames = (torch.from_numpy(np.ascontiguousarray(images[i:i + EVAL_BATCH], dtype=np.float32)).to(device)
-                      for i in range(0, images.shape[0], EVAL_BATCH))
+            if opt.eval_frames_path is not None:
+                images = np.load(opt.eval_frames_path, mmap_mode="r")
+                frames = (torch.from_numpy(np.ascontiguousarray(images[i:i + EVAL_BATCH], dtype=np.float32)).to(device)
+                          for i in range(0, images.shape[0], EVAL_BATCH))
+            elif opt.dataset == "kitti":
+                # MD2/evaluate_depth.py:242-251: the test list through KITTIRAWDataset's level 0 (K31), no flip
+                from .datasets.kitti import eval_frames, read_split
+                lines = read_split(os.path.join(opt.split_dir, opt.eval_split, "test_files.txt"))
+                frames = eval_frames(opt.data_path, lines, 320, 1024, device, ".png" if opt.png else ".jpg", EVAL_BATCH,
+                                     opt.num_workers)
+            else:
+                raise RuntimeError("--dataset %s has no loader here: give --eval_frames_path (an .npy of [N, 3, 320, 1024] frames "
+                                   "in [0, 1]) or --ext_disp_to_eval, or use --dataset kitti / synthetic" % opt.dataset)
     if opt.ext_disp_to_eval is None:
         model = import_depth_model((1024, 320), pre_model_path=opt.load_weights_folder).to(device).eval()
         encoder, decoder = model.encoder, model.decoder

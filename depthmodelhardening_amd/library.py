@@ -32,6 +32,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::pose_head            MD2/networks/pose_decoder.py:47-52 + MD2/layers.py:28-103   (K29) + dmh::pose_head_bwd
     dmh::cost_volume          manydepth2/networks/resnet_encoder.py:157-236,258-265,294-296   (K30, forward only)
     dmh::cost_volume_into     the same, cost_volume * confidence written into channels 64 .. of ``buffer``   (K30, in place)
+    dmh::pil_resample         MD2/datasets/mono_dataset.py:100-104,119-144 (PIL.Image.resize, 8-bit, bit for bit)   (K31, no autograd)
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -693,8 +694,25 @@ def _(current_feats, lookup_feats, poses, K, invK, depth_bins, buffer, set_missi
     return current_feats.new_empty((B, H, W)), current_feats.new_empty((B, H, W), dtype=torch.int32)
 
 
+# ---------------------------------------------------------------------------------------------------------------- K31
+@custom_op("dmh::pil_resample", mutates_args=())
+def pil_resample(src: torch.Tensor, out_h: int, out_w: int, filter: str = "lanczos", flip: Optional[torch.Tensor] = None,
+                 sizes: Optional[List[int]] = None, hwc: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(uint8 [N, C, out_h, out_w], the same as float32 / 255).  ``sizes``: h0, w0, h1, w1, ... of the images in their slots;
+    ``hwc``: a uint8 source is [N, H, W, C].  Images carry no gradient: there is no autograd formula."""
+    pairs = None if sizes is None else list(zip(sizes[0::2], sizes[1::2]))
+    ops._need_cuda(src)
+    return tuple(ops.pil_resize(src, (out_h, out_w), filter, flip, pairs, True, "hwc" if hwc else "chw"))
+
+
+@pil_resample.register_fake
+def _(src, out_h, out_w, filter="lanczos", flip=None, sizes=None, hwc=False):
+    shape = (src.shape[0], src.shape[3] if hwc else src.shape[1], out_h, out_w)
+    return src.new_empty(shape, dtype=torch.uint8), src.new_empty(shape, dtype=torch.float32)
+
+
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
-       "cost_volume", "cost_volume_into")
+       "cost_volume", "cost_volume_into", "pil_resample")

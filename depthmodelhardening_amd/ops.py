@@ -7,7 +7,7 @@ below is one or a few launches of hand-written gfx950 kernels through the C ABI
 import contextlib
 import ctypes as C
 import os
-from collections import namedtuple
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -3077,3 +3077,281 @@ def cost_volume(current_feats, lookup_feats, poses, K, invK, depth_bins, set_mis
     for t in (current_feats, lookup_feats, poses, K, invK, depth_bins) + (() if into is None else (into,)):
         _need_cuda(t)
     return cost_volume_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max, into, volume=into is None)
+
+
+# ----------------------------------------------------------------------------------------------------------------- K31
+PIL_FILTERS = {"lanczos": (N.PIL_LANCZOS, 3.0), "bilinear": (N.PIL_BILINEAR, 1.0)}      # name -> (PIL's number, support)
+PIL_PRECISION_BITS = 22
+PilLevel = namedtuple("PilLevel", ["u8", "f32"])
+_pil_axis_cache = {}
+_pil_device_cache = OrderedDict()      # (device, sizes, out, filter) -> descriptors on the device; bounded, see PIL_DESC_CACHE
+
+
+def _pil_filter(filter):
+    try:
+        return PIL_FILTERS[str(filter).lower()]
+    except KeyError:
+        raise RuntimeError("pil_resize: filter must be one of %s; got %r" % (sorted(PIL_FILTERS), filter))
+
+
+def _pil_weight(x, support):
+    """Pillow's filter functions (Resample.c: bilinear_filter; lanczos_filter = sinc(x) sinc(x / 3) on [-3, 3)) on Python
+    floats: ``math.sin`` is the C library's, as Pillow's is."""
+    import math
+    if support == 1.0:
+        x = -x if x < 0.0 else x
+        return 1.0 - x if x < 1.0 else 0.0
+    if not -3.0 <= x < 3.0:
+        return 0.0
+
+    def sinc(v):
+        if v == 0.0:
+            return 1.0
+        v = v * math.pi
+        return math.sin(v) / v
+    return sinc(x) * sinc(x / 3)
+
+
+def pil_axis_table(in_size, out_size, filter="lanczos"):
+    """Host: Pillow's coefficients of one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc) for ``in_size`` ->
+    ``out_size``: (xmin int32 [out], count int32 [out], k int32 [out, ksize]).  float64 in Pillow's order -- the taps
+    ``filter((x + xmin - center + 0.5) * (1 / filterscale))`` summed by index, each divided by the sum -- then integers with 22
+    fraction bits, rounded half away from zero.  Equal sizes give the pass Pillow skips as the table (x, 1, 2^22).  Cached."""
+    in_size, out_size = int(in_size), int(out_size)
+    number, support0 = _pil_filter(filter)
+    if not (0 < in_size < (1 << 20) and 0 < out_size < (1 << 20)):
+        raise RuntimeError("pil_axis_table: sizes must be in [1, 2^20); got %d -> %d" % (in_size, out_size))
+    key = (in_size, out_size, number)
+    hit = _pil_axis_cache.get(key)
+    if hit is not None:
+        return hit
+    if in_size == out_size:
+        tab = (np.arange(out_size, dtype=np.int32), np.ones(out_size, dtype=np.int32),
+               np.full((out_size, 1), 1 << PIL_PRECISION_BITS, dtype=np.int32))
+    else:
+        import math
+        scale = in_size / out_size
+        filterscale = max(scale, 1.0)
+        support = support0 * filterscale
+        ksize = int(math.ceil(support)) * 2 + 1
+        ss = 1.0 / filterscale
+        xmins, counts = np.zeros(out_size, dtype=np.int32), np.zeros(out_size, dtype=np.int32)
+        k = np.zeros((out_size, ksize), dtype=np.int32)
+        one = float(1 << PIL_PRECISION_BITS)
+        for xx in range(out_size):
+            center = (xx + 0.5) * scale
+            xmin = max(int(center - support + 0.5), 0)
+            xmax = min(int(center + support + 0.5), in_size) - xmin
+            w = [_pil_weight((x + xmin - center + 0.5) * ss, support0) for x in range(xmax)]
+            ww = 0.0
+            for v in w:
+                ww += v
+            if ww != 0.0:
+                w = [v / ww for v in w]
+            xmins[xx], counts[xx] = xmin, xmax
+            k[xx, :xmax] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+        tab = (xmins, counts, k)
+    for a in tab:
+        a.setflags(write=False)
+    _pil_axis_cache[key] = tab
+    return tab
+
+
+def _pil_pass_host(a, table, sums=None):
+    """One pass of Pillow's 8-bit resample along the last axis of uint8 ``a``: clip((2^21 + sum(p k)) >> 22, 0, 255) in int32.
+    ``sums`` (a list) receives the sums before the shift and the clip."""
+    xmin, count, k = table
+    idx = np.minimum(xmin[:, None] + np.arange(k.shape[1])[None, :], a.shape[-1] - 1)      # taps past ``count`` weigh 0
+    acc = (a[..., idx].astype(np.int32) * k).sum(-1, dtype=np.int32) + np.int32(1 << (PIL_PRECISION_BITS - 1))
+    if sums is not None:
+        sums.append(acc)
+    return np.clip(acc >> PIL_PRECISION_BITS, 0, 255).astype(np.uint8)
+
+
+def pil_quantize_host(x):
+    """torchvision's ``ToPILImage`` on a float tensor: ``pic.mul(255).byte()``, a truncation in fp32."""
+    return (np.asarray(x, dtype=np.float32) * np.float32(255.0)).astype(np.uint8)
+
+
+def pil_resize_host(img, out_size, filter="lanczos", flip=False, sums=None):
+    """Host twin of K31 in numpy: ``PIL.Image.fromarray(img).resize((out_w, out_h), filter)`` of uint8 ``img`` [..., H, W]
+    (planar: leading axes are channels or a batch), bit-equal to Pillow's.  ``flip``: transpose(FLIP_LEFT_RIGHT) first.  The
+    horizontal pass runs first into an 8-bit intermediate; a pass whose size does not change is skipped."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim < 2:
+        raise RuntimeError("pil_resize_host: need a uint8 array [..., H, W]; got %s %s" % (img.dtype, img.shape))
+    oh, ow = (int(v) for v in out_size)
+    if flip:
+        img = img[..., ::-1]
+    H, W = img.shape[-2:]
+    if W != ow:
+        img = _pil_pass_host(img, pil_axis_table(W, ow, filter), sums)
+    if H != oh:
+        img = np.swapaxes(_pil_pass_host(np.swapaxes(img, -1, -2), pil_axis_table(H, oh, filter), sums), -1, -2)
+    return np.ascontiguousarray(img)
+
+
+PIL_DESC_CACHE = 64         # descriptor sets kept per process (a few hundred bytes each); the tables themselves are never repeated
+
+
+class _PilArena(object):
+    """The axis tables of one device: one int32 tensor that holds every distinct (in, out, filter) table once, at a word offset
+    that never changes.  KITTI raw has about five frame sizes, so the arena stops growing after the first batches; when a new
+    table arrives the whole arena is uploaded again (pinned, asynchronous) and the upload is waited for once, so that any stream
+    may read it afterwards."""
+
+    def __init__(self, device):
+        self.device, self.entries, self.words, self.tables = device, {}, [], None
+        self.tile_rows = {}
+
+    def place(self, n_in, n_out, number, filter):
+        """(word offset, ksize) of the table; ``self.tables`` is stale until ``sync`` when this added one."""
+        key = (n_in, n_out, number)
+        if key not in self.entries:
+            xmin, count, k = pil_axis_table(n_in, n_out, filter)
+            flat = np.concatenate([xmin, count, np.ascontiguousarray(k.T).reshape(-1)])
+            want = N.lib().dmh_pil_resample_tables_size(n_in, n_out, number)
+            if want != flat.size:
+                raise RuntimeError("pil_resize: the table of %d -> %d has %d words, the library expects %d" % (n_in, n_out, flat.size, want))
+            self.entries[key] = (sum(w.size for w in self.words), k.shape[1])
+            self.words.append(flat)
+            self.tables = None
+        return self.entries[key]
+
+    def rows(self, h, oh, filter, number):
+        """The most source rows one tile of PIL_TILE_ROWS output rows needs on the vertical axis h -> oh."""
+        key = (h, oh, number)
+        if key not in self.tile_rows:
+            tile = N.PIL_TILE_ROWS
+            ymin, count, _ = pil_axis_table(h, oh, filter)
+            last_i = np.minimum(np.arange(tile - 1, oh + tile - 1, tile), oh - 1)
+            self.tile_rows[key] = int((ymin[last_i] + count[last_i] - ymin[::tile]).max())
+        return self.tile_rows[key]
+
+    def sync(self):
+        if self.tables is None:
+            host = torch.from_numpy(np.concatenate(self.words)).pin_memory()
+            self.tables = host.to(self.device, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self.device))
+            done.synchronize()          # once per new table: later calls, on any stream, read a finished upload
+        return self.tables
+
+
+_pil_arenas = {}
+_pil_graph_keys = set()     # descriptor sets a captured graph has launched with: a replay reads them, so they are never evicted
+
+
+def _pil_tables_device(device, sizes, oh, ow, number, filter):
+    """(tables int32 [words], desc int32 [N, 8], lds_rows) on ``device`` for a batch whose images have the source sizes
+    ``sizes`` (a tuple of (h, w)).  The tables live once per distinct (in, out, filter) in the device's arena; what depends on
+    the batch is the descriptor set alone (32 bytes per image), uploaded from pinned memory without a wait.  The last
+    PIL_DESC_CACHE descriptor sets are kept, with the event of their upload, so that a repeated batch shape -- a captured graph's,
+    a pyramid's coarser levels -- launches with the same device buffer and no copy."""
+    arena = _pil_arenas.get(str(device))
+    if arena is None:
+        arena = _pil_arenas[str(device)] = _PilArena(device)
+    key = (str(device), sizes, oh, ow, number)
+    hit = _pil_device_cache.get(key)
+    if hit is not None:
+        _pil_device_cache.move_to_end(key)
+        desc_d, lds_rows, uploaded, _ = hit
+        if torch.cuda.is_current_stream_capturing():
+            _pil_graph_keys.add(key)
+        elif not uploaded.query():
+            torch.cuda.current_stream(device).wait_event(uploaded)      # uploaded on another stream a moment ago
+        return arena.sync(), desc_d, lds_rows
+    desc, lds_rows = np.zeros((len(sizes), 8), dtype=np.int32), 1
+    for i, (h, w) in enumerate(sizes):
+        (ho, hk), (vo, vk) = arena.place(w, ow, number, filter), arena.place(h, oh, number, filter)
+        desc[i, :6] = (h, w, ho, hk, vo, vk)
+        lds_rows = max(lds_rows, arena.rows(h, oh, filter, number))
+    if lds_rows * ow > 65536:
+        raise RuntimeError("pil_resize: %d source rows of %d output columns per tile exceed the 64 KiB LDS tile; resize in two "
+                           "steps" % (lds_rows, ow))
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("pil_resize: the first call with these source sizes uploads their descriptors; make it once before "
+                           "capturing a graph")
+    tables = arena.sync()
+    host = torch.from_numpy(desc.reshape(-1)).pin_memory()
+    desc_d = host.to(device, non_blocking=True).view(-1, 8)
+    uploaded = torch.cuda.Event()
+    uploaded.record(torch.cuda.current_stream(device))
+    _pil_device_cache[key] = (desc_d, lds_rows, uploaded, host)     # the pinned copy lives as long as the upload may
+    for old in [k for k in _pil_device_cache if k not in _pil_graph_keys][:max(0, len(_pil_device_cache) - PIL_DESC_CACHE)]:
+        del _pil_device_cache[old]
+    return tables, desc_d, lds_rows
+
+
+def _pil_sizes(sizes, n, H, W):
+    if sizes is None:
+        return ((H, W),) * n
+    sizes = tuple((int(h), int(w)) for h, w in (sizes.tolist() if hasattr(sizes, "tolist") else sizes))
+    if len(sizes) != n or not all(0 < h <= H and 0 < w <= W for h, w in sizes):
+        raise RuntimeError("pil_resize: sizes must be %d pairs (h, w) within the buffer's %d x %d; got %s" % (n, H, W, sizes))
+    return sizes
+
+
+def pil_resize(src, out_size, filter="lanczos", flip=None, sizes=None, want_float=True, layout=None, want_u8=True):
+    """K31: ``PIL.Image.resize((out_w, out_h), filter)`` of a batch of 8-bit images, bit for bit, in one launch.
+
+    src      uint8 [N, H, W, C] (``layout="hwc"``, the default for uint8: decoded files), uint8 [N, C, H, W]
+             (``layout="chw"``: a previous level), or float32 [N, C, H, W] in [0, 1], quantised on read as ToPILImage does.
+    sizes    per image (h, w) <= (H, W): the image lies in the top-left corner of its slot (host values: they choose the tables).
+    flip     per image, a device int32 [N] (or a host sequence of bools): != 0 resizes transpose(FLIP_LEFT_RIGHT) of the image.
+    Returns  PilLevel(u8 uint8 [N, C, out_h, out_w] or None, f32 = u8.float() / 255 or None).
+
+    CPU tensors run the numpy restatement of the same integers (``pil_resize_host``)."""
+    number, _ = _pil_filter(filter)
+    oh, ow = (int(v) for v in out_size)
+    if oh < 1 or ow < 1:
+        raise RuntimeError("pil_resize: out_size must be positive; got %s" % (tuple(out_size),))
+    if src.dim() != 4 or src.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError("pil_resize: src must be uint8 or float32 with 4 dimensions; got %s %s" % (src.dtype, tuple(src.shape)))
+    if not (want_float or want_u8):
+        raise RuntimeError("pil_resize: nothing to return (want_float and want_u8 are both off)")
+    layout = layout or ("hwc" if src.dtype == torch.uint8 else "chw")
+    if layout not in ("hwc", "chw") or (src.dtype == torch.float32 and layout != "chw"):
+        raise RuntimeError("pil_resize: layout must be 'hwc' or 'chw' (float32 sources are 'chw'); got %r" % (layout,))
+    n, (H, W, C_) = int(src.shape[0]), ((int(v) for v in src.shape[1:]) if layout == "hwc" else (int(src.shape[2]), int(src.shape[3]), int(src.shape[1])))
+    sizes = _pil_sizes(sizes, n, H, W)
+    if src.device.type != "cuda":
+        planar = src.permute(0, 3, 1, 2) if layout == "hwc" else src
+        planar = planar.numpy() if src.dtype == torch.uint8 else pil_quantize_host(planar.numpy())
+        flips = [False] * n if flip is None else [bool(v) for v in (flip.tolist() if hasattr(flip, "tolist") else flip)]
+        if len(flips) != n:
+            raise RuntimeError("pil_resize: flip must have one entry per image")
+        u8 = torch.from_numpy(np.stack([pil_resize_host(planar[i, :, :h, :w], (oh, ow), filter, flips[i])
+                                        for i, (h, w) in enumerate(sizes)]))
+        return PilLevel(u8 if want_u8 else None, u8.float().div(255) if want_float else None)
+    src = _c(src)
+    dev = src.device
+    if flip is not None and not torch.is_tensor(flip):
+        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    if flip is not None and (flip.dtype != torch.int32 or flip.numel() != n or flip.device != dev):
+        raise RuntimeError("pil_resize: flip must be an int32 tensor of %d entries on %s" % (n, dev))
+    tables, desc, lds_rows = _pil_tables_device(dev, sizes, oh, ow, number, filter)
+    u8 = torch.empty((n, C_, oh, ow), device=dev, dtype=torch.uint8) if want_u8 else None
+    f32 = torch.empty((n, C_, oh, ow), device=dev, dtype=torch.float32) if want_float else None
+    strides = (H * W * C_, 1, W * C_, C_) if layout == "hwc" else (C_ * H * W, H * W, W, 1)
+    N.check(_timed("pil_resample", lambda: N.lib().dmh_pil_resample(
+        N.ptr(src), int(src.dtype == torch.float32), *strides, H, W, N.ptr(tables), int(tables.numel()), N.ptr(desc),
+        N.ptr(None if flip is None else _c(flip)), n, C_, oh, ow, lds_rows, N.ptr(u8), N.ptr(f32), N.stream()),
+        src.numel() * src.element_size() + n * C_ * oh * ow * (int(want_u8) + 4 * int(want_float))))
+    return PilLevel(u8, f32)
+
+
+def pil_pyramid(src, height, width, num_scales=4, filter="lanczos", flip=None, sizes=None, want_float=True, layout=None):
+    """The loader's image pyramid (MD2/datasets/mono_dataset.py:100-104,119-144): level 0 is ``src`` resized to height x width,
+    level i the 8-bit level i - 1 resized to (height // 2^i) x (width // 2^i) -- one launch of K31 per level.  ``flip`` applies to
+    level 0 (the reference flips the loaded image).  Returns ``num_scales`` PilLevel(u8, f32)."""
+    levels = []
+    for i in range(int(num_scales)):
+        s = 2 ** i
+        if height // s < 1 or width // s < 1:
+            raise RuntimeError("pil_pyramid: level %d of %d x %d is empty" % (i, height, width))
+        if i == 0:
+            levels.append(pil_resize(src, (height, width), filter, flip, sizes, want_float, layout))
+        else:
+            levels.append(pil_resize(levels[-1].u8, (height // s, width // s), filter, None, None, want_float, "chw"))
+    return levels

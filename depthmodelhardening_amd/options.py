@@ -89,6 +89,16 @@ class MonodepthOptions:
                        help="md2 = MD2/trainer.py:647-660; dh = DepthHints normalisation, DH/trainer.py:700-708")
         p.add_argument("--synthetic_len", type=int, default=64, help="items per epoch of --dataset synthetic")
         p.add_argument("--seed", type=int, default=1234)
+        p.add_argument("--split_dir", type=str, default=os.path.join(file_dir, "splits"),
+                       help="--dataset kitti: the folder holding <split>/train_files.txt and val_files.txt and <eval_split>/"
+                            "test_files.txt -- Monodepth2's lists, which the user brings (none ships with this repository)")
+        p.add_argument("--scene_root", type=str,
+                       help="--dataset kitti with --adv_train: the attack's scenes (dataLoader.py:107-209), a folder with "
+                            "vehicle_detection/training.txt and training/image_2/*.png of at least 375 x 1242")
+        p.add_argument("--kitti_preprocess", type=str, default="reference", choices=["reference", "fast"],
+                       help="--dataset kitti: reference = the loader's PIL chain on the device, bit for bit (K31: LANCZOS levels "
+                            "from 8-bit levels, the 8-bit round trip of the pasted frames); fast = the synthetic set's path fed "
+                            "from files (bilinear resize inside the paste, box-mean levels): NOT the reference's pixels")
         p.add_argument("--eval_gt_path", type=str,
                        help="evaluate_depth: the ground truth, an .npz with the object array ``data`` of 2-D maps (the reference "
                             "reads splits/<eval_split>/gt_depths.npz); default with --dataset synthetic: made-up LiDAR-like maps")

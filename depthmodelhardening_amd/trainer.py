@@ -271,12 +271,15 @@ class Trainer:
             self.load_model()
 
         # data
-        if self.opt.dataset != "synthetic":
-            raise NotImplementedError("KITTI file loaders are outside the hot-path scope (SURVEY.md section 2, rows "
-                                      "12-13); use --dataset synthetic")
-        self.dataset = SyntheticKITTIDataset(self.opt.height, self.opt.width, self.opt.frame_ids, 4,
-                                             self.opt.synthetic_len, self.device, seed=self.opt.seed + rank)
-        self.dataset.both_sides = self.dataset.flip_augmentation = not self.opt.no_flip_sides
+        if self.opt.dataset == "kitti":
+            self.dataset = self._kitti_dataset(rank)
+        elif self.opt.dataset != "synthetic":
+            raise NotImplementedError("--dataset %s: only KITTI raw (kitti) is read from disk; kitti_odom, kitti_depth and "
+                                      "kitti_test have no loader here" % self.opt.dataset)
+        else:
+            self.dataset = SyntheticKITTIDataset(self.opt.height, self.opt.width, self.opt.frame_ids, 4,
+                                                 self.opt.synthetic_len, self.device, seed=self.opt.seed + rank)
+            self.dataset.both_sides = self.dataset.flip_augmentation = not self.opt.no_flip_sides
         self.dataset.reference_stale_patch = bool(self.opt.reference_stale_patch)
         self.dataset.make_depth_hints = bool(self.opt.use_depth_hints)
         self.dataset.right_pyramid = bool(self.opt.v1_multiscale)
@@ -336,6 +339,11 @@ class Trainer:
                     break
         finally:
             self.step_log.close()       # writes the last iteration's line
+
+    def _kitti_dataset(self, rank):
+        """MD2/trainer.py:162-181: KITTIRAWDataset on <split_dir>/<split>/train_files.txt; len(dataset) is the list's length."""
+        from .datasets.kitti import from_options
+        return from_options(self.opt, self.device, rank)
 
     def update_adv_obj(self):
         """dataset.update_adv_obj on this iteration's attack scenes (MD2/trainer.py:300-307): --atk_batch_size scenes per

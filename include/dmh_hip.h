@@ -832,6 +832,33 @@ int dmh_cost_volume_fwd(const float* current, const float* lookup, const float* 
                         float* nhwc, float* cost_volume, float* missing, float* confidence, int32_t* argmin, float* buffer,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K31 Pillow's 8-bit separable resample, Image.resize(size, filter) of mode RGB / L with reducing_gap=None, bit for bit
+ *     (MD2/datasets/mono_dataset.py:100-104,119-144: the loader's four-level ANTIALIAS chain).  One launch per level: a
+ *     workgroup takes DMH_PIL_TILE_ROWS output rows of one channel of one image, runs the horizontal pass for the source rows
+ *     those need into an 8-bit LDS tile (``lds_rows`` rows of W_out bytes), then the vertical pass from the tile.  Integer
+ *     arithmetic only: pixel = clip((2^21 + sum(p * k)) >> 22, 0, 255) per pass, Pillow's own 32-bit sums.
+ *     tables: int32 words, every axis table laid out as min[out] | count[out] | k[ksize][out] (k has 22 fraction bits; a pass
+ *     whose size does not change is the table with ksize 1 and k = 2^22, which reproduces the pixel).  They are made on the
+ *     host in float64 (ops.pil_axis_table); dmh_pil_resample_tables_size(in, out, filter) is the word count of one table, -1
+ *     for sizes it does not take.  filter: DMH_PIL_BILINEAR (support 1) or DMH_PIL_LANCZOS (support 3).
+ *     desc: int32 [N][8] per image = source rows, source columns, word offset and ksize of its horizontal table, word offset and
+ *     ksize of its vertical table, 0, 0.  flip (int32 [N], may be NULL): != 0 mirrors the read of the source column, which is
+ *     transpose(FLIP_LEFT_RIGHT) before the resize.
+ *     src: element (n, c, y, x) at n sn + c sc + y sy + x sx (elements), uint8, or float32 when src_f32 != 0, quantised on read
+ *     as ToPILImage does: (uint8)(v * 255.f).  Hs, Ws: the rows and columns the buffer holds per image (every image's own size
+ *     is <= them; reads are clamped to them).
+ *     out_u8 [N][C][H_out][W_out] and out_f32 = (float)u8 / 255.f (IEEE division) of the same shape; either may be NULL, not both.
+ *     N, C <= 65535, every buffer < 2^31 elements, lds_rows W_out <= 65536.  No atomics, no host read; bitwise reproducible.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_PIL_BILINEAR 2
+#define DMH_PIL_LANCZOS 1
+#define DMH_PIL_TILE_ROWS 8
+int64_t dmh_pil_resample_tables_size(int in_size, int out_size, int filter);
+int dmh_pil_resample(const void* src, int src_f32, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Hs, int Ws,
+                     const int32_t* tables, int64_t table_words, const int32_t* desc, const int32_t* flip, int N, int C,
+                     int H_out, int W_out, int lds_rows, uint8_t* out_u8, float* out_f32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
