@@ -191,6 +191,9 @@ _SIGNATURES = {
     "dmh_pil_resample_tables_size": (C.c_int64, [C.c_int] * 3),
     "dmh_pil_resample": (C.c_int, [_fp, C.c_int] + [C.c_int64] * 4 + [C.c_int, C.c_int, _fp, C.c_int64, _fp, _fp] + [C.c_int] * 5
                          + [_fp] * 3),
+    "dmh_velo_depth_ws_size": (C.c_int64, [C.c_int64, C.c_int64]),
+    "dmh_velo_depth_map": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                     _fp, _fp, _fp]),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

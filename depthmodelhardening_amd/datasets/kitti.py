@@ -21,12 +21,18 @@ resized by F.interpolate, the coarse levels are 2^s box means.  Not the referenc
 
 Departures, stated: ColorJitter (only with ``color_aug``, for half of the samples, mono_dataset.py:297,344-348) is applied to the
 float level 0 with color_jitter.py's tensor operations, not to the 8-bit PIL image, and the coarser ``color_aug`` levels are not
-built (nothing reads them).  ``depth_gt`` from velodyne points is not built: ``load_depth`` is False.  Under
+built (nothing reads them).  Under
 ``half_no_synthesis`` the samples without an object take the float round trip of the others, which returns every byte
 ((v / 255.f) * 255.f truncates to v for all 256 values: tests/test_pil_resample_ref.py).  The reference pins Pillow
 5.4.1; K31 is held to the Pillow that is installed (12.x), whose 8-bit resample is believed, not checked, to round the same way.
 
-PIL is imported here and nowhere else in the package, when a file is first decoded.
+``depth_gt`` (kitti_dataset.py:70-85): when the scan of the first split line exists (``check_depth``), the scans of a batch are read
+by the same pool with ``np.fromfile`` into a pinned float32 buffer [points, 4], ragged, the offsets from the file sizes, uploaded with
+the frames; ``ops.velo_depth_map`` (K32) projects them with the camera of the split line's side, resizes to ``full_res_shape`` and
+mirrors the flipped samples -> inputs["depth_gt"] [B, 1, 375, 1242].  The resize is K32's integer nearest rule, not
+scikit-image 0.17.2's fitted affine map.
+
+PIL is imported here (and by export_gt_depth's PNG branch) and nowhere else in the package, when a file is first decoded.
 """
 import os
 import random
@@ -38,6 +44,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import color_jitter, ops
+from . import kitti_velo
 from ..my_utils import ori_H, ori_W, to_device_async
 from .synthetic import SyntheticKITTIDataset
 
@@ -114,25 +121,58 @@ class _Prefetcher(object):
         self.consumed = [None, None]     # event: the kernels that read the device buffer have been queued before it
         self.pending = {}
         self.wait_s = 0.0                # time the consuming thread spent waiting for a batch that was not ready
+        # velodyne scans: per buffer a pinned float32 [capacity, 4] and int32 offsets, their device twins; grown on demand
+        self.cloud_host, self.cloud_dev = [None, None], [None, None]
+        self.clouds = [None, None]       # (device points [total, 4], device offsets int32 [n + 1]) of the buffer's batch
 
-    def _load(self, k, paths):
+    def _load_clouds(self, b, velo):
+        """The scans ``velo`` into buffer b: ragged, offsets from the file sizes.  Runs after the buffer's last upload finished."""
+        counts = [kitti_velo.cloud_points(p) for p in velo]
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        total, n = int(offsets[-1]), len(velo)
+        host = self.cloud_host[b]
+        if host is None or host[0].shape[0] < total or host[1].numel() < n + 1:
+            if self.cuda and self.consumed[b] is not None:
+                self.consumed[b].synchronize()      # the kernels that read the old device buffer have run
+            cap = max(total + total // 4, 1)
+            host = self.cloud_host[b] = (torch.empty((cap, 4), dtype=torch.float32, pin_memory=self.cuda),
+                                         torch.empty(n + 1, dtype=torch.int32, pin_memory=self.cuda))
+            if self.cuda:
+                self.cloud_dev[b] = tuple(torch.empty(t.shape, dtype=t.dtype, device=self.device) for t in host)
+                fresh = torch.cuda.Event()      # the allocator may hand out memory that queued work still reads
+                fresh.record(torch.cuda.current_stream(self.device))
+                self.side.wait_event(fresh)
+            else:
+                self.cloud_dev[b] = host
+        pts, off = host[0].numpy(), host[1].numpy()
+        off[:n + 1] = offsets
+        list(self.workers.map(lambda ip: kitti_velo.read_cloud_into(ip[1], pts[offsets[ip[0]]:offsets[ip[0] + 1]]), enumerate(velo)))
+        return total, n
+
+    def _load(self, k, paths, velo=None):
         b = k % 2
         if self.cuda and self.uploaded[b] is not None:
-            self.uploaded[b].synchronize()          # the pinned buffer is free once its last upload is done
+            self.uploaded[b].synchronize()          # the pinned buffers are free once their last upload is done
         sizes = list(self.workers.map(lambda ip: decode_into(ip[1], self.host_np[b][ip[0]]), enumerate(paths)))
+        total, n = self._load_clouds(b, velo) if velo else (0, 0)
+        if velo:
+            self.clouds[b] = (self.cloud_dev[b][0][:total], self.cloud_dev[b][1][:n + 1])
         if self.cuda:
             with torch.cuda.stream(self.side):
                 if self.consumed[b] is not None:
                     self.side.wait_event(self.consumed[b])
                 self.dev[b][:len(paths)].copy_(self.host[b][:len(paths)], non_blocking=True)
+                if velo:
+                    self.clouds[b][0].copy_(self.cloud_host[b][0][:total], non_blocking=True)
+                    self.clouds[b][1].copy_(self.cloud_host[b][1][:n + 1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.side)
             self.uploaded[b] = ev
         return sizes
 
-    def submit(self, k, paths):
+    def submit(self, k, paths, velo=None):
         if k not in self.pending:
-            self.pending[k] = (self.loader.submit(self._load, k, list(paths)), len(paths))
+            self.pending[k] = (self.loader.submit(self._load, k, list(paths), None if velo is None else list(velo)), len(paths))
 
     def take(self, k):
         fut, n = self.pending.pop(k)
@@ -143,6 +183,10 @@ class _Prefetcher(object):
         if self.cuda:
             torch.cuda.current_stream(self.device).wait_event(self.uploaded[b])
         return self.dev[b][:n], sizes
+
+    def take_clouds(self, k):
+        """(points [total, 4], offsets int32 [n + 1]) of batch k on the device, after ``take(k)``."""
+        return self.clouds[k % 2]
 
     def release(self, k):
         """The current stream has queued every read of batch k's device buffer."""
@@ -161,7 +205,7 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
     (``set_adv_train``, ``update_adv_obj``, ``begin_epoch``), ``synthesize`` and ``_camera`` are the base class's code."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, device, is_train=False, img_ext=".jpg",
-                 seed=1234, num_workers=12, preprocess="reference", color_aug=False):
+                 seed=1234, num_workers=12, preprocess="reference", color_aug=False, full_res_shape=(ori_H, ori_W)):
         if preprocess not in ("reference", "fast"):
             raise RuntimeError("kitti_preprocess must be 'reference' or 'fast'; got %r" % (preprocess,))
         if not filenames:
@@ -173,7 +217,8 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
         self.preprocess, self.color_aug = preprocess, bool(color_aug)
         self.order_rng = random.Random(seed + 1)     # the DataLoader's shuffle: apart, so that it never moves a draw
         self.flip_augmentation = self.is_train       # mono_dataset.py:298
-        self.load_depth = False                      # velodyne ground truth is not built
+        self.full_res_shape = (int(full_res_shape[0]), int(full_res_shape[1]))      # depth_gt's size (kitti_dataset.py:34)
+        self.load_depth = self.check_depth()
         self.views = [0] + (["s"] if "s" in self.frame_idxs else []) + self.neighbour_ids
         self.pool_workers = pool_workers(num_workers)
         self._prefetch = None
@@ -192,6 +237,13 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
                 out.append(image_path(self.data_path, folder, frame_index + f, side, self.img_ext))
         return out
 
+    def check_depth(self):
+        return kitti_velo.check_depth(self.data_path, self.filenames)
+
+    def velo_path(self, index):
+        folder, frame_index, _ = parse_line(self.filenames[index])
+        return kitti_velo.velo_path(self.data_path, folder, frame_index)
+
     def _next_indices(self, n):
         idx = []
         while len(idx) < n:
@@ -208,8 +260,16 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
         idx = self._next_indices(batch_size)
         # view-major: slot v * batch + i
         paths = [p for v in range(len(self.views)) for p in (self.paths_of(i)[v] for i in idx)]
-        self._prefetch.submit(k, paths)
+        self._prefetch.submit(k, paths, [self.velo_path(i) for i in idx] if self.load_depth else None)
         return idx
+
+    def _depth_gt(self, k, idx, sides, flip):
+        """get_depth (kitti_dataset.py:70-85) for the batch: K32 with each line's camera, at full_res_shape, flipped samples mirrored."""
+        points, offsets = self._prefetch.take_clouds(k)
+        calib = [kitti_velo.velo_projection(kitti_velo.calib_dir(self.data_path, parse_line(self.filenames[i])[0]), SIDE_MAP[sd])
+                 for i, sd in zip(idx, sides)]
+        proj = to_device_async(np.stack([P for P, _ in calib]), self.device)
+        return ops.velo_depth_map(points, offsets, proj, [hw for _, hw in calib], False, self.full_res_shape, flip).unsqueeze(1)
 
     def _draw_first(self, geo):
         """do_color_aug's coin (mono_dataset.py:297: one ``random()`` whenever is_train, whether or not colour is augmented) comes
@@ -326,6 +386,10 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
                 self._box_levels(inputs, v, img)
             if v != "s" or self.neighbour_ids:
                 inputs[("color_aug", v, 0)] = inputs[("color", v, 0)]
+        if self.load_depth:
+            if any(sd is None for sd in sides):
+                raise RuntimeError("KITTIRAWDataset: depth_gt needs the camera side of every split line")
+            inputs["depth_gt"] = self._depth_gt(k, idx, sides, flip)
         self._prefetch.release(k)
         if any(geo["jitter"]):
             # mono_dataset.py:344-348 on the float level 0 (the reference jitters the 8-bit image): one transform per item, the
@@ -450,8 +514,8 @@ def from_options(opt, device, rank=0):
         raise NotImplementedError("--dataset %s: only KITTI raw (kitti) is read from disk; kitti_odom, kitti_depth and "
                                   "kitti_test have no loader here" % opt.dataset)
     if opt.gt_depth:
-        raise NotImplementedError("--gt_depth with --dataset kitti needs depth_gt from velodyne points, which this loader "
-                                  "does not build (load_depth is False)")
+        raise NotImplementedError("--gt_depth with --dataset kitti: the pseudo-depth term on depth_gt from velodyne points is "
+                                  "not wired to this loader (depth_gt itself is built when the scans exist: load_depth)")
     if opt.use_depth_hints:
         raise NotImplementedError("--use_depth_hints with --dataset kitti: precomputed hints are not read from disk")
     lines = read_split(os.path.join(opt.split_dir, opt.split, "train_files.txt"))

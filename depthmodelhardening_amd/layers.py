@@ -195,3 +195,17 @@ class SSIM(nn.Module):
         n = (2 * mu_x * mu_y + self.C1) * (2 * sigma_xy + self.C2)
         d = (mu_x ** 2 + mu_y ** 2 + self.C1) * (sigma_x + sigma_y + self.C2)
         return torch.clamp((1 - n / d) / 2, 0, 1)
+
+
+def compute_depth_errors(gt, pred):
+    """The seven depth metrics between ground truth and prediction (MD2/layers.py:256-274), as tensors on the inputs' device:
+    abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3."""
+    thresh = torch.max((gt / pred), (pred / gt))
+    a1 = (thresh < 1.25).float().mean()
+    a2 = (thresh < 1.25 ** 2).float().mean()
+    a3 = (thresh < 1.25 ** 3).float().mean()
+    rmse = torch.sqrt(((gt - pred) ** 2).mean())
+    rmse_log = torch.sqrt(((torch.log(gt) - torch.log(pred)) ** 2).mean())
+    abs_rel = torch.mean(torch.abs(gt - pred) / gt)
+    sq_rel = torch.mean((gt - pred) ** 2 / gt)
+    return abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3

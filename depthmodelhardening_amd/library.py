@@ -33,6 +33,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::cost_volume          manydepth2/networks/resnet_encoder.py:157-236,258-265,294-296   (K30, forward only)
     dmh::cost_volume_into     the same, cost_volume * confidence written into channels 64 .. of ``buffer``   (K30, in place)
     dmh::pil_resample         MD2/datasets/mono_dataset.py:100-104,119-144 (PIL.Image.resize, 8-bit, bit for bit)   (K31, no autograd)
+    dmh::velo_depth_map       MD2/kitti_utils.py:46-98 + datasets/kitti_dataset.py:70-85 (generate_depth_map, float32-equal) (K32, no autograd)
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -711,8 +712,26 @@ def _(src, out_h, out_w, filter="lanczos", flip=None, sizes=None, hwc=False):
     return src.new_empty(shape, dtype=torch.uint8), src.new_empty(shape, dtype=torch.float32)
 
 
+# ---------------------------------------------------------------------------------------------------------------- K32
+@custom_op("dmh::velo_depth_map", mutates_args=())
+def velo_depth_map(points: torch.Tensor, offsets: torch.Tensor, proj: torch.Tensor, shapes: List[int], vel_depth: bool = False,
+                   out_size: Optional[List[int]] = None, flip: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``shapes``: H0, W0, H1, W1, ... of the frames.  With ``out_size`` float32 [n, out_h, out_w]; without it the maps at their own
+    sizes in one flat float32 buffer, frame f at sum(H W of the frames before it).  Ground truth carries no gradient."""
+    ops._need_cuda(points)
+    out = ops.velo_depth_map(points, offsets, proj, list(zip(shapes[0::2], shapes[1::2])), vel_depth, out_size, flip)
+    return out if out_size is not None else out[0]
+
+
+@velo_depth_map.register_fake
+def _(points, offsets, proj, shapes, vel_depth=False, out_size=None, flip=None):
+    if out_size is not None:
+        return points.new_empty((offsets.shape[0] - 1, out_size[0], out_size[1]))
+    return points.new_empty((sum(h * w for h, w in zip(shapes[0::2], shapes[1::2])),))
+
+
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
-       "cost_volume", "cost_volume_into", "pil_resample")
+       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map")

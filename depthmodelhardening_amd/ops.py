@@ -3355,3 +3355,160 @@ def pil_pyramid(src, height, width, num_scales=4, filter="lanczos", flip=None, s
         else:
             levels.append(pil_resize(levels[-1].u8, (height // s, width // s), filter, None, None, want_float, "chw"))
     return levels
+
+
+# ---------------------------------------------------------------------------------------------------------------- K32
+VELO_EMPTY, VELO_DESC_CACHE = 0xFFFFFFFF, 16
+_velo_desc_cache = OrderedDict()      # (device, shapes) -> descriptors on the device
+
+
+def nearest_index(n_in, n_out):
+    """Source index of every output index of K32's nearest resize: ((2 o + 1) n_in) // (2 n_out), the exact-arithmetic value of
+    the pixel-centre mapping round((o + 0.5) n_in / n_out - 0.5); the identity when the sizes agree."""
+    o = np.arange(int(n_out), dtype=np.int64)
+    return ((2 * o + 1) * int(n_in)) // (2 * int(n_out))
+
+
+def _velo_shapes(shapes, n):
+    shapes = tuple((int(h), int(w)) for h, w in (shapes.tolist() if hasattr(shapes, "tolist") else shapes))
+    if len(shapes) != n or not all(h >= 1 and w >= 2 for h, w in shapes):
+        raise RuntimeError("velo_depth_map: shapes must be %d pairs (H, W) with H >= 1 and W >= 2; got %s" % (n, shapes))
+    return shapes
+
+
+def _velo_frame_host(pts, P, H, W, vel_depth):
+    """One frame of K32 in numpy -> float32 [H, W]: the kernel's arithmetic in the kernel's order (csrc/velo_depth.hip)."""
+    idx = np.nonzero(pts[:, 0] >= 0)[0]                     # a NaN fails the test
+    x, y, z = (pts[idx, c].astype(np.float64) for c in range(3))
+    with np.errstate(all="ignore"):
+        q = [((P[r, 0] * x + P[r, 1] * y) + P[r, 2] * z) + P[r, 3] for r in range(3)]
+        u, v = np.rint(q[0] / q[2]) - 1.0, np.rint(q[1] / q[2]) - 1.0
+        keep = (u >= 0) & (v >= 0) & (u < W) & (v < H)      # NaN and inf fall out
+        d = (x if vel_depth else q[2])[keep]
+        val = np.where(d > 0, d, 0.0).astype(np.float32)    # float32(max(d, 0)); rounding and the clamp are monotone
+    idx, ui, vi = idx[keep], u[keep].astype(np.int64), v[keep].astype(np.int64)
+    if idx.size == 0:
+        return np.zeros((H, W), dtype=np.float32)
+    bits = val.view(np.uint32)                             # non-negative floats order as their bits do
+    cells = np.full(H * W, VELO_EMPTY, dtype=np.uint32)
+    np.minimum.at(cells, vi * W + ui, bits)
+    out = np.where(cells == VELO_EMPTY, np.uint32(0), cells).reshape(H, W)
+    if H > 1:
+        # the reference's sub2ind gives A = (y, W - 1) and B = (y + 1, 0) one key: where both hold points, the one that holds the
+        # pair's earliest point gets the minimum over both, the other keeps its last point's value
+        first = np.full((H, 2), np.iinfo(np.int64).max, dtype=np.int64)
+        last = np.full((H, 2), -1, dtype=np.int64)
+        for side, col in ((0, 0), (1, W - 1)):
+            on = ui == col
+            np.minimum.at(first[:, side], vi[on], idx[on])
+            np.maximum.at(last[:, side], vi[on], idx[on])
+        cells = cells.reshape(H, W)
+        a, b = cells[:-1, W - 1], cells[1:, 0]
+        both = (a != VELO_EMPTY) & (b != VELO_EMPTY)
+        a_first = first[:-1, 1] < first[1:, 0]
+        low = np.minimum(a, b)
+        pos = np.full(pts.shape[0], -1, dtype=np.int64)
+        pos[idx] = np.arange(idx.size)
+        last_a, last_b = bits[pos[np.maximum(last[:-1, 1], 0)]], bits[pos[np.maximum(last[1:, 0], 0)]]
+        out[:-1, W - 1] = np.where(both, np.where(a_first, low, last_a), out[:-1, W - 1])
+        out[1:, 0] = np.where(both, np.where(a_first, last_b, low), out[1:, 0])
+    return out.view(np.float32)
+
+
+def velo_depth_map_host(points, offsets, proj, shapes, vel_depth=False, out_size=None, flip=None):
+    """K32 in numpy, the definition the kernel is held to (and the path CPU tensors take): vectorised, no loop per duplicate.
+    points float32 [npts, 4], offsets [n + 1], proj float64 [n, 3, 4] or [n, 12], shapes n pairs (H, W).  Returns float32
+    [n, out_h, out_w] with ``out_size``, else the list of the n maps at their own sizes."""
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+    offsets = [int(v) for v in np.asarray(offsets).reshape(-1)]
+    n = len(offsets) - 1
+    proj = np.asarray(proj, dtype=np.float64).reshape(n, 3, 4)
+    shapes = _velo_shapes(shapes, n)
+    flips = [False] * n if flip is None else [bool(v) for v in np.asarray(flip).reshape(-1)]
+    if len(flips) != n:
+        raise RuntimeError("velo_depth_map: flip must have one entry per frame")
+    if offsets[0] < 0 or offsets[-1] > points.shape[0] or any(a > b for a, b in zip(offsets[:-1], offsets[1:])):
+        raise RuntimeError("velo_depth_map: offsets must ascend within the %d points; got %s" % (points.shape[0], offsets))
+    maps = []
+    for f, (H, W) in enumerate(shapes):
+        m = _velo_frame_host(points[offsets[f]:offsets[f + 1]], proj[f], H, W, bool(vel_depth))
+        if out_size is not None:
+            m = m[nearest_index(H, out_size[0])][:, nearest_index(W, out_size[1])]
+        maps.append(np.ascontiguousarray(m[:, ::-1] if flips[f] else m))
+    return np.stack(maps) if out_size is not None else maps
+
+
+def _velo_desc_device(device, shapes):
+    key = (str(device), shapes)
+    hit = _velo_desc_cache.get(key)
+    if hit is not None:
+        _velo_desc_cache.move_to_end(key)
+        return hit[0]
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("velo_depth_map: the first call with these shapes uploads their descriptors; make it once before "
+                           "capturing a graph")
+    cells = np.cumsum([0] + [h * w for h, w in shapes])
+    rows = np.cumsum([0] + [h for h, _ in shapes])
+    host = torch.tensor([[h, w, int(cells[i]), int(rows[i])] for i, (h, w) in enumerate(shapes)], dtype=torch.int32).pin_memory()
+    _velo_desc_cache[key] = (host.to(device, non_blocking=True), host)      # the pinned copy lives as long as the upload may
+    while len(_velo_desc_cache) > VELO_DESC_CACHE:
+        _velo_desc_cache.popitem(last=False)
+    return _velo_desc_cache[key][0]
+
+
+def velo_depth_map(points, offsets, proj, shapes, vel_depth=False, out_size=None, flip=None):
+    """K32: the sparse depth maps of a batch of velodyne scans (MD2/kitti_utils.py:46-98, generate_depth_map, float32-equal),
+    with the loader's nearest resize and flip (MD2/datasets/kitti_dataset.py:70-85).
+
+    points   float32 [npts, 4], the frames' points packed in file order; offsets int32 [n + 1] on the same device.
+    proj     float64 [n, 3, 4] (or [n, 12]): P_velo2im of each frame (datasets.kitti_velo.velo_projection).
+    shapes   n pairs (H, W): each frame's image size.  Host values: they size the workspace and the output.
+    flip     per frame, an int32 tensor [n] on the device (or a host sequence of bools): != 0 mirrors the columns.
+    Returns  float32 [n, out_h, out_w] with ``out_size``; without it (flat float32 [sum H W], cell offsets as a list of n + 1
+             ints): frame f is flat[off[f]:off[f + 1]].view(H, W).
+
+    CPU tensors run ``velo_depth_map_host``, the numpy restatement the kernel is bit-equal to."""
+    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4:
+        raise RuntimeError("velo_depth_map: points must be a float32 tensor [npts, 4]; got %s %s"
+                           % (getattr(points, "dtype", type(points)), tuple(getattr(points, "shape", ()))))
+    _eigen_i32(offsets, "offsets")
+    n = offsets.numel() - 1
+    if offsets.dim() != 1 or n < 1:
+        raise RuntimeError("velo_depth_map: offsets must hold n + 1 >= 2 entries; got %s" % (tuple(offsets.shape),))
+    if not torch.is_tensor(proj) or proj.dtype != torch.float64 or proj.numel() != 12 * n:
+        raise RuntimeError("velo_depth_map: proj must be a float64 tensor of %d x 12 entries; got %s %s"
+                           % (n, getattr(proj, "dtype", type(proj)), tuple(getattr(proj, "shape", ()))))
+    shapes = _velo_shapes(shapes, n)
+    if out_size is not None:
+        out_size = tuple(int(v) for v in out_size)
+        if len(out_size) != 2 or out_size[0] < 1 or out_size[1] < 1:
+            raise RuntimeError("velo_depth_map: out_size must be a positive (h, w); got %s" % (out_size,))
+    cell_off = [int(v) for v in np.cumsum([0] + [h * w for h, w in shapes])]
+    dev = points.device
+    if offsets.device != dev or proj.device != dev:
+        raise RuntimeError("velo_depth_map: points, offsets and proj must share a device")
+    if dev.type != "cuda":
+        res = velo_depth_map_host(points.numpy(), offsets.numpy(), proj.numpy(), shapes, vel_depth, out_size,
+                                  None if flip is None else (flip.tolist() if hasattr(flip, "tolist") else flip))
+        if out_size is not None:
+            return torch.from_numpy(res)
+        return torch.from_numpy(np.concatenate([m.reshape(-1) for m in res])), cell_off
+    if flip is not None and not torch.is_tensor(flip):
+        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    if flip is not None and (flip.dtype != torch.int32 or flip.numel() != n or flip.device != dev):
+        raise RuntimeError("velo_depth_map: flip must be an int32 tensor of %d entries on %s" % (n, dev))
+    lib = N.lib()
+    total_cells, total_rows = cell_off[-1], sum(h for h, _ in shapes)
+    words = lib.dmh_velo_depth_ws_size(total_cells, total_rows)
+    if words < 0:
+        raise RuntimeError("velo_depth_map: %d cells and %d rows do not fit a 2^31-word workspace" % (total_cells, total_rows))
+    desc = _velo_desc_device(dev, shapes)
+    ws = torch.empty(words, device=dev, dtype=torch.int32)
+    out = torch.empty((n,) + out_size if out_size is not None else (total_cells,), device=dev, dtype=torch.float32)
+    points, proj = _c(points), _c(proj)
+    oh, ow = out_size if out_size is not None else (0, 0)
+    N.check(_timed("velo_depth_map", lambda: lib.dmh_velo_depth_map(
+        N.ptr(points) if points.numel() else None, int(points.shape[0]), N.ptr(_c(offsets)), N.ptr_f64(proj), N.ptr(desc),
+        N.ptr(None if flip is None else _c(flip)), n, int(bool(vel_depth)), total_cells, total_rows, oh, ow, N.ptr(ws), N.ptr(out),
+        N.stream()), points.numel() * 4 + 8 * words + out.numel() * 4))
+    return out if out_size is not None else (out, cell_off)

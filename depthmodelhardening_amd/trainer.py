@@ -17,6 +17,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 import torch.optim as optim
@@ -27,7 +28,7 @@ from .contrastive import SimSiam
 from .datasets import SyntheticKITTIDataset, make_object
 from .ddp import GradBucket, average_buffers, broadcast_parameters
 from .depth_model import DepthModelWrapper, import_depth_model
-from .layers import SSIM, get_smooth_loss
+from .layers import SSIM, compute_depth_errors, disp_to_depth, get_smooth_loss
 from .my_utils import ori_H, ori_W
 
 
@@ -41,6 +42,7 @@ class StepLog:
         self.file = None
         self.images = images_per_step
         self.marks, self.pending, self.t0, self.host = [], None, None, None
+        self.extra = {}                 # values for the next line written (the depth metrics of a logging step)
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             self.file = open(path, "a")
@@ -99,6 +101,8 @@ class StepLog:
             line["images_per_s"] = round(self.images / (device_ms * 1e-3), 2)
         if t0 is not None:
             line["host_enqueue_ms"] = round((now - t0) * 1e3, 3)
+        line.update(self.extra)
+        self.extra.clear()
         self.file.write(json.dumps(line) + "\n")
         self.file.flush()
         self.pending = None
@@ -108,6 +112,26 @@ class StepLog:
             self._flush()
             self.file.close()
             self.file = None
+
+
+DEPTH_METRIC_NAMES = ["de/abs_rel", "de/sq_rel", "de/rms", "de/log_rms", "da/a1", "da/a2", "da/a3"]     # MD2/trainer.py:204-205
+
+
+def depth_metrics(depth_pred, depth_gt):
+    """The body of ``compute_depth_losses`` (MD2/trainer.py:676-704): the prediction [B, 1, h, w] bilinearly to depth_gt's
+    375 x 1242 and clamped to [1e-3, 80], the pixels with ground truth inside the Garg/Eigen crop [153:371, 44:1197], one median
+    ratio over the whole batch, clamped again -> the seven numbers of ``compute_depth_errors`` as one float tensor [7] on the
+    device.  Torch expressions: it runs at the logging steps only."""
+    depth_pred = torch.clamp(F.interpolate(depth_pred.detach(), [ori_H, ori_W], mode="bilinear", align_corners=False), 1e-3, 80)
+    mask = depth_gt > 0
+    crop_mask = torch.zeros_like(mask)
+    crop_mask[:, :, 153:371, 44:1197] = 1
+    mask = mask * crop_mask
+    depth_gt = depth_gt[mask]
+    depth_pred = depth_pred[mask]
+    depth_pred = depth_pred * (torch.median(depth_gt) / torch.median(depth_pred))
+    depth_pred = torch.clamp(depth_pred, min=1e-3, max=80)
+    return torch.stack(compute_depth_errors(depth_gt, depth_pred))
 
 
 class LazyOutputs(dict):
@@ -375,6 +399,8 @@ class Trainer:
                 log.mark("attack")
         inputs = self.dataset.next_batch(self.opt.batch_size)
         outputs, losses = self.process_batch(inputs)
+        # what compute_depth_losses reads at the logging steps, and nothing else of the step (the rest is freed as before)
+        self._last_batch = ({"depth_gt": inputs["depth_gt"]}, {("disp", 0): outputs[("disp", 0)].detach()}) if "depth_gt" in inputs else ({}, {})
         log.mark("forward+loss")
         with self.bucket.released():             # model_optimizer.zero_grad(); gradients land in the flat bucket afterwards
             losses["loss"].backward()
@@ -418,6 +444,8 @@ class Trainer:
             late_phase = self.step % 2000 == 0
             if (early_phase or late_phase) and self.rank == 0:
                 self.log_time(batch_idx, time.time() - before_op_time, losses["loss"].detach().cpu())
+                if "depth_gt" in self._last_batch[0]:           # MD2/trainer.py:326-327
+                    self.compute_depth_losses(self._last_batch[0], self._last_batch[1], losses)
                 if self.opt.adv_train and self.val_eval_count > 0:
                     self._apply_pending_update()
                     self.val()
@@ -773,6 +801,20 @@ class Trainer:
         return losses
 
     # ------------------------------------------------------------------ logging / checkpoints
+    depth_metric_names = DEPTH_METRIC_NAMES
+
+    def compute_depth_losses(self, inputs, outputs, losses):
+        """Depth metrics against inputs["depth_gt"], to monitor training (MD2/trainer.py:676-704; averaged over the whole batch,
+        so an indication only).  The depth is the reference's ("depth", 0, 0): the scale-0 disparity through disp_to_depth.
+        The seven values go into ``losses`` under ``depth_metric_names`` and into the step log's next line."""
+        _, depth = disp_to_depth(outputs[("disp", 0)].detach(), self.opt.min_depth, self.opt.max_depth)
+        errors = depth_metrics(depth, inputs["depth_gt"]).cpu()
+        for i, metric in enumerate(self.depth_metric_names):
+            losses[metric] = np.array(float(errors[i]), dtype=np.float32)
+        self.step_log.extra.update({m: float(errors[i]) for i, m in enumerate(self.depth_metric_names)})
+        print("depth metrics | " + " | ".join("{}: {:.4f}".format(m, float(errors[i])) for i, m in enumerate(self.depth_metric_names)),
+              flush=True)
+
     def log_time(self, batch_idx, duration, loss):
         samples_per_sec = self.opt.batch_size * self.world_size / duration
         time_sofar = time.time() - self.start_time if hasattr(self, "start_time") else 0.0

@@ -859,6 +859,32 @@ int dmh_pil_resample(const void* src, int src_f32, int64_t sn, int64_t sc, int64
                      const int32_t* tables, int64_t table_words, const int32_t* desc, const int32_t* flip, int N, int C,
                      int H_out, int W_out, int lds_rows, uint8_t* out_u8, float* out_f32, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K32 The sparse depth maps of a batch of velodyne scans: MD2/kitti_utils.py:46-98 (generate_depth_map) with the loader's
+ *     nearest resize and flip (MD2/datasets/kitti_dataset.py:70-85), float32-equal to the reference.
+ *     points: float32 [npts][4] (x forward, y left, z up, reflectance: ignored, the reference overwrites it with 1), the frames
+ *     packed one after the other; offsets: int32 [n + 1], frame f owns the points offsets[f] .. offsets[f + 1] - 1 in file order.
+ *     proj: float64 [n][12], the row-major 3 x 4 P_velo2im of each frame.  A point is kept if x >= 0; q = P (x, y, z, 1) in float64
+ *     as ((P[r][0] x + P[r][1] y) + P[r][2] z) + P[r][3] without contraction; u = rint(q0 / q2) - 1, v = rint(q1 / q2) - 1, kept
+ *     if 0 <= u < W and 0 <= v < H; the value is q2, or x when vel_depth != 0, as float32(max(., 0)).  A pixel holds the minimum
+ *     over its points, except for the pixel pairs (y, W - 1) / (y + 1, 0) that the reference's sub2ind gives one key: when both
+ *     hold points, the one with the earliest point of the pair holds the minimum over both and the other the value of the last
+ *     point that fell on it.  A pixel no point reaches is 0.
+ *     desc: int32 [n][4] per frame = H, W (W >= 2), the offset of its H W cells in the workspace (and in the native-size output),
+ *     the offset of its H rows in the edge table; total_cells = sum H W, total_rows = sum H.  A frame whose descriptor leaves
+ *     these bounds is written as zeros.
+ *     out_h, out_w > 0: out [n][out_h][out_w], element (oy, ox) reads the map at (((2 oy + 1) H) / (2 out_h),
+ *     ((2 ox + 1) W) / (2 out_w)) in integers -- nearest, pixel centres, the identity at equal sizes -- and with flip[f] != 0
+ *     (int32 [n], may be NULL) the column out_w - 1 - ox.  out_h = out_w = 0: out [total_cells], every map at its own size at
+ *     its cell offset (flip mirrors the columns).  Every element of out is written.
+ *     ws: dmh_velo_depth_ws_size(total_cells, total_rows) uint32 words (-1 when they do not fit 2^31), contents ignored.
+ *     Three launches (fill, scatter, finalise); 32-bit integer atomics only, no host read: bitwise reproducible.
+ * ---------------------------------------------------------------------------------- */
+int64_t dmh_velo_depth_ws_size(int64_t total_cells, int64_t total_rows);
+int dmh_velo_depth_map(const float* points, int64_t npts, const int32_t* offsets, const double* proj, const int32_t* desc,
+                       const int32_t* flip, int n, int vel_depth, int64_t total_cells, int64_t total_rows, int out_h, int out_w,
+                       uint32_t* ws, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
