@@ -133,7 +133,6 @@ _SIGNATURES = {
     "dmh_bn_act_fwd": (C.c_int, [_fp] * 4 + [C.c_int] * 4 + [_fp, _fp]),
     "dmh_bn_act_bwd": (C.c_int, [_fp] * 3 + [C.c_int] * 4 + [_fp, _fp, _fp]),
     "dmh_bn_stats_partials_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
-    "dmh_bn_train_stats": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float] + [_fp] * 8),
     "dmh_bn_train_stats_tracked": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, C.c_float] + [_fp] * 9),
     "dmh_channel_sum_partials_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "dmh_channel_sum": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_void_p]),
@@ -169,9 +168,7 @@ _SIGNATURES = {
     "dmh_conv3x3_small_wrw": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp] * 4),
     "dmh_conv7x7s2_bwd_data": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp, _fp]),
     "dmh_stem_conv_norm_fwd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp]),
-    "dmh_down_conv_fwd": (C.c_int, [_fp] * 3 + [C.c_int] * 5 + [_fp] * 3),
     "dmh_down_conv_fwd_act": (C.c_int, [_fp] * 5 + [C.c_int] * 6 + [_fp] * 3),
-    "dmh_down_conv_bwd_data": (C.c_int, [_fp] * 4 + [C.c_int] * 5 + [_fp, _fp]),
     "dmh_down_conv_bwd_data_acc": (C.c_int, [_fp] * 5 + [C.c_int] * 5 + [_fp, _fp]),
     "dmh_down_conv_image_size": (C.c_int64, [C.c_int, C.c_int]),
     "dmh_down_conv_weight_image": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),

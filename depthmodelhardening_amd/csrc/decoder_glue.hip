@@ -12,8 +12,6 @@
 // and the convolutions run with padding = 0 on the padded tensors.  Backward kernels are gathers (the adjoint of the
 // reflection pad folds the border rows/columns back onto rows 1 and H-2): deterministic, no atomics.
 // Pure HBM streaming: one read + one write per element, 64-lane coalesced rows.
-#include <stdlib.h>
-
 #include "common.hpp"
 
 using namespace dmh;
@@ -297,12 +295,6 @@ __global__ __launch_bounds__(NT) void elu_pad_bwd4_kernel(const float* __restric
 
 inline unsigned blocks_for(int n) { return (unsigned)((n + NT - 1) / NT); }
 
-// DMH_GLUE_PAIRS=1 forces the two-wide kernels (timing comparisons, tools/glue_bench.py)
-inline bool use_quads() {
-    static const bool q = [] { const char* e = getenv("DMH_GLUE_PAIRS"); return !(e && e[0] == '1'); }();
-    return q;
-}
-
 }  // namespace
 
 extern "C" {
@@ -312,7 +304,7 @@ int dmh_dec_up_cat_pad_fwd(const float* y, const float* skip, int B, int C1, int
     DMH_REQUIRE(y && out && (skip || C2 == 0), "null pointer");
     DMH_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && h >= 1 && w >= 1, "bad sizes");
     DMH_REQUIRE((int64_t)B * (C1 + C2) <= 65535 && (int64_t)(2 * h + 2) * (2 * w + 2) < (1 << 30), "tensor too large");
-    if ((w & 1) == 0 && use_quads()) {
+    if ((w & 1) == 0) {
         const int bpa = (int)blocks_for(h * (w / 2)), bpb = (int)blocks_for(h * w);
         const int64_t nA = (int64_t)B * C1 * bpa, nB = (int64_t)B * C2 * bpb;
         DMH_REQUIRE(nA + nB < ((int64_t)1 << 31), "grid too large");
@@ -331,7 +323,7 @@ int dmh_dec_up_cat_pad_bwd(const float* y, const float* g_out, int B, int C1, in
     DMH_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && h >= 1 && w >= 1, "bad sizes");
     const int planes = B * C1 + (g_skip ? B * C2 : 0);
     DMH_REQUIRE(planes <= 65535 && (int64_t)(2 * h + 2) * (2 * w + 2) < (1 << 30), "tensor too large");
-    if ((w & 1) == 0 && use_quads()) {
+    if ((w & 1) == 0) {
         const int bpa = (int)blocks_for(h * (w / 2)), bpb = (int)blocks_for(h * w);
         const int64_t nA = (int64_t)B * C1 * bpa, nB = g_skip ? (int64_t)B * C2 * bpb : 0;
         DMH_REQUIRE(nA + nB < ((int64_t)1 << 31), "grid too large");
@@ -349,7 +341,7 @@ int dmh_elu_pad_fwd(const float* z, int B, int C, int H, int W, int apply_elu, f
     DMH_REQUIRE(z && out, "null pointer");
     DMH_REQUIRE(B > 0 && C > 0 && H >= 2 && W >= 2, "bad sizes");
     DMH_REQUIRE((int64_t)B * C <= 65535 && (int64_t)(H + 2) * (W + 2) < (1 << 30), "tensor too large");
-    if ((W & 3) == 0 && use_quads())
+    if ((W & 3) == 0)
         hipLaunchKernelGGL(elu_pad_fwd4_kernel, dim3(blocks_for(H * W / 4), B * C), dim3(NT), 0, (hipStream_t)stream, z, H,
                            W, apply_elu, out);
     else if ((W & 1) == 0)
@@ -366,7 +358,7 @@ int dmh_elu_pad_bwd(const float* z, const float* g_out, int B, int C, int H, int
     DMH_REQUIRE(z && g_out && g_z, "null pointer");
     DMH_REQUIRE(B > 0 && C > 0 && H >= 2 && W >= 2, "bad sizes");
     DMH_REQUIRE((int64_t)B * C <= 65535 && (int64_t)(H + 2) * (W + 2) < (1 << 30), "tensor too large");
-    if ((W & 3) == 0 && use_quads())
+    if ((W & 3) == 0)
         hipLaunchKernelGGL(elu_pad_bwd4_kernel, dim3(blocks_for(H * W / 4), B * C), dim3(NT), 0, (hipStream_t)stream, z,
                            g_out, H, W, apply_elu, g_z);
     else if ((W & 1) == 0)

@@ -666,14 +666,6 @@ int check_sizes(int B, int Cin, int Cout, int H, int W) {
 extern "C" {
 
 int dmh_down_conv_fwd_act(const float* x, const float* w3, const float* wd, const float* shift3, const float* shiftd,
-                          int relu3, int B, int Cin, int Cout, int H, int W, float* y3, float* yd, void* stream);
-
-int dmh_down_conv_fwd(const float* x, const float* w3, const float* wd, int B, int Cin, int Cout, int H, int W,
-                      float* y3, float* yd, void* stream) {
-    return dmh_down_conv_fwd_act(x, w3, wd, nullptr, nullptr, 0, B, Cin, Cout, H, W, y3, yd, stream);
-}
-
-int dmh_down_conv_fwd_act(const float* x, const float* w3, const float* wd, const float* shift3, const float* shiftd,
                           int relu3, int B, int Cin, int Cout, int H, int W, float* y3, float* yd, void* stream) {
     DMH_REQUIRE(x && w3 && y3 && ((wd == nullptr) == (yd == nullptr)), "null pointer");
     DMH_REQUIRE(shiftd == nullptr || wd != nullptr, "shiftd without the shortcut convolution");
@@ -756,11 +748,6 @@ int dmh_down_conv_fwd_img(const float* x, const float* image, int has_down, cons
     return check_launch("dmh_down_conv_fwd_img");
 }
 
-int dmh_down_conv_bwd_data(const float* g3, const float* gd, const float* w3t, const float* wdt, int B, int Cin, int Cout,
-                           int H, int W, float* g_x, void* stream) {
-    return dmh_down_conv_bwd_data_acc(g3, gd, w3t, wdt, nullptr, B, Cin, Cout, H, W, g_x, stream);
-}
-
 int dmh_down_conv_bwd_data_acc(const float* g3, const float* gd, const float* w3t, const float* wdt, const float* g_add, int B,
                                int Cin, int Cout, int H, int W, float* g_x, void* stream) {
     DMH_REQUIRE(g3 && w3t && g_x && ((gd == nullptr) == (wdt == nullptr)), "null pointer");
@@ -795,7 +782,7 @@ int dmh_down_conv_bwd_data_acc(const float* g3, const float* gd, const float* w3
         hipLaunchKernelGGL((down_conv_bwd_kernel<false, 2>), dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL((down_conv_bwd_kernel<false, 1>), dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, a);
-    return check_launch("dmh_down_conv_bwd_data");
+    return check_launch("dmh_down_conv_bwd_data_acc");
 }
 
 int dmh_down_conv_bwd_data_img(const float* g3, const float* gd, const float* image, const float* g_add, int B, int Cin, int Cout,

@@ -620,13 +620,6 @@ int64_t dmh_bn_stats_partials_size(int B, int C, int HW) {
     return (int64_t)C * S * 3;
 }
 
-int dmh_bn_train_stats(const float* x, int B, int C, int HW, const float* weight, const float* bias, float momentum,
-                       float eps, float* running_mean, float* running_var, float* partials, float* scale, float* shift,
-                       float* save_mean, float* save_invstd, void* stream) {
-    return dmh_bn_train_stats_tracked(x, B, C, HW, weight, bias, momentum, eps, running_mean, running_var, nullptr, partials,
-                                      scale, shift, save_mean, save_invstd, stream);
-}
-
 int dmh_bn_train_stats_tracked(const float* x, int B, int C, int HW, const float* weight, const float* bias, float momentum,
                                float eps, float* running_mean, float* running_var, long long* num_batches_tracked,
                                float* partials, float* scale, float* shift, float* save_mean, float* save_invstd,
@@ -640,7 +633,7 @@ int dmh_bn_train_stats_tracked(const float* x, int B, int C, int HW, const float
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3((unsigned)S, C), dim3(NT), 0, st, x, B, C, HW, (int)S, partials);
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(blocks_for(C)), dim3(NT), 0, st, partials, C, (int)S, weight, bias,
                        momentum, eps, running_mean, running_var, scale, shift, save_mean, save_invstd, num_batches_tracked);
-    return check_launch("dmh_bn_train_stats");
+    return check_launch("dmh_bn_train_stats_tracked");
 }
 
 int64_t dmh_channel_sum_partials_size(int B, int C, int HW) {

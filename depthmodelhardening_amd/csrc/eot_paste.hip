@@ -12,8 +12,6 @@
 // HBM-bound: the scene (5.6 MB/sample) is read once, the 1.2 MB patch+mask stay L2-resident, the
 // output (5.2 MB/sample) is written once with 64-lane coalesced rows.  The backward is a gather per patch
 // texel over the inverse homography: deterministic, no atomics.
-#include <stdlib.h>
-
 #include "common.hpp"
 
 using namespace dmh;
@@ -483,12 +481,6 @@ __global__ __launch_bounds__(NT) void paste_bwd_kernel(const dmh_paste_args a, c
     }
 }
 
-// DMH_PASTE_FWD4=1 keeps the untiled four-pixel kernel (timing comparisons, tools/prof_k3.py)
-inline bool force_paste4() {
-    static const bool f = [] { const char* e = getenv("DMH_PASTE_FWD4"); return e && e[0] == '1'; }();
-    return f;
-}
-
 int check_paste(const dmh_paste_args* a) {
     DMH_REQUIRE(a != nullptr, "args is null");
     DMH_REQUIRE(a->mode == DMH_PASTE_COMPOSITE || a->mode == DMH_PASTE_WARP_ONLY, "bad mode");
@@ -511,7 +503,7 @@ int dmh_eot_paste_fwd(const dmh_paste_args* a, float* adv, float* mask_out, void
                       (a->mode == DMH_PASTE_WARP_ONLY || a->scene != nullptr);
     // the tiled kernel's LDS rectangle must hold the taps of a TH x TW output tile
     const float rh = (float)a->SH / (float)a->OH, rw = (float)a->SW / (float)a->OW;
-    const bool tiled = vec4 && (int)floorf(rh * (TH - 1)) + 3 <= RMAX && (int)floorf(rw * (TW - 1)) + 3 <= CMAX && !force_paste4();
+    const bool tiled = vec4 && (int)floorf(rh * (TH - 1)) + 3 <= RMAX && (int)floorf(rw * (TW - 1)) + 3 <= CMAX;
     if (tiled)
         hipLaunchKernelGGL(paste_fwd_tile_kernel, dim3((a->OW + TW - 1) / TW, (a->OH + TH - 1) / TH, a->N), dim3(NT), 0,
                            (hipStream_t)stream, *a, adv, mask_out);

@@ -14,8 +14,6 @@
 // channel by channel, 14 rows per batch of loads (1 coalesced load, 2 DPP lane shifts and 9 FMAs per row); nine wave sums per channel go to a
 // per-strip partial, and head_wrw_reduce_kernel adds the partials in a fixed order (deterministic, no atomics).
 // Small maps split their channels over several waves per strip.
-#include <stdlib.h>
-
 #include "common.hpp"
 
 using namespace dmh;
@@ -348,12 +346,6 @@ __global__ __launch_bounds__(NT) void head_wrw_reduce_kernel(const float* __rest
     }
 }
 
-// DMH_HEAD_TILE=1 keeps the LDS-tile forward kernel (timing comparisons)
-inline bool force_tile_kernel() {
-    static const bool f = [] { const char* e = getenv("DMH_HEAD_TILE"); return e && e[0] == '1'; }();
-    return f;
-}
-
 struct WrwGeo { int sx, sy, cg; long long strips; };
 inline WrwGeo wrw_geo(int B, int C, int Ho, int Wo) {
     WrwGeo g;
@@ -368,7 +360,7 @@ inline WrwGeo wrw_geo(int B, int C, int Ho, int Wo) {
 // ---- launch forms: ONE host function per decision, called by the launcher and returned by the dmh_*_form queries below
 // forward: the strip kernel at pad 0 while the byte offsets of an image fit 32 bits, the LDS-tile kernel otherwise
 inline bool head_fwd_strips(int C, int H, int W, int pad) {
-    return pad == 0 && (int64_t)C * H * W < ((int64_t)1 << 29) && !force_tile_kernel();
+    return pad == 0 && (int64_t)C * H * W < ((int64_t)1 << 29);
 }
 // backward-data: waves that share a strip of 62 x BR pixels of g_x (channel split); few strips: four, to fill the chip
 inline long long head_bwd_strips(int B, int H, int W) {

@@ -29,8 +29,6 @@
 //
 // Reference semantics: MD2/trainer.py:472-537,589-660; MD2/layers.py:16-25,139-198,223-253;
 // DH/trainer.py:557-590,638-708.  (file:line relative to /root/reference/DepthNetworks/...)
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.hpp"
@@ -250,17 +248,6 @@ __device__ __forceinline__ float disp_value_cached(rsrc_t rd, const DispGeo& g, 
     return (1.f - r.ly) * c.dA + r.ly * c.dB;
 }
 
-// Branch-free: the two source rows are re-read every image row (they sit in L1; a cached row pair would cost a
-// branch and register copies in the hot loop).  Same association as ATen's upsample_bilinear2d.
-__device__ __forceinline__ float disp_value(rsrc_t rd, const DispGeo& g, int yr) {
-    if (g.f == 1) return ldb(rd, (unsigned)(yr * g.Ws + g.x0) * 4u, 0u);
-    const RowLerp r = row_lerp(g, yr);
-    const float v00 = ldb(rd, (unsigned)(r.y0 * g.Ws + g.x0) * 4u, 0u), v01 = ldb(rd, (unsigned)(r.y0 * g.Ws + g.x1) * 4u, 0u);
-    const float v10 = ldb(rd, (unsigned)(r.y1 * g.Ws + g.x0) * 4u, 0u), v11 = ldb(rd, (unsigned)(r.y1 * g.Ws + g.x1) * 4u, 0u);
-    const float hx = 1.f - g.lx;
-    return (1.f - r.ly) * (hx * v00 + g.lx * v01) + r.ly * (hx * v10 + g.lx * v11);
-}
-
 // ---------------------------------------------------------------------------------------------- SSIM
 // Window statistics with every factor scaled by 81 (mu = S/9) and sums taken of (value - SHIFT):
 //   n = (2 mu_x mu_y + C1)(2 sigma_xy + C2),  d = (mu_x^2 + mu_y^2 + C1)(sigma_x + sigma_y + C2)   MD2/layers.py:243-253
@@ -312,10 +299,6 @@ struct KArgs {
 __host__ inline int pick_rows(int B, int H, int W, int out_cols) {
     const int tx = (W + out_cols - 1) / out_cols;
     const int64_t want = out_cols == FW_OUT ? 8192 : 4096;   // forward strips are 1 wave each, backward strips 1 per scale
-    if (const char* e = getenv("DMH_K1_ROWS")) {   // tuning knob (tools/kbench.py)
-        const int v = atoi(e);
-        if (v >= 2 && v <= 1024) return v;
-    }
     if (out_cols == FW_OUT) {
         int R = 32;
         while (R > 8 && (int64_t)B * tx * ((H + R - 1) / R) < want) R >>= 1;
@@ -342,28 +325,21 @@ struct FRow {   // row sums of one image row: target (y, y^2) and per stream (x,
 };
 
 // ------------------------------------------------------------------------------------------------ forward
-// NF source frames, SPP + SPL scales per pass.  The rolling row sums of the identity term, of the (optional) hint view and
-// of the first SPP scales live in registers (NF * (1 + SPP) streams); those of the next SPL scales live in LDS, private to
-// the wave (2 records x 3 x 16 B per lane and stream, lane-linear 16-byte words: conflict-free ds_read/write_b128, no
-// barrier).  With one source frame that allows ONE pass of four scales (target sums, identity term and tie-break noise
-// formed once instead of twice) -- measured slower than two passes of two scales, see the launch site; kept selectable.
+// NF source frames, SPP scales per pass.  The rolling row sums of the identity term, of the (optional) hint view and of the
+// SPP scales live in registers (NF * (1 + SPP) streams).  (Keeping the row sums of two more scales in LDS allowed ONE pass
+// of four scales with one source frame -- measured slower than two passes of two scales, see the launch site; removed.)
 // HINT: DepthHints' extra candidate (DH/trainer.py:510-525,629-636,700-725): the source view warped with the depth
 // HINT is one more stream (formed per pass, like the identity term), the per-pixel argmin runs over [reprojection,
 // identity, hint], and where the hint wins the proxy log-L1 term is accumulated.
 // FL >= 0: the option flags as compile-time constants (bit 0 automask, bit 1 no_ssim, bit 2 MD2 variant, bits 3-4 noise
 // mode): the hot configurations get straight-line code without the flag branches and their merge copies; FL = -1 reads the
 // flags at run time (every other combination).
-template <int NF, int SPP, int SPL, bool HINT, int MINW = DMH_FWD_WAVES, int FL = -1>
+template <int NF, int SPP, bool HINT, int MINW = DMH_FWD_WAVES, int FL = -1>
 __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
     constexpr int NSTR = NF * (1 + SPP) + (HINT ? 1 : 0);      // streams with register-resident row sums
     constexpr int ST_HINT = NF * (1 + SPP);
-    constexpr int SPT = SPP + SPL;                             // scales per pass
-    constexpr int NVAL = NSTR + NF * SPL;                      // candidates per pixel: val[] slots
-    constexpr int LREC = 3 * WAVE;                             // float4 words of one LDS record (one stream, one row)
-    __shared__ float4 s_rec[SPL > 0 ? WPB * SPL * NF * 2 * LREC : 1];
     const dmh_photo_args& a = k.a;
     const int lane = threadIdx.x & (WAVE - 1);
-    float4* const lrec = s_rec + (SPL > 0 ? (threadIdx.x >> 6) * (SPL * NF * 2 * LREC) : 0) + lane;
     const int tile = wave_item();
     if (tile >= k.ntiles) return;
     const int H = a.H, W = a.W, NS = a.num_scales;
@@ -392,7 +368,7 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
     const bool md2 = FL >= 0 ? (FL & 4) != 0 : a.variant == DMH_VARIANT_MD2;
     const int noise_mode = FL >= 0 ? ((FL >> 3) & 3) : a.noise_mode;
     const int nf_noise = md2 ? NF : 1;
-    const int npass = (NS + SPT - 1) / SPT;
+    const int npass = (NS + SPP - 1) / SPP;
     const Philox<7> rng(a.seed);
     const rsrc_t rhint = make_rsrc(HINT ? a.depth_hint + (size_t)b * H * W : a.target, (unsigned)(H * W) * 4u);
     const rsrc_t rhmask = make_rsrc(HINT ? a.depth_hint_mask + (size_t)b * H * W : a.target, (unsigned)(H * W) * 4u);
@@ -401,33 +377,30 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
     const float hsx = (float)W / (float)(W - 1), hsy = (float)H / (float)(H - 1);
     const float hox = (float)xr / (float)(W - 1) - 0.5f;
 
-    for (int s0 = 0, pass = 0; s0 < NS; s0 += SPT, ++pass) {
+    for (int s0 = 0, pass = 0; s0 < NS; s0 += SPP, ++pass) {
         DispGeo dg[SPP];
         DispRow dr[SPP];
-        rsrc_t rd[SPT];
+        rsrc_t rd[SPP];
 #pragma unroll
-        for (int j = 0; j < SPT; ++j) {
+        for (int j = 0; j < SPP; ++j) {
             const int s = min(s0 + j, NS - 1);
-            if (j < SPP) {
-                dg[j] = disp_geo(a.Hs[s], a.Ws[s], H, W, xr);
-                dr[j].y0 = -1;
-                dr[j].dA = dr[j].dB = 0.f;
-            }
+            dg[j] = disp_geo(a.Hs[s], a.Ws[s], H, W, xr);
+            dr[j].y0 = -1;
+            dr[j].dA = dr[j].dB = 0.f;
             rd[j] = make_rsrc(a.disp[s] + (size_t)b * a.Hs[s] * a.Ws[s], (unsigned)(a.Hs[s] * a.Ws[s]) * 4u);
         }
         FRow<NSTR> rowA, rowB;
         float l1p[NSTR];       // L1 of the previous row (the centre row of the next window)
-        float acc1[SPT], acc2[SPT], acc3[SPT], acc4[SPT];
-        float sd_prev[SPT];    // scaled disparity of the previous row (depth of the centre row, for the hint term)
+        float acc1[SPP], acc2[SPP], acc3[SPP], acc4[SPP];
+        float sd_prev[SPP];    // scaled disparity of the previous row (depth of the centre row, for the hint term)
 #pragma unroll
-        for (int j = 0; j < SPT; ++j) acc1[j] = acc2[j] = acc3[j] = acc4[j] = sd_prev[j] = 0.f;
+        for (int j = 0; j < SPP; ++j) acc1[j] = acc2[j] = acc3[j] = acc4[j] = sd_prev[j] = 0.f;
 #pragma unroll
         for (int i = 0; i < NSTR; ++i) l1p[i] = 0.f;
 
         // One image row: `older` / `newer` are the row sums of the two rows above; the finished centre row is
-        // the one in between; the current row's sums replace `older`.  `par` = kk & 1 as a literal: the LDS-resident
-        // streams keep `older` in record par and `newer` in record par ^ 1.
-        auto step = [&](const int kk, FRow<NSTR>& older, const FRow<NSTR>& newer, const int par) __attribute__((always_inline)) {
+        // the one in between; the current row's sums replace `older`.
+        auto step = [&](const int kk, FRow<NSTR>& older, const FRow<NSTR>& newer) __attribute__((always_inline)) {
             const int r = Y0 - 1 + kk;
             const int yr = reflect_idx(r, H);
             const unsigned rowoff = (unsigned)(yr * W + xr) * 4u;
@@ -444,7 +417,7 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
                 older.ty[c] = hy;
                 older.tyy[c] = hyy;
             }
-            float val[NVAL];
+            float val[NSTR];
             // accumulate one stream: xv = this row's (shifted) values of the stream
             auto stream = [&](const int st, const float (&xv)[3]) __attribute__((always_inline)) {
                 float ss = 0.f, l1 = 0.f;
@@ -462,24 +435,6 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
                 // compute_reprojection_loss (MD2/trainer.py:525-537) of the centre row: its L1 was formed one row ago
                 val[st] = no_ssim ? l1p[st] * (1.f / 3.f) : (0.85f / 3.f) * ss + (0.15f / 3.f) * l1p[st];
                 l1p[st] = l1;
-            };
-            // the same for a stream whose two row-sum records live in LDS (slot ls), candidate slot vi: one 16-byte word per
-            // channel (sx, sxx, sxy, l1 of the row) read just before use; same association of the sums as above
-            auto stream_lds = [&](const int ls, const int vi, const float (&xv)[3]) __attribute__((always_inline)) {
-                float4* const ro = lrec + (ls * 2 + par) * LREC;
-                const float4* const rn = lrec + (ls * 2 + (par ^ 1)) * LREC;
-                float ss = 0.f, l1 = 0.f, l1prev = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float4 o = ro[c * WAVE], n = rn[c * WAVE];
-                    const float hx = hsum3(xv[c]), hxx = hsum3(xv[c] * xv[c]), hxy = hsum3(xv[c] * tv[c]);
-                    if (emit && !no_ssim) ss += ssim_val(o.x + n.x + hx, o.y + n.y + hxx, o.z + n.z + hxy, tw[c]);
-                    const float l1c = fabsf(tv[c] - xv[c]);
-                    l1 += l1c;
-                    l1prev += n.w;
-                    ro[c * WAVE] = make_float4(hx, hxx, hxy, l1c);
-                }
-                val[vi] = no_ssim ? l1prev * (1.f / 3.f) : (0.85f / 3.f) * ss + (0.15f / 3.f) * l1prev;
             };
             if (automask) {
 #pragma unroll
@@ -520,18 +475,12 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
                 }
                 stream(ST_HINT, xv);
             }
-            float sd_centre[SPT];
+            float sd_centre[SPP];
 #pragma unroll
-            for (int j = 0; j < SPT; ++j) {
+            for (int j = 0; j < SPP; ++j) {
                 if constexpr (HINT) sd_centre[j] = sd_prev[j];
                 if (s0 + j >= NS) break;
-                float d;
-                if (j < SPP) {
-                    d = disp_value_cached(rd[j], dg[j], dr[j], yr);
-                } else {    // LDS-resident scale: its up-sampling geometry is re-formed per row instead of held in registers
-                    const int s = s0 + j;
-                    d = disp_value(rd[j], disp_geo(a.Hs[s], a.Ws[s], H, W, xr), yr);
-                }
+                const float d = disp_value_cached(rd[j], dg[j], dr[j], yr);
                 const float sd = fmaf(k.dmul, d, k.min_disp);
                 if constexpr (HINT) sd_prev[j] = sd;
 #pragma unroll
@@ -548,8 +497,7 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
                         xv[c] = (ldb(rsrc[f], t.o00, po) * w00 + ldb(rsrc[f], t.o01, po) * w01 + ldb(rsrc[f], t.o10, po) * w10 +
                                  ldb(rsrc[f], t.o11, po) * w11) - SHIFT;
                     }
-                    if (j < SPP) stream(NF + j * NF + f, xv);
-                    else stream_lds((j - SPP) * NF + f, NSTR + (j - SPP) * NF + f, xv);
+                    stream(NF + j * NF + f, xv);
                 }
             }
             if (!emit) return;
@@ -573,14 +521,14 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
             }
             unsigned bits = 0u;
 #pragma unroll
-            for (int j = 0; j < SPT; ++j) {
+            for (int j = 0; j < SPP; ++j) {
                 if (s0 + j >= NS) break;
                 const int s = s0 + j;
                 float best = 3.0e38f;
                 int bestf = 0;
 #pragma unroll
                 for (int f = 0; f < NF; ++f) {
-                    const float v = val[j < SPP ? NF + j * NF + f : NSTR + (j - SPP) * NF + f];
+                    const float v = val[NF + j * NF + f];
                     if (v < best) {
                         best = v;
                         bestf = f;
@@ -643,12 +591,12 @@ __global__ __launch_bounds__(NT, MINW) void photo_fwd_kernel(const KArgs k) {
         // state in fixed registers (a conditional second step cost ~60 register copies per iteration at the merge); with an
         // odd row count the last step runs on a row past the strip's end and emits nothing
         for (int kk = 0; kk < nrows; kk += 2) {
-            step(kk, rowA, rowB, 0);
-            step(kk + 1, rowB, rowA, 1);
+            step(kk, rowA, rowB);
+            step(kk + 1, rowB, rowA);
         }
         // fixed-order wave sums -> one partial pair per (scale, strip)
 #pragma unroll
-        for (int j = 0; j < SPT; ++j) {
+        for (int j = 0; j < SPP; ++j) {
             if (s0 + j >= NS) break;
             const float t1 = wave_sum(acc1[j]), t2 = wave_sum(acc2[j]);
             const float t3 = HINT ? wave_sum(acc3[j]) : 0.f, t4 = HINT ? wave_sum(acc4[j]) : 0.f;
@@ -1117,19 +1065,16 @@ int dmh_photo_loss_fwd(const dmh_photo_args* a, uint8_t* sel, float* const to_op
     switch (a->num_frames) {
         // one source frame: two passes of two scales (3 streams of row sums in registers, 160 VGPRs, 3 waves/SIMD).  Measured
         // alternatives (profiles/README.md): one pass of four scales with all five streams in registers (229 VGPRs, 2
-        // waves/SIMD; round 2) +10 %; one pass with the row sums of scales 2-3 in wave-private LDS (round 3, this kernel with
-        // SPL = 2: 10 % fewer VALU instructions, but 194 VGPRs = 2 waves/SIMD, or 168 with scratch spills) +20 %:
-        // DMH_K1_FWD_VARIANT=2 selects it for timing comparisons.
+        // waves/SIMD; round 2) +10 %; one pass with the row sums of scales 2-3 in wave-private LDS (round 3: 10 % fewer VALU
+        // instructions, but 194 VGPRs = 2 waves/SIMD, or 168 with scratch spills) +20 %.  Both have been removed.
         case 1: {
-            static const int variant = getenv("DMH_K1_FWD_VARIANT") ? atoi(getenv("DMH_K1_FWD_VARIANT")) : 0;
-            if (a->depth_hint) hipLaunchKernelGGL((photo_fwd_kernel<1, 2, 0, true>), grid, block, 0, (hipStream_t)stream, k);
-            else if (variant == 2) hipLaunchKernelGGL((photo_fwd_kernel<1, 2, 2, false>), grid, block, 0, (hipStream_t)stream, k);
-            else if (variant == 1 || !a->automask || a->no_ssim)
-                hipLaunchKernelGGL((photo_fwd_kernel<1, 2, 0, false>), grid, block, 0, (hipStream_t)stream, k);
+            if (a->depth_hint) hipLaunchKernelGGL((photo_fwd_kernel<1, 2, true>), grid, block, 0, (hipStream_t)stream, k);
+            else if (!a->automask || a->no_ssim)
+                hipLaunchKernelGGL((photo_fwd_kernel<1, 2, false>), grid, block, 0, (hipStream_t)stream, k);
             else {      // the training configurations: flags as constants
                 const bool md2 = a->variant == DMH_VARIANT_MD2;
 #define DMH_K1_FWD_FL(MD2, NOISE) \
-    hipLaunchKernelGGL((photo_fwd_kernel<1, 2, 0, false, 3, 1 | ((MD2) << 2) | ((NOISE) << 3)>), grid, block, 0, (hipStream_t)stream, k)
+    hipLaunchKernelGGL((photo_fwd_kernel<1, 2, false, 3, 1 | ((MD2) << 2) | ((NOISE) << 3)>), grid, block, 0, (hipStream_t)stream, k)
                 if (a->noise_mode == DMH_NOISE_PHILOX) { if (md2) DMH_K1_FWD_FL(1, DMH_NOISE_PHILOX); else DMH_K1_FWD_FL(0, DMH_NOISE_PHILOX); }
                 else if (a->noise_mode == DMH_NOISE_TENSOR) { if (md2) DMH_K1_FWD_FL(1, DMH_NOISE_TENSOR); else DMH_K1_FWD_FL(0, DMH_NOISE_TENSOR); }
                 else { if (md2) DMH_K1_FWD_FL(1, DMH_NOISE_NONE); else DMH_K1_FWD_FL(0, DMH_NOISE_NONE); }
@@ -1137,8 +1082,8 @@ int dmh_photo_loss_fwd(const dmh_photo_args* a, uint8_t* sel, float* const to_op
             }
             break;
         }
-        case 2: hipLaunchKernelGGL((photo_fwd_kernel<2, 2, 0, false>), grid, block, 0, (hipStream_t)stream, k); break;
-        default: hipLaunchKernelGGL((photo_fwd_kernel<3, 1, 0, false>), grid, block, 0, (hipStream_t)stream, k); break;
+        case 2: hipLaunchKernelGGL((photo_fwd_kernel<2, 2, false>), grid, block, 0, (hipStream_t)stream, k); break;
+        default: hipLaunchKernelGGL((photo_fwd_kernel<3, 1, false>), grid, block, 0, (hipStream_t)stream, k); break;
     }
     return check_launch("dmh_photo_loss_fwd");
 }

@@ -16,7 +16,6 @@
 // Backward = a gather over the same index map (deterministic, no atomics); positions no window entry reads get 0.
 //
 //   roi_cost : cost = sum_b sum_window (sigmoid(d_pre) * mask)^2 / (B H W)        (mask is the full-frame K3 output)
-#include <stdlib.h>
 
 #include "common.hpp"
 
@@ -46,7 +45,7 @@ __device__ __forceinline__ void split_rc(int t, int w2, unsigned magic, int& row
 template <int CPT>
 __global__ __launch_bounds__(NT) void roi_glue_fwd_kernel(const dmh_roi_glue_args a, unsigned magic, float* __restrict__ out) {
     // CPT consecutive channel planes of one part (the up-sampled y planes, or the skip planes) of one sample per thread: they
-    // share the index map, so it is formed once (see roi_glue_bwd2_kernel)
+    // share the index map, so it is formed once (the backward gather gains nothing from that: see roi_glue_bwd2_kernel)
     const int PH = a.hc + 2, PW = a.wc + 2, C = a.C1 + a.C2;
     const int t = blockIdx.x * NT + threadIdx.x;                // PW is even: a pair never straddles two rows
     if (2 * t >= PH * PW) return;
@@ -218,17 +217,16 @@ struct Region2 {
     unsigned ymagic, kmagic;    // ceil(2^32 / (width / 2)) of the two parts
     int yblocks, kblocks;       // blocks along x of the two parts
 };
-template <int CPT>
 __global__ __launch_bounds__(NT) void roi_glue_bwd2_kernel(const dmh_roi_glue_args a, const Region2 r2,
                                                            const float* __restrict__ g_out, float* __restrict__ g_y,
                                                            float* __restrict__ g_skip) {
-    // CPT consecutive channel planes of one sample per thread: the planes of a sample share their geometry (origins, window
-    // offsets, the fast-path test), so the index arithmetic is done once and a block moves CPT times the bytes.  Measured: no
-    // gain here (see the launcher: the default is CPT = 1); the forward kernel, roi_crop and roi_paste take 5-15 % from it.
+    // One channel plane per thread.  The forward kernel, roi_crop and roi_paste take 5-15 % from several consecutive planes of
+    // a sample per thread (shared index arithmetic); this gather does not: with eight planes it ran at HALF the speed of one
+    // (3.6 against 1.97 ms per step, profiles/README.md round 6), whichever way its three cases were laid out.
     const Region& rg = r2.rg;
     const int PH = a.hc + 2, PW = a.wc + 2, C = a.C1 + a.C2;
-    // flat grid: the blocks of the g_y plane groups, then those of the g_skip plane groups (uniform decode: scalar divisions)
-    const int ytotal = r2.yblocks * a.B * (a.C1 / CPT);
+    // flat grid: the blocks of the g_y planes, then those of the g_skip planes (uniform decode: scalar divisions)
+    const int ytotal = r2.yblocks * a.B * a.C1;
     const bool ypart = (int)blockIdx.x < ytotal;
     const int bid = ypart ? (int)blockIdx.x : (int)blockIdx.x - ytotal;
     const int per = ypart ? r2.yblocks : r2.kblocks;
@@ -236,8 +234,7 @@ __global__ __launch_bounds__(NT) void roi_glue_bwd2_kernel(const dmh_roi_glue_ar
     const int t = (bid - pl * per) * NT + (int)threadIdx.x;
     const size_t gplane = (size_t)PH * PW;
     if (ypart) {
-        const int groups = a.C1 / CPT;
-        const int b = pl / groups, c0 = (pl - b * groups) * CPT;
+        const int b = pl / a.C1, c0 = pl - b * a.C1;
         const int w2 = rg.yw >> 1;
         if (t >= rg.yh * w2) return;
         const int oy = a.dst_org[2 * b], ox = a.dst_org[2 * b + 1];
@@ -251,8 +248,7 @@ __global__ __launch_bounds__(NT) void roi_glue_bwd2_kernel(const dmh_roi_glue_ar
         }
         const int Ys = sy0 + yy, Xs = sx0 + xx;
         const float* gp = g_out + (size_t)(b * C + c0) * gplane;
-        const size_t splane = (size_t)a.sh * a.sw;
-        size_t o = ((size_t)(b * a.C1 + c0) * a.sh + yy) * a.sw + xx;
+        const size_t o = ((size_t)(b * a.C1 + c0) * a.sh + yy) * a.sw + xx;
         int fast = 0, off = 0;              // 1: up-sampled, all eight entries inside; 2: plain, both entries inside
         if (a.up) {
             const int Y0 = 2 * Ys, X0 = 2 * Xs, r = Y0 + 1 - oy, q = X0 + 1 - ox;
@@ -267,48 +263,37 @@ __global__ __launch_bounds__(NT) void roi_glue_bwd2_kernel(const dmh_roi_glue_ar
                 off = r * PW + q;
             }
         }
-        // the three cases as three loops (fast is per thread, but the common case must not carry the general path's code in
-        // every unrolled iteration: a first version did, and ran at half the speed of the one-plane kernel)
+        // the three cases apart (fast is per thread, but the common case must not carry the general path's code)
         if (fast == 1) {
-#pragma unroll
-            for (int j = 0; j < CPT; ++j, gp += gplane, o += splane) {
-                const float* p0 = gp + off;
-                float v0 = p0[0] + p0[1] + p0[PW] + p0[PW + 1];
-                float v1 = p0[2] + p0[3] + p0[PW + 2] + p0[PW + 3];
-                if (a.elu) {
-                    const float2 yv = *reinterpret_cast<const float2*>(a.y + o);
-                    v0 = v0 != 0.f ? v0 * elu_grad(yv.x) : v0;
-                    v1 = v1 != 0.f ? v1 * elu_grad(yv.y) : v1;
-                }
-                *reinterpret_cast<float2*>(g_y + o) = make_float2(v0, v1);
+            const float* p0 = gp + off;
+            float v0 = p0[0] + p0[1] + p0[PW] + p0[PW + 1];
+            float v1 = p0[2] + p0[3] + p0[PW + 2] + p0[PW + 3];
+            if (a.elu) {
+                const float2 yv = *reinterpret_cast<const float2*>(a.y + o);
+                v0 = v0 != 0.f ? v0 * elu_grad(yv.x) : v0;
+                v1 = v1 != 0.f ? v1 * elu_grad(yv.y) : v1;
             }
+            *reinterpret_cast<float2*>(g_y + o) = make_float2(v0, v1);
         } else if (fast == 2) {
-#pragma unroll
-            for (int j = 0; j < CPT; ++j, gp += gplane, o += splane) {
-                float v0 = gp[off], v1 = gp[off + 1];
-                if (a.elu) {
-                    const float2 yv = *reinterpret_cast<const float2*>(a.y + o);
-                    v0 = v0 != 0.f ? v0 * elu_grad(yv.x) : v0;
-                    v1 = v1 != 0.f ? v1 * elu_grad(yv.y) : v1;
-                }
-                *reinterpret_cast<float2*>(g_y + o) = make_float2(v0, v1);
+            float v0 = gp[off], v1 = gp[off + 1];
+            if (a.elu) {
+                const float2 yv = *reinterpret_cast<const float2*>(a.y + o);
+                v0 = v0 != 0.f ? v0 * elu_grad(yv.x) : v0;
+                v1 = v1 != 0.f ? v1 * elu_grad(yv.y) : v1;
             }
+            *reinterpret_cast<float2*>(g_y + o) = make_float2(v0, v1);
         } else {
-#pragma unroll 1
-            for (int j = 0; j < CPT; ++j, gp += gplane, o += splane) {
-                float v0 = glue_bwd_y_elem(a, gp, Ys, Xs, oy, ox, PH, PW);
-                float v1 = glue_bwd_y_elem(a, gp, Ys, Xs + 1, oy, ox, PH, PW);
-                if (a.elu) {
-                    const float2 yv = *reinterpret_cast<const float2*>(a.y + o);
-                    v0 = v0 != 0.f ? v0 * elu_grad(yv.x) : v0;
-                    v1 = v1 != 0.f ? v1 * elu_grad(yv.y) : v1;
-                }
-                *reinterpret_cast<float2*>(g_y + o) = make_float2(v0, v1);
+            float v0 = glue_bwd_y_elem(a, gp, Ys, Xs, oy, ox, PH, PW);
+            float v1 = glue_bwd_y_elem(a, gp, Ys, Xs + 1, oy, ox, PH, PW);
+            if (a.elu) {
+                const float2 yv = *reinterpret_cast<const float2*>(a.y + o);
+                v0 = v0 != 0.f ? v0 * elu_grad(yv.x) : v0;
+                v1 = v1 != 0.f ? v1 * elu_grad(yv.y) : v1;
             }
+            *reinterpret_cast<float2*>(g_y + o) = make_float2(v0, v1);
         }
     } else {
-        const int groups = a.C2 / CPT;
-        const int b = pl / groups, c0 = (pl - b * groups) * CPT;
+        const int b = pl / a.C2, c0 = pl - b * a.C2;
         const int w2 = rg.kw >> 1;
         if (t >= rg.kh * w2) return;
         const int oy = a.dst_org[2 * b], ox = a.dst_org[2 * b + 1];
@@ -325,19 +310,13 @@ __global__ __launch_bounds__(NT) void roi_glue_bwd2_kernel(const dmh_roi_glue_ar
         const int r = Ys + 1 - oy, qq = Xs + 1 - ox;
         const bool fast = Ys > 1 && Ys < a.H - 2 && Xs > 1 && Xs + 1 < a.W - 2 && r >= 0 && r < PH && qq >= 0 && qq + 1 < PW;
         const bool in0 = Ys > 1 && Ys < a.H - 2 && Xs > 1 && Xs < a.W - 2, in1 = Ys > 1 && Ys < a.H - 2 && Xs + 1 > 1 && Xs + 1 < a.W - 2;
-        const size_t kplane = (size_t)a.kh * a.kw;
         float* gs = g_skip + ((size_t)(b * a.C2 + c0) * a.kh + yy) * a.kw + xx;
         if (fast) {
-#pragma unroll
-            for (int j = 0; j < CPT; ++j, gp += gplane, gs += kplane)
-                *reinterpret_cast<float2*>(gs) = make_float2(gp[r * PW + qq], gp[r * PW + qq + 1]);
+            *reinterpret_cast<float2*>(gs) = make_float2(gp[r * PW + qq], gp[r * PW + qq + 1]);
         } else {
-#pragma unroll 1
-            for (int j = 0; j < CPT; ++j, gp += gplane, gs += kplane) {
-                const float v0 = in0 ? gather_interior(gp, Ys, Xs, oy, ox, PH, PW) : gather_pad(gp, Ys, Xs, a.H, a.W, oy, ox, PH, PW);
-                const float v1 = in1 ? gather_interior(gp, Ys, Xs + 1, oy, ox, PH, PW) : gather_pad(gp, Ys, Xs + 1, a.H, a.W, oy, ox, PH, PW);
-                *reinterpret_cast<float2*>(gs) = make_float2(v0, v1);
-            }
+            const float v0 = in0 ? gather_interior(gp, Ys, Xs, oy, ox, PH, PW) : gather_pad(gp, Ys, Xs, a.H, a.W, oy, ox, PH, PW);
+            const float v1 = in1 ? gather_interior(gp, Ys, Xs + 1, oy, ox, PH, PW) : gather_pad(gp, Ys, Xs + 1, a.H, a.W, oy, ox, PH, PW);
+            *reinterpret_cast<float2*>(gs) = make_float2(v0, v1);
         }
     }
 }
@@ -441,9 +420,8 @@ int dmh_roi_glue_bwd(const dmh_roi_glue_args* a, const float* g_out, float* g_y,
     const int planes = a->B * a->C1 + (skip ? a->B * a->C2 : 0);
     const int64_t ny = (int64_t)rg.yh * rg.yw, nk = skip ? (int64_t)rg.kh * rg.kw : 0;
     // two elements per thread where every width involved is even and every base 8-byte aligned (the window plan's sizes and
-    // origins all are; DMH_ROI_GLUE2=0: the one-element kernel, A/B switch)
-    static const bool wide_ok = !(getenv("DMH_ROI_GLUE2") && atoi(getenv("DMH_ROI_GLUE2")) == 0);
-    bool wide = wide_ok && !(rg.yw & 1) && !(a->sw & 1) && !(((uintptr_t)g_y | (uintptr_t)a->y) & 7) &&
+    // origins all are); otherwise the one-element kernel
+    const bool wide = !(rg.yw & 1) && !(a->sw & 1) && !(((uintptr_t)g_y | (uintptr_t)a->y) & 7) &&
                 (!skip || (!(rg.kw & 1) && !(a->kw & 1) && !((uintptr_t)g_skip & 7)));
     if (wide) {
         Region2 r2;
@@ -453,18 +431,10 @@ int dmh_roi_glue_bwd(const dmh_roi_glue_args* a, const float* g_out, float* g_y,
         r2.kmagic = (unsigned)(((uint64_t)1 << 32) / kw2) + 1u;
         r2.yblocks = (int)blocks_for(ny / 2);
         r2.kblocks = skip ? (int)blocks_for(nk / 2) : 1;
-        const int c2 = skip ? a->C2 : 0;
-        // planes per thread: ONE.  The forward kernel, the crops and the pastes gain 5-15 % from eight planes per thread (shared
-        // index map); this gather does not -- with eight planes it ran at HALF the speed of one (3.6 against 1.97 ms per step,
-        // profiles/README.md round 6), whichever way its three cases were laid out: DMH_ROI_GLUE_CPT=8 / 4 keeps it measurable
-        static const int cpt_env = getenv("DMH_ROI_GLUE_CPT") ? atoi(getenv("DMH_ROI_GLUE_CPT")) : 1;
-        const int cpt = (cpt_env == 8 && a->C1 % 8 == 0 && c2 % 8 == 0) ? 8 : ((cpt_env >= 4 && a->C1 % 4 == 0 && c2 % 4 == 0) ? 4 : 1);
-        const int64_t total = (int64_t)r2.yblocks * a->B * (a->C1 / cpt) + (skip ? (int64_t)r2.kblocks * a->B * (c2 / cpt) : 0);
+        const int64_t total = (int64_t)r2.yblocks * a->B * a->C1 + (skip ? (int64_t)r2.kblocks * a->B * a->C2 : 0);
         DMH_REQUIRE(total < ((int64_t)1 << 31), "too many blocks");
         const dim3 grid((unsigned)total);
-        if (cpt == 8) hipLaunchKernelGGL(roi_glue_bwd2_kernel<8>, grid, dim3(NT), 0, (hipStream_t)stream, *a, r2, g_out, g_y, g_skip);
-        else if (cpt == 4) hipLaunchKernelGGL(roi_glue_bwd2_kernel<4>, grid, dim3(NT), 0, (hipStream_t)stream, *a, r2, g_out, g_y, g_skip);
-        else hipLaunchKernelGGL(roi_glue_bwd2_kernel<1>, grid, dim3(NT), 0, (hipStream_t)stream, *a, r2, g_out, g_y, g_skip);
+        hipLaunchKernelGGL(roi_glue_bwd2_kernel, grid, dim3(NT), 0, (hipStream_t)stream, *a, r2, g_out, g_y, g_skip);
         return check_launch("dmh_roi_glue_bwd");
     }
     hipLaunchKernelGGL(roi_glue_bwd_kernel, dim3(blocks_for(ny > nk ? ny : nk), planes), dim3(NT), 0, (hipStream_t)stream, *a,

@@ -9,8 +9,6 @@
 // The loss is positively homogeneous of degree 1 in norm, which gives the backward in one pass:
 //   d smooth / d disp_j = G_j/|den_b| - R_b * sign(den_b) / (den_b^2 * H*W),  den_b = mean_b + 1e-7.
 // Pure HBM streaming (16 B per low-resolution pixel); no LDS tiling needed beyond the block reduce.
-#include <stdlib.h>
-
 #include "common.hpp"
 
 using namespace dmh;
@@ -418,7 +416,7 @@ int dmh_smooth_loss_bwd(const dmh_smooth_args* a, const float* gvec, const float
         k.g_disp[s] = g_disp[s];
     }
     // four-wide kernel: every scale's width a multiple of 4 and every row of disp / color / g_disp 16-byte aligned
-    bool vec4 = !(getenv("DMH_K2_BWD_SCALAR") && atoi(getenv("DMH_K2_BWD_SCALAR")) != 0);
+    bool vec4 = true;
     for (int s = 0; s < a->num_scales; ++s)
         vec4 = vec4 && a->Ws[s] % 4 == 0 && ((uintptr_t)a->disp[s] % 16) == 0 && ((uintptr_t)a->color[s] % 16) == 0 &&
                ((uintptr_t)g_disp[s] % 16) == 0 && ((size_t)a->Hs[s] * a->Ws[s]) % 4 == 0;

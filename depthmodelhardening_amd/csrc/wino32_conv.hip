@@ -32,13 +32,11 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// DMH_W32_PK (round 6, as DMH_WINO_PK in wino_conv.hip): the input transform on packed fp32 adds -- the raw rows of a thread's
+// Round 6 (as in wino_conv.hip): the input transform on packed fp32 adds -- the raw rows of a thread's
 // channel pair are interleaved in LDS ([pair][row][channel of the pair][word]), one ds_read2_b32 fetches a patch element of both
 // channels into a register pair, both stages are v_pk_add_f32 on such pairs (56 instead of 112 per chunk), and the results are
-// the (channel, channel + 1) pairs the 8-byte image writes want.  Same additions in the same order: bit-identical results.
-#ifndef DMH_W32_PK
-#define DMH_W32_PK 1
-#endif
+// the (channel, channel + 1) pairs the 8-byte image writes want.  Same additions in the same order as the scalar transform of
+// round 5 (since removed): bit-identical results.
 constexpr int CK = 8;                       // input channels per chunk
 constexpr int NT = 256;
 constexpr int TRW = 32, TRH = 4;            // tile region of an item
@@ -48,7 +46,7 @@ constexpr int RWA = 4 * NWR;                // LDS row pitch in floats (72)
 constexpr int RAW_N = CK * RH * NWR;        // 1440 words
 constexpr int RAW_PER_T = (RAW_N + NT - 1) / NT;   // 6 loads per thread and chunk (dword loads: 21)
 constexpr int RAW_BUF = RAW_N * 4;          // floats per raw buffer (23 KB)
-constexpr int PKI = DMH_W32_PK ? 2 : 1;     // DMH_W32_PK: the rows of a channel pair are interleaved
+constexpr int PKI = 2;                      // the rows of a channel pair are interleaved
 constexpr int UBUF = 16 * 2 * 32;           // f32x4 words of one U chunk image (16 KB)
 constexpr int VBUF = 16 * 2 * 128;          // f32x4 words of the V image (64 KB)
 
@@ -152,7 +150,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         const int cbase = (it.b * a.C + cb_ * CK) * (int)HW;                                      \
         _Pragma("unroll") for (int k = 0; k < RAW_PER_T; ++k) {                                   \
             const int e = tid_o + NT * k;                                                         \
-            /* LDS order: [channel][row][word]; DMH_W32_PK: [channel pair][row][channel of the pair][word] */ \
+            /* LDS order: [channel pair][row][channel of the pair][word] */                                    \
             const int cq = e / (PKI * RH * NWR), r1 = e - cq * (PKI * RH * NWR), rr = r1 / (PKI * NWR), r2 = r1 - rr * (PKI * NWR); \
             const int c = PKI * cq + r2 / NWR, xx = 4 * (r2 % NWR);                               \
             const int iy = iy0 + rr, ix = ix0 + xx;                                               \
@@ -194,7 +192,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     // the raw patch at RS): the horizontal stage d B is taken once per raw row -- six rows instead of two times four (24
     // instead of 32 LDS words read, 56 instead of 64 additions per channel) --, the vertical stage B^T (.) per tile.
     // V words at VD (upper tile) and VD + 32 words (the tile below it).
-#if DMH_W32_PK
 #define DMH_W32_TRANSFORM_PAIR(RS, VD)                                                            \
     {                                                                                             \
         f32x2 h_[6][4];         /* (channel, channel + 1) pairs */                                \
@@ -217,33 +214,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             }                                                                                     \
         }                                                                                         \
     }
-#else
-#define DMH_W32_TRANSFORM_PAIR(RS, VD)                                                            \
-    {                                                                                             \
-        float h_[2][6][4];                                                                        \
-        _Pragma("unroll") for (int ch_ = 0; ch_ < 2; ++ch_) {                                     \
-            _Pragma("unroll") for (int i = 0; i < 6; ++i) {                                       \
-                const float* row_ = (RS) + ch_ * (RH * RWA) + i * RWA;    /* 4-byte aligned only */ \
-                const float d0_ = row_[0], d1_ = row_[1], d2_ = row_[2], d3_ = row_[3];           \
-                h_[ch_][i][0] = d0_ - d2_;                                                        \
-                h_[ch_][i][1] = d1_ + d2_;                                                        \
-                h_[ch_][i][2] = d2_ - d1_;                                                        \
-                h_[ch_][i][3] = d1_ - d3_;                                                        \
-            }                                                                                     \
-        }                                                                                         \
-        _Pragma("unroll") for (int tv_ = 0; tv_ < 2; ++tv_) {                                     \
-            float* const vd_ = (VD) + tv_ * (32 * 4);                                             \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                       \
-                const float a0_ = h_[0][2 * tv_][j], a1_ = h_[0][2 * tv_ + 1][j], a2_ = h_[0][2 * tv_ + 2][j], a3_ = h_[0][2 * tv_ + 3][j]; \
-                const float b0_ = h_[1][2 * tv_][j], b1_ = h_[1][2 * tv_ + 1][j], b2_ = h_[1][2 * tv_ + 2][j], b3_ = h_[1][2 * tv_ + 3][j]; \
-                *reinterpret_cast<float2*>(vd_ + (0 * 4 + j) * 1024) = make_float2(a0_ - a2_, b0_ - b2_); \
-                *reinterpret_cast<float2*>(vd_ + (1 * 4 + j) * 1024) = make_float2(a1_ + a2_, b1_ + b2_); \
-                *reinterpret_cast<float2*>(vd_ + (2 * 4 + j) * 1024) = make_float2(a2_ - a1_, b2_ - b1_); \
-                *reinterpret_cast<float2*>(vd_ + (3 * 4 + j) * 1024) = make_float2(a1_ - a3_, b1_ - b3_); \
-            }                                                                                     \
-        }                                                                                         \
-    }
-#endif
 #define DMH_W32_TRANSFORM(BUFI) DMH_W32_TRANSFORM_PAIR(rsrc0 + (BUFI) * RAW_BUF, vdst0)
 
     f32x16 acc[16];         // never cleared: the first chunk of a piece multiplies onto a zero C operand (an inline constant), as in K10

@@ -147,15 +147,12 @@ __global__ __launch_bounds__(NT) void wino_weight_batch_kernel(const WtBatch b) 
                         ((int)blockIdx.x - b.first[j]) * NT + (int)threadIdx.x);
 }
 
-// DMH_WINO_PK (round 6): the input transform B^T d B on PACKED fp32 adds.  A thread transforms the patches of TWO channels of
+// Round 6: the input transform B^T d B on PACKED fp32 adds.  A thread transforms the patches of TWO channels of
 // one tile; the raw region keeps the rows of such a channel pair INTERLEAVED ([pair][row][channel of the pair][word]), so that the
 // same patch element of both channels is one ds_read2_b32 (offsets j, j + row pitch) into a register pair, both passes of the
 // transform are v_pk_add_f32 on such pairs (32 instructions instead of 64 -- the fp32 MFMA shadows no vector instruction, so
 // they come straight off the chunk time), and the results are the (channel, channel + 1) pairs the 8-byte image writes want.
-// Same additions in the same order: bit-identical results.
-#ifndef DMH_WINO_PK
-#define DMH_WINO_PK 1
-#endif
+// Same additions in the same order as the scalar transform of round 5 (since removed): bit-identical results.
 // 16-byte words of one channel's raw region (rows x words per row), and the channel pitch in words
 template <int TRW, bool FLAT>
 struct RawGeo {
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     constexpr int TRS = (FLAT ? 4 : 2) * RWA;               // raw floats from one tile row to the next
     constexpr int CHPW = RawGeo<TRW, FLAT>::CHPW;           // words of one channel's raw region
     constexpr int CHP = 4 * CHPW;                           // ... floats
-    constexpr int PKI = DMH_WINO_PK ? 2 : 1;                // DMH_WINO_PK: the rows of a channel pair are interleaved
+    constexpr int PKI = 2;                                  // the rows of a channel pair are interleaved
     constexpr int RAW_N = CK * CHPW;                        // words of one raw buffer
     static_assert(RH * NWR == RawGeo<TRW, FLAT>::CHW, "raw geometry");
     constexpr int RAW_PER_T = (RAW_N + NT - 1) / NT;
@@ -313,7 +310,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         }                                                                                         \
         _Pragma("unroll") for (int k = 0; k < RAW_PER_T; ++k) {                                   \
             const int e = tid_o + NT * k;                                                         \
-            /* LDS order: [channel][row][word]; DMH_WINO_PK: [channel pair][row][channel of the pair][word] */ \
+            /* LDS order: [channel pair][row][channel of the pair][word] */                                    \
             const int cq = e / (PKI * CHPW), r1 = e - cq * (PKI * CHPW), rr = r1 / (PKI * NWR), r2 = r1 - rr * (PKI * NWR); \
             const int c = PKI * cq + r2 / NWR, xx = 4 * (r2 % NWR);                               \
             int iy, bofs = cbase;                                                                 \
@@ -402,7 +399,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             float d[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {       // 4-byte aligned only (coff is odd for pad 1): dword reads, paired by the compiler
-                const float* row = DMH_WINO_PK ? rsrc + (2 * i + ch) * RWA : rsrc + ch * CHP + i * RWA;
+                const float* row = rsrc + (2 * i + ch) * RWA;
                 d[i][0] = row[0]; d[i][1] = row[1]; d[i][2] = row[2]; d[i][3] = row[3];
             }
 #pragma unroll
@@ -463,11 +460,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             f32x4 ua[16], vb[16];
             ua[0] = Uc[0]; vb[0] = Vc[0];
             ua[1] = Uc[128]; vb[1] = Vc[128];
-#if DMH_WINO_PK
             f32x2 D[4][4], T[4][4];         // (channel, channel + 1) pairs: patch elements, then B^T d
-#else
-            float d[4][4], t[2][4][4];
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #if DMH_WINO_ABLATE & 16
 #define DMH_MFMA(A, B, C) (C)
@@ -493,7 +486,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 if (sl < 8) {                               // filter chunk g+1 -> U[nxt] by LDS-DMA, one row per slot
                     if (!(DMH_WINO_ABLATE & 1)) DMH_WINO_GLDS_U_ROW(ucb, nxt, sl)
                 } else if (DMH_WINO_ABLATE & 2) {
-#if DMH_WINO_PK
                 } else if (sl < 22) {
                     if (sl < 12) {              // column sl - 8 of BOTH channels' patches: one read per row = (channel, channel + 1)
                         const int j = sl - 8;
@@ -520,30 +512,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                             *reinterpret_cast<f32x2*>(vd + (rr * 4 + 3) * 512) = pk_sub(T[rr][1], T[rr][3]);
                         }
                     }
-#else
-                } else if ((sl >= 8 && sl < 12) || (sl >= 14 && sl < 18)) {   // raw patch row of channel 0 / 1
-                    const int c2 = sl >= 14, i = c2 ? sl - 14 : sl - 8;
-                    const float* row = rs + c2 * CHP + i * RWA;
-                    d[i][0] = row[0]; d[i][1] = row[1]; d[i][2] = row[2]; d[i][3] = row[3];
-                } else if (sl == 12 || sl == 13 || sl == 18 || sl == 19) {    // rows of B^T d, two columns per slot
-                    const int c2 = sl >= 18, j0 = 2 * (sl & 1);
-#pragma unroll
-                    for (int j = j0; j < j0 + 2; ++j) {
-                        t[c2][0][j] = d[0][j] - d[2][j];
-                        t[c2][1][j] = d[1][j] + d[2][j];
-                        t[c2][2][j] = d[2][j] - d[1][j];
-                        t[c2][3][j] = d[1][j] - d[3][j];
-                    }
-                } else if (sl >= 20 && sl < 28) {           // columns: half an output row (2 positions) per slot -> V
-                    const int rr = (sl - 20) >> 1;
-                    if ((sl & 1) == 0) {
-                        *reinterpret_cast<float2*>(vd + (rr * 4 + 0) * 512) = make_float2(t[0][rr][0] - t[0][rr][2], t[1][rr][0] - t[1][rr][2]);
-                        *reinterpret_cast<float2*>(vd + (rr * 4 + 1) * 512) = make_float2(t[0][rr][1] + t[0][rr][2], t[1][rr][1] + t[1][rr][2]);
-                    } else {
-                        *reinterpret_cast<float2*>(vd + (rr * 4 + 2) * 512) = make_float2(t[0][rr][2] - t[0][rr][1], t[1][rr][2] - t[1][rr][1]);
-                        *reinterpret_cast<float2*>(vd + (rr * 4 + 3) * 512) = make_float2(t[0][rr][1] - t[0][rr][3], t[1][rr][1] - t[1][rr][3]);
-                    }
-#endif
                 }
                 if (FLAT && sl == 28) {     // single raw buffer: every wave has read this chunk's patches (slots 8-17)
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -822,9 +790,8 @@ bool sk_decide(long long regions, int nch, bool epi, bool have_ws, int64_t ws_fl
     if (!(G >= 2 && units < ((long long)1 << 30) && (long long)2 * G * SK_SLOT <= ws_floats)) return false;
     const int cs = (!epi && regions < (3 * cus) / 4 && nch % 2 == 0 && nch >= 6) ? 2 : 1;   // what the legacy path would do
     const long long items = regions * cs;
-    // microseconds per chunk, per item epilogue, for the second launch; the margin (DMH_SK_MODEL="chunk,epilogue,launch,margin": A/B)
-    static const struct Model { double c = 3.05, e = 4.0, l = 6.0, m = 0.92; Model() {
-        if (const char* v = getenv("DMH_SK_MODEL")) sscanf(v, "%lf,%lf,%lf,%lf", &c, &e, &l, &m); } } M;
+    // microseconds per chunk, per item epilogue, for the second launch; the margin (swept in round 6: insensitive)
+    constexpr struct { double c, e, l, m; } M = {3.05, 4.0, 6.0, 0.92};
     const double t_cur = (double)((items + cus - 1) / cus) * ((nch / cs) * M.c + M.e) + (cs > 1 ? M.l : 0.0);
     const double per = (double)units / G;
     const double t_sk = per * M.c + M.e * (per / nch + 1.5) + M.l;

@@ -15,14 +15,12 @@
 //                   channels.  Raw rows through registers into LDS (buffer loads: uniform row offsets in SGPRs, an
 //                   out-of-range offset = zero padding = masked ragged edge), both transforms LDS -> LDS into the images
 //                   dM[p][h][k][4], V[p][h][c][4] (h + 2s = tile: a 16-byte operand read feeds 4 k-steps, as in K10),
-//                   64 MFMAs per wave.  Images single-buffered, raw rows double-buffered: MFMA phase / transform phase with
-//                   two barriers per chunk (K17's scheme; the fp32 MFMA shares the vector pipe, so nothing is lost by
-//                   taking the transforms out from between the MFMAs).
+//                   64 MFMAs per wave.  Images single-buffered, raw rows double-buffered; the chunk loop interleaves the
+//                   MFMAs of one half of a chunk with the transforms of the other ("interleaved form" below), two barriers
+//                   per chunk.
 //   * split       : the 256 workgroups are dealt over the (k-block, c-block) pairs, each pair's chunks split into equal
 //                   contiguous slices; every workgroup stores its partial dU, and wino_wrw_reduce_kernel adds the slices in
 //                   a fixed order and applies G^T . G  -> dw[K][C][3][3].  No atomics: bitwise reproducible.
-#include <stdlib.h>
-
 #include "common.hpp"
 
 using namespace dmh;
@@ -68,9 +66,7 @@ struct RArgs {
     int nchunks, nk, nc, S, cps;   // chunks in total; channel blocks; slices per pair; chunks per slice
 };
 
-// IL (round 6): the interleaved form of the chunk loop -- see "interleaved form" below.  Same sums in the same order: the two
-// forms give bit-identical results (tests/test_gpu_conv_anchor.py).
-template <int KS, int CS, bool IL>
+template <int KS, int CS>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void wino_wrw_kernel(RArgs a) {
     using G = Cfg<KS, CS>;
     constexpr int KCH = G::KCH, CCH = G::CCH, NXL = G::NXL, NDL = G::NDL, XRAW = G::XRAW, RAWBUF = G::RAWBUF;
@@ -171,80 +167,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #pragma unroll
         for (int k = 0; k < NDL; ++k) store_d(buf, k, wrem_held);
     };
-    // transforms of one chunk: work item = (channel, tile pair tp): tiles h + 4j, h + 4j + 2 with h = tp & 1, j = tp >> 1; the
-    // two tiles are components 2j, 2j + 1 of the channel's 16-byte image word -> one 8-byte write per position.  Items are
-    // dealt channel-fastest over the threads (64 channels: lane = channel, wave = tile pair).
-    auto xform_d = [&](const int buf, const int ch, const int tp) __attribute__((always_inline)) {
-        // dM = A dY A^T, A = [[1,0],[1,1],[1,-1],[0,-1]]
-        const int th = tp & 1, tj = tp >> 1;
-        const float* ds = raw + buf * RAWBUF + XRAW + ch * DCS + 2 * (th + 4 * tj);
-        float* const md = reinterpret_cast<float*>(M_lds + th * KCH + ch) + 2 * tj;
-        float m[2][4][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const float2 r0 = *reinterpret_cast<const float2*>(ds + 4 * t), r1 = *reinterpret_cast<const float2*>(ds + DC + 4 * t);
-            const float u[4][2] = {{r0.x, r0.y}, {r0.x + r1.x, r0.y + r1.y}, {r0.x - r1.x, r0.y - r1.y}, {-r1.x, -r1.y}};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                m[t][i][0] = u[i][0];
-                m[t][i][1] = u[i][0] + u[i][1];
-                m[t][i][2] = u[i][0] - u[i][1];
-                m[t][i][3] = -u[i][1];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *reinterpret_cast<float2*>(md + (i * 4 + j) * (8 * KCH)) = make_float2(m[0][i][j], m[1][i][j]);
-    };
-    auto xform_x = [&](const int buf, const int ch, const int tp) __attribute__((always_inline)) {
-        // V = B^T d B
-        const int th = tp & 1, tj = tp >> 1;
-        const float* xs = raw + buf * RAWBUF + ch * XCS + coff + 2 * (th + 4 * tj);  // tile A; tile B: + 4 columns
-        float* const vd = reinterpret_cast<float*>(V_lds + th * CCH + ch) + 2 * tj;
-        float v[2][4][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            float d[4][4], q[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float* row = xs + i * XC + 4 * t;      // 4-byte aligned only (coff is odd for pad 1): four dword reads,
-                d[i][0] = row[0]; d[i][1] = row[1]; d[i][2] = row[2]; d[i][3] = row[3];   // paired by the compiler (ds_read2_b32)
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                q[0][j] = d[0][j] - d[2][j];
-                q[1][j] = d[1][j] + d[2][j];
-                q[2][j] = d[2][j] - d[1][j];
-                q[3][j] = d[1][j] - d[3][j];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v[t][i][0] = q[i][0] - q[i][2];
-                v[t][i][1] = q[i][1] + q[i][2];
-                v[t][i][2] = q[i][2] - q[i][1];
-                v[t][i][3] = q[i][1] - q[i][3];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *reinterpret_cast<float2*>(vd + (i * 4 + j) * (8 * CCH)) = make_float2(v[0][i][j], v[1][i][j]);
-    };
-    auto transform = [&](const int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < (KCH * 4 + NT - 1) / NT; ++r) {
-            const int it = tid + NT * r;
-            if ((KCH * 4) % NT == 0 || it < KCH * 4) xform_d(buf, it % KCH, it / KCH);
-        }
-#pragma unroll
-        for (int r = 0; r < (CCH * 4 + NT - 1) / NT; ++r) {
-            const int it = tid + NT * r;
-            if ((CCH * 4) % NT == 0 || it < CCH * 4) xform_x(buf, it % CCH, it / CCH);
-        }
-    };
 
     // MFMA phase: wave w owns positions 4w .. 4w+3 of every sub-block: per position KS + CS operand words (16 bytes = the 4
     // k-steps of a chunk) feed 4 KS CS MFMAs, and consecutive MFMAs run on different accumulators.
@@ -253,11 +175,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     for (int p = 0; p < G::NACC; ++p)
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[p][v] = 0.f;
-    const f32x4* const Mw = M_lds + (4 * wv_s) * (2 * KCH) + (lane >> 5) * KCH + (lane & 31);
-    const f32x4* const Vw = V_lds + (4 * wv_s) * (2 * CCH) + (lane >> 5) * CCH + (lane & 31);
+    const float2* const Mw2 = reinterpret_cast<const float2*>(M_lds) + (4 * wv_s) * (4 * KCH) + (lane >> 5) * (2 * KCH) + (lane & 31);
+    const float2* const Vw2 = reinterpret_cast<const float2*>(V_lds) + (4 * wv_s) * (4 * CCH) + (lane >> 5) * (2 * CCH) + (lane & 31);
 
-    if (IL && n > 0) {
-        // ---- interleaved form.  The two-phase loop below it leaves the matrix pipe idle while the transforms run (LDS read ->
+    if (n > 0) {
+        // ---- interleaved form (round 6).  The two-phase loop of rounds 3-5 (MFMAs of a chunk, barrier, transforms of the next,
+        // barrier; since removed, it gave the same bits) left the matrix pipe idle while the transforms ran (LDS read ->
         // arithmetic -> LDS write, a chain of latencies that one wave per SIMD cannot cover: 107 of 388 us at layer1's shape,
         // tools/wrw_ablate.py) because the images are single-buffered and there is no LDS for a second pair (2 x 64 KB).  But an
         // image word holds FOUR tiles (its components = the 4 k-steps of a chunk), and a k-step only reads its own component:
@@ -364,8 +287,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                 for (int pp = 8 * part; pp < 8 * part + 8; ++pp) vd[pp * (8 * CCH)] = xt[k][pp];
             }
         };
-        const float2* const Mw2 = reinterpret_cast<const float2*>(M_lds) + (4 * wv_s) * (4 * KCH) + (lane >> 5) * (2 * KCH) + (lane & 31);
-        const float2* const Vw2 = reinterpret_cast<const float2*>(V_lds) + (4 * wv_s) * (4 * CCH) + (lane >> 5) * (2 * CCH) + (lane & 31);
         constexpr int NST = NXL + NDL;
         // one phase: the 8 (position, k-step) MFMA groups of half J on the images, with the transform of (tbuf, tJ) and --
         // STAGE -- the raw stores / refill loads dealt over its slots
@@ -470,79 +391,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             phase(1, 1, 0, true, 0, g);
         }
     }
-    if (!IL && n > 0) {
-        // prologue: chunk 0 -> raw[0] -> images; chunk 1 -> raw[1]; chunk 2 in registers
-        load_chunk(c_first);
-        store_raw(0);
-        load_chunk(c_first + 1);
-        __syncthreads();
-        transform(0);
-        store_raw(1);
-        load_chunk(c_first + 2);
-        __syncthreads();
-        for (int g = 0; g < n; ++g) {
-            const int cur = g & 1, nxt = cur ^ 1;
-            f32x4 ua[2][KS], vb[2][CS];
-#pragma unroll
-            for (int i = 0; i < KS; ++i) ua[0][i] = Mw[i * 32];
-#pragma unroll
-            for (int i = 0; i < CS; ++i) vb[0][i] = Vw[i * 32];
-            // staging work of this iteration, dealt over the 16 MFMA groups below: groups 0-7 the raw registers (chunk g+2)
-            // -> raw[cur] (read by transform(g) one iteration ago), groups 8-15 the refill of those registers with chunk g+3
-            constexpr int NST = NXL + NDL;
-            const int wrem_st = wrem_held;
-            Chunk cn;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-                    for (int ci = 0; ci < CS; ++ci)
-#pragma unroll
-                        for (int ki = 0; ki < KS; ++ki) {
-                            f32x16& c = acc[(q * CS + ci) * KS + ki];
-                            if (!(DMH_WRW_ABLATE & 8)) c = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[q & 1][ki][ks], vb[q & 1][ci][ks], c, 0, 0, 0);
-                            else c[ks] += ua[q & 1][ki][ks] * vb[q & 1][ci][ks];
-                        }
-                    if (q + 1 < 4) {                          // operands of the next position, spread over the four k-steps
-#pragma unroll
-                        for (int r = ks; r < KS + CS; r += 4) {
-                            if (r < KS) ua[(q + 1) & 1][r] = Mw[(q + 1) * (2 * KCH) + r * 32];
-                            else vb[(q + 1) & 1][r - KS] = Vw[(q + 1) * (2 * CCH) + (r - KS) * 32];
-                        }
-                    }
-                    const int sl = q * 4 + ks;
-                    if (sl < 8) {
-                        if (!(DMH_WRW_ABLATE & 4)) {
-#pragma unroll
-                            for (int k = sl * NST / 8; k < (sl + 1) * NST / 8; ++k) {
-                                if (k < NXL) store_x(cur, k);
-                                else store_d(cur, k - NXL, wrem_st);
-                            }
-                        }
-                    } else {
-                        if (sl == 8) cn = chunk_at(c_first + g + 3);
-#pragma unroll
-                        for (int k = (sl - 8) * NST / 8; k < (sl - 7) * NST / 8; ++k) {
-                            if (k < NXL) load_x(cn, k);
-                            else load_d(cn, k - NXL);
-                        }
-                        if (sl == 15) wrem_held = cn.wrem;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            // raw s_barrier + lgkmcnt only: __syncthreads() would also wait for the loads just issued (vmcnt(0))
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (!(DMH_WRW_ABLATE & 16)) __builtin_amdgcn_s_barrier();   // every wave has read the images of chunk g
-            asm volatile("" ::: "memory");
-            if (!(DMH_WRW_ABLATE & 2)) transform(nxt);      // chunk g+1 (written to raw[nxt] one iteration ago)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (!(DMH_WRW_ABLATE & 16)) __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-    }
     // ---- partial dU of this slice: ws[pair][slice][p][k KCH][c CCH]; D row (k) = 8 (v >> 2) + 4 (lane >> 5) + (v & 3), col (c) = lane & 31
     float* wsb = a.ws + (((size_t)pair * a.S + slice) * 16 + 4 * wv) * (KCH * CCH) + (size_t)(4 * (lane >> 5)) * CCH + (lane & 31);
 #pragma unroll
@@ -623,21 +471,14 @@ void plan(RArgs& a, int kch, int cch) {
     a.cps = (a.nchunks + S - 1) / S;
 }
 
-template <int KS, int CS, bool IL>
-int launch_form(const RArgs& a, hipStream_t st) {
-    constexpr size_t smem = Cfg<KS, CS>::SMEM;
-    static std::atomic<uint64_t> configured{0};     // per device, see configure_dynamic_lds
-    if (configure_dynamic_lds(wino_wrw_kernel<KS, CS, IL>, smem, configured) != hipSuccess)
-        return fail(DMH_ELAUNCH, "%s: cannot raise the dynamic LDS limit", "dmh_wino_wrw");
-    hipLaunchKernelGGL((wino_wrw_kernel<KS, CS, IL>), dim3((unsigned)(a.nk * a.nc * a.S)), dim3(NT), smem, st, a);
-    return check_launch("dmh_wino_wrw");
-}
-
 template <int KS, int CS>
 int launch(const RArgs& a, hipStream_t st) {
-    // DMH_WRW_FORM=0: the two-phase loop of rounds 3-5 (A/B switch; bit-identical results)
-    static const bool il = !(getenv("DMH_WRW_FORM") && atoi(getenv("DMH_WRW_FORM")) == 0);
-    return il ? launch_form<KS, CS, true>(a, st) : launch_form<KS, CS, false>(a, st);
+    constexpr size_t smem = Cfg<KS, CS>::SMEM;
+    static std::atomic<uint64_t> configured{0};     // per device, see configure_dynamic_lds
+    if (configure_dynamic_lds(wino_wrw_kernel<KS, CS>, smem, configured) != hipSuccess)
+        return fail(DMH_ELAUNCH, "%s: cannot raise the dynamic LDS limit", "dmh_wino_wrw");
+    hipLaunchKernelGGL((wino_wrw_kernel<KS, CS>), dim3((unsigned)(a.nk * a.nc * a.S)), dim3(NT), smem, st, a);
+    return check_launch("dmh_wino_wrw");
 }
 
 }  // namespace

@@ -10,8 +10,6 @@ the convolutions (BatchNorm with running statistics, identity add, ReLU, the ste
 kernels of libdmh_hip (``ops.bn_act``, ``ops.stem_bn_relu_pool``); train() mode and CPU tensors take the module
 path below, which is the reference's.  ``ResNet.fuse_eval_bn = False`` switches the fused path off.
 """
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -234,8 +232,7 @@ class ResnetEncoder(nn.Module):
         block, layers = _CONFIGS[num_layers]
         self.encoder = ResNet(block, layers, num_input_images)
         self.roi_backward = True    # forward(x, roi=...) may run the head's backward on the attack's windows (ops.encoder_head_eval)
-        self.roi_incremental = os.environ.get("DMH_ROI_INCREMENTAL", "1") != "0"     # ... and, given the clean frames, its forward
-        self.roi_incremental_layer2 = os.environ.get("DMH_ROI_LAYER2", "1") != "0"   # ... and layer2's forward and backward
+        # ... and, given the clean frames, its forward, and layer2's forward and backward
         if num_layers > 34:
             self.num_ch_enc[1:] *= 4
 
@@ -338,10 +335,10 @@ class ResnetEncoder(nn.Module):
             c = e.conv1
             if (blocks is not None and c.stride == (2, 2) and c.padding == (3, 3) and c.dilation == (1, 1) and c.groups == 1
                     and c.bias is None and ops.encoder_head_ok(input_image, c.weight, [(b[0], b[2]) for b in blocks])):
-                if (clean is not None and self.roi_incremental and ops.weights_frozen() and roi[0].head_incremental_ok
+                if (clean is not None and ops.weights_frozen() and roi[0].head_incremental_ok
                         and clean.shape == input_image.shape and clean.is_cuda and clean.dtype == torch.float32):
                     # forward AND backward of the head on one window per scene, on top of the clean frames' feature 1
-                    l2 = self._layer2_blocks(aff) if self.roi_incremental_layer2 else None
+                    l2 = self._layer2_blocks(aff)
                     if l2 is not None and not (roi[0].layer2_incremental_ok and ops.layer2_incremental_ok(input_image, l2)):
                         l2 = None
                     cache = ops.frozen_memo(("clean_head", id(self), clean.data_ptr(), clean._version, l2 is not None),

@@ -1201,9 +1201,6 @@ def channel_sum(g):
     return out
 
 
-BN_BWD_ENABLED = os.environ.get("DMH_BN_BWD", "1") != "0"      # A/B switch: 0 = K9 mask pass + MIOpen's backward
-
-
 def _bn_backward_fused(g, x, out, weight, mean, invstd, want_pre):
     """K9 train-mode BatchNorm backward (dmh_bn_train_bwd): ReLU mask (``out`` = the saved ReLU output, or None) + the
     three gradients in three launches.  Returns (g_x, g_weight, g_bias, g_pre or None)."""
@@ -1247,7 +1244,7 @@ class _BnActTrain(torch.autograd.Function):
         lib = N.lib()
         g = _c(g)
         B, Cc = g.shape[0], g.shape[1]
-        if BN_BWD_ENABLED and weight is not None and g.numel() < (1 << 31) and Cc <= 65535:
+        if weight is not None and g.numel() < (1 << 31) and Cc <= 65535:
             gx, gw, gb, g_pre = _bn_backward_fused(g, x, out if ctx.relu else None, weight, mean, invstd,
                                                    ctx.res_grad and ctx.relu)
             if ctx.res_grad and not ctx.relu:
@@ -1340,7 +1337,7 @@ class _StemTrain(torch.autograd.Function):
         N.check(_timed("stem_bwd", lambda: lib.dmh_stem_bn_relu_pool_bwd(N.ptr(feat), N.ptr(arg), N.ptr(g_feat),
                                                                         N.ptr(g_pooled), N.ptr(ones), B, Cc, H, W,
                                                                         N.ptr(g_pre), N.stream()), 12 * feat.numel()))
-        if BN_BWD_ENABLED and weight is not None and g_pre.numel() < (1 << 31) and Cc <= 65535:
+        if weight is not None and g_pre.numel() < (1 << 31) and Cc <= 65535:
             gx, gw, gb, _ = _bn_backward_fused(g_pre, x, None, weight, mean, invstd, False)
             return gx, gw, gb, None
         gx, gw, gb = _bn_backward(g_pre, x, weight, ctx.bn, mean, invstd, ctx.eps,
@@ -1369,7 +1366,6 @@ def stem_bn_relu_pool(x, scale, shift):
 # channels (tools/wino_bench.py, profiles/); everything else is the ATen/MIOpen convolution.
 # ---------------------------------------------------------------------------------------------------------------
 WINO_ENABLED = os.environ.get("DMH_WINO", "1") != "0"
-WRW_ENABLED = os.environ.get("DMH_WRW", "1") != "0"     # K18 / K20 / K21 (weight gradients); 0: MIOpen (A/B switch)
 _wino_frozen = 0
 _wino_cache = {}
 
@@ -1499,12 +1495,12 @@ def wino_prefetch(jobs, fresh=False):
 
 
 WINO_SK = os.environ.get("DMH_WINO_SK", "1") != "0"       # A/B switch: stream-K decomposition of the plain K10 launches
-# work items below which MIOpen is level or ahead (A/B switch).  200 until round 5: measured with whole items only.  With the
+# work items below which MIOpen is level or ahead.  200 until round 5: measured with whole items only.  With the
 # stream-K forms a launch of 64 items (or 512 (item, chunk) units) already beats the library's fixed costs: the strong-scaling
 # share (train batch 4, 2 attack scenes) 50.2 -> 38.5 ms per step at 75 / 50 / 35 alike, batch 4 + 12 scenes and the headline
-# batch unchanged (tools/ab_min_items.sh)
-_WINO_MIN_ITEMS = int(os.environ.get("DMH_WINO_MIN_ITEMS", "64"))
-_WINO_MIN_FILL = float(os.environ.get("DMH_WINO_MIN_FILL", "0.5"))      # real tiles / tiles of the regions below which MIOpen is ahead (A/B switch)
+# batch unchanged (round 6, with a switch since removed)
+_WINO_MIN_ITEMS = 64
+_WINO_MIN_FILL = 0.5        # real tiles / tiles of the regions below which MIOpen is ahead
 
 
 def _wino_ok(B, n_in, n_out, Ho, Wo, allow_split=True, allow_sk=False):
@@ -1547,7 +1543,7 @@ def _wrw_ok(x, g, K, Cc):
     """Shapes of K18 (Winograd-domain weight gradient): both channel counts multiples of 64 (64 x 64 blocks), or 32 k output
     channels with 96 k' / 64 k' input channels (32 x 96 / 32 x 64 blocks: upconv(1,1), upconv(1,0)); even output size, enough
     tile chunks (8 tiles) to give every workgroup of a (k-block, c-block) pair a few, tensors below 4 GB."""
-    if not WINO_ENABLED or not WRW_ENABLED or g.shape[2] % 2 or g.shape[3] % 2:
+    if not WINO_ENABLED or g.shape[2] % 2 or g.shape[3] % 2:
         return False
     if K % 64 == 0 and Cc % 64 == 0:
         kch, cch = 64, 64
@@ -1852,7 +1848,7 @@ def _stem_wrw(x, g, weight, mean, std):
     """K21: dW of the 7x7/2 first convolution on (x - mean) / std, fixed-order sums on the fp32 MFMA; None when the shape is
     not the kernel's (3 -> 64 channels, even H, W a multiple of 8): the caller then takes ATen's."""
     B, Cin, H, W = x.shape
-    if not WINO_ENABLED or not WRW_ENABLED or tuple(weight.shape) != (64, 3, 7, 7) or Cin != 3 or x.numel() * 4 > 0xFFFFFF00:
+    if not WINO_ENABLED or tuple(weight.shape) != (64, 3, 7, 7) or Cin != 3 or x.numel() * 4 > 0xFFFFFF00:
         return None
     lib = N.lib()
     n = lib.dmh_stem_wrw_workspace_size(B, H, W)
@@ -1982,7 +1978,6 @@ def stem_conv_norm(x, weight, mean=0.45, std=0.225):
     return _StemConvNorm.apply(_c(x), weight, float(mean), float(std))
 
 
-DOWN_WIDE = os.environ.get("DMH_DOWN_WIDE", "1") != "0"     # A/B switch: K15 with 16-byte loaders and the filter image (round 5)
 
 
 def _down_image(w3, wd):
@@ -2002,7 +1997,7 @@ def _down_image(w3, wd):
 
 def _k15_fwd(lib, x, w3, wd, shift3, shiftd, relu3, B, Cin, Cout, H, W, y3, yd, stream):
     """dmh_down_conv_fwd_act, in its image form (16-byte loaders; bit-identical) where the rows are whole 16-byte words."""
-    if DOWN_WIDE and W % 4 == 0 and Cout % 32 == 0:
+    if W % 4 == 0 and Cout % 32 == 0:
         return lib.dmh_down_conv_fwd_img(N.ptr(x), N.ptr(_down_image(w3, wd)), int(wd is not None), N.ptr(shift3), N.ptr(shiftd),
                                          int(relu3), B, Cin, Cout, H, W, N.ptr(y3), N.ptr(yd), stream)
     return lib.dmh_down_conv_fwd_act(N.ptr(x), N.ptr(w3), N.ptr(wd), N.ptr(shift3), N.ptr(shiftd), int(relu3), B, Cin, Cout, H, W,
@@ -2011,7 +2006,7 @@ def _k15_fwd(lib, x, w3, wd, shift3, shiftd, relu3, B, Cin, Cout, H, W, y3, yd, 
 
 def _k15_bwd(lib, g3, gd, w3t, wdt, g_add, B, Cin, Cout, H, W, g_x, stream):
     """dmh_down_conv_bwd_data_acc (filters transposed: w3t [Cin, Cout, 3, 3], wdt [Cin, Cout]), image form where W % 8 == 0."""
-    if DOWN_WIDE and W % 8 == 0 and Cin % 32 == 0:
+    if W % 8 == 0 and Cin % 32 == 0:
         return lib.dmh_down_conv_bwd_data_img(N.ptr(g3), N.ptr(gd), N.ptr(_down_image(w3t, wdt)), N.ptr(g_add), B, Cin, Cout, H, W,
                                               N.ptr(g_x), stream)
     return lib.dmh_down_conv_bwd_data_acc(N.ptr(g3), N.ptr(gd), N.ptr(w3t), N.ptr(wdt), N.ptr(g_add), B, Cin, Cout, H, W, N.ptr(g_x),
@@ -2054,7 +2049,7 @@ class _DownConvs(torch.autograd.Function):
             N.check(_timed("down_conv_bwd", lambda: _k15_bwd(lib, g3, gd, w3t, wdt, None, B, Cin, Cout, H, W, g_x, N.stream()),
                            nb, 20 * Cin * g3.numel()))
         if not ctx.params_const and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
-            n = lib.dmh_down_wrw_workspace_size(B, Cin, Cout, H, W) if (WRW_ENABLED and x.numel() * 4 <= 0xFFFFFF00) else -1
+            n = lib.dmh_down_wrw_workspace_size(B, Cin, Cout, H, W) if x.numel() * 4 <= 0xFFFFFF00 else -1
             if n >= 0 and ctx.needs_input_grad[1]:
                 ws = torch.empty(n, device=x.device, dtype=torch.float32)
                 g_w3 = torch.empty_like(w3, memory_format=torch.contiguous_format)
@@ -2214,12 +2209,11 @@ class _DownBlockEval(torch.autograd.Function):
         return (_down_block_bwd(g1, g2, g_skip, ctx.in_shape, w3, s1, wd, sd),) + (None,) * 10
 
 
-DOWN_NODE_ENABLED = os.environ.get("DMH_DOWN_NODE", "1") != "0"     # timing comparisons
 
 
 def down_block_eval_ok(x, w3, wd, w2):
     """Inside frozen_weights(), K15 shapes, and the block's second convolution on the K10 epilogue kernel."""
-    if not (_wino_frozen > 0 and DOWN_NODE_ENABLED and down_convs_ok(x, w3, wd)):
+    if not (_wino_frozen > 0 and down_convs_ok(x, w3, wd)):
         return False
     Co = w3.shape[0]
     return tuple(w2.shape) == (Co, Co, 3, 3) and _wino_ok(x.shape[0], Co, Co, x.shape[2] // 2, x.shape[3] // 2, allow_split=False,
@@ -2324,7 +2318,7 @@ def _roi_glue_bwd(a, g_out, device, want_skip, y_region=None, skip_region=None, 
 
 from .roi import STAGES as _ROI_STAGES, TABLE as _ROI_NAMES     # noqa: E402  (row order of the device table of origins)
 
-ROI_DEPTH = int(os.environ.get("DMH_ROI_DEPTH", "4"))      # level of the deepest windowed decoder stage (2, 3 or 4)
+ROI_DEPTH = 4       # level of the deepest windowed decoder stage (2, 3 or 4)
 # channel plan of the reference decoder's stages (MD2/networks/depth_decoder.py:22-37), by window name: (out, in)
 _ROI_CHANNELS = {"d": (1, 16), "z01": (16, 16), "y00": (16, 32), "z11": (32, 96), "y10": (32, 64), "z21": (64, 128),
                  "y20": (64, 128), "z31": (128, 256), "y30": (128, 256), "z41": (256, 512)}
@@ -2740,7 +2734,7 @@ def layer2_incremental_ok(x, layer2):
     B, _, H, W = x.shape
     probe = x.new_empty((B, 64, H // 4, W // 4))
     return (tuple(w3.shape) == (128, 64, 3, 3) and tuple(wd.shape) == (128, 64, 1, 1) and down_convs_ok(probe, w3, wd)
-            and all(tuple(w.shape) == (128, 128, 3, 3) for w in (w2, v1, v2)) and DOWN_NODE_ENABLED
+            and all(tuple(w.shape) == (128, 128, 3, 3) for w in (w2, v1, v2))
             and _wino_ok(B, 128, 128, H // 8, W // 8, allow_split=False))
 
 

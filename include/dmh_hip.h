@@ -565,11 +565,8 @@ int dmh_bn_act_bwd(const float* out, const float* g_out, const float* scale, int
  * and running_mean / running_var are updated in place with `momentum` (unbiased variance), as nn.BatchNorm2d does.
  * weight / bias / running_* may be NULL.  partials: dmh_bn_stats_partials_size(B, C, HW) floats of scratch. */
 int64_t dmh_bn_stats_partials_size(int B, int C, int HW);
-int dmh_bn_train_stats(const float* x, int B, int C, int HW, const float* weight, const float* bias, float momentum,
-                       float eps, float* running_mean, float* running_var, float* partials, float* scale, float* shift,
-                       float* save_mean, float* save_invstd, void* stream);
-/* The same, and num_batches_tracked[0] += 1 (the module's int64 counter, nn.BatchNorm2d.forward in train mode; may be NULL) in
- * the second launch instead of one more element-wise launch per BatchNorm (20 per train pass of the ResNet-18 encoder). */
+/* Also num_batches_tracked[0] += 1 (the module's int64 counter, nn.BatchNorm2d.forward in train mode; may be NULL) in the
+ * second launch instead of one more element-wise launch per BatchNorm (20 per train pass of the ResNet-18 encoder). */
 int dmh_bn_train_stats_tracked(const float* x, int B, int C, int HW, const float* weight, const float* bias, float momentum,
                                float eps, float* running_mean, float* running_var, long long* num_batches_tracked,
                                float* partials, float* scale, float* shift, float* save_mean, float* save_invstd,
@@ -768,15 +765,11 @@ int dmh_stem_conv_norm_fwd_win(const float* x, const float* w, const int* org, i
  *           wdt[Ci][Co]                                                      (gd, wdt both NULL: 3x3 only)
  *     Exact-fp32 MFMA.  H, W even; fwd: Ci % 8 == 0, Co % 64 == 0; bwd: Co % 8 == 0, Ci % 64 == 0.
  * ---------------------------------------------------------------------------------- */
-int dmh_down_conv_fwd(const float* x, const float* w3, const float* wd, int B, int Cin, int Cout, int H, int W,
-                      float* y3, float* yd, void* stream);
-/* the same with eval-mode BatchNorms folded in (scales already in the filters): y3 = act(corr3x3_s2(x, w3) + shift3[k]),
- * act = ReLU when relu3 != 0; yd = corr1x1_s2(x, wd) + shiftd[k]; shift3 / shiftd may be NULL. */
+/* fwd with eval-mode BatchNorms folded in (scales already in the filters): y3 = act(corr3x3_s2(x, w3) + shift3[k]),
+ * act = ReLU when relu3 != 0; yd = corr1x1_s2(x, wd) + shiftd[k]; shift3 / shiftd may be NULL (both, relu3 = 0: as above). */
 int dmh_down_conv_fwd_act(const float* x, const float* w3, const float* wd, const float* shift3, const float* shiftd,
                           int relu3, int B, int Cin, int Cout, int H, int W, float* y3, float* yd, void* stream);
-int dmh_down_conv_bwd_data(const float* g3, const float* gd, const float* w3t, const float* wdt, int B, int Cin, int Cout,
-                           int H, int W, float* g_x, void* stream);
-/* the same with g_add[B, Cin, H, W] (may be NULL) added in the epilogue: the gradient the same tensor receives from its other
+/* bwd with g_add[B, Cin, H, W] (may be NULL) added in the epilogue: the gradient the same tensor receives from its other
  * consumer (the decoder's skip connection), instead of autograd's separate accumulation pass. */
 int dmh_down_conv_bwd_data_acc(const float* g3, const float* gd, const float* w3t, const float* wdt, const float* g_add, int B,
                                int Cin, int Cout, int H, int W, float* g_x, void* stream);

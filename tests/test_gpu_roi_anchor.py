@@ -24,11 +24,6 @@ with S from the float64 reference and n_round READ FROM THE KERNEL, in units of 
   windowed stem        at most four pooled gradients meet in an element (the first onto 0.f: 3 rounded additions, counted as 4),
                        + g_feat: 1, * scale: 1: 6.  S = scale [feat > 0] (adjoint of |g_pool| + |g_feat|).
 """
-import os
-import subprocess
-import sys
-import time
-
 import numpy as np
 import pytest
 import torch
@@ -37,8 +32,6 @@ from tests import roi_ref as R
 from tests.util import assert_round_bound as _rb
 
 pytestmark = pytest.mark.gpu
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Largest error of the device's expf, in ulps.  ROCm's math-accuracy table is not among the documentation installed with the
 # toolchain, so the number is measured: expf against float64 exp on the device over EVERY fp32 argument of [-20, 0] (1.1e9 of
@@ -370,7 +363,7 @@ def test_glue_backward_rectangles_zero_fill_contract(prezero):
             _t64(R.cut(r["g_skip"], ko, kext)), _t64(R.cut(r["S_skip"], ko, kext)), 8)
 
 
-# ---- the two backward kernels, and the two-wide kernel's plane groups, bit for bit --------------------------------------------------------
+# ---- the two backward kernels, bit for bit ----------------------------------------------------------------------------------------------------
 
 TWIN_CASES = [c for c in R.GLUE_CASES if c[0] in ("G1", "G1e", "G3a", "G3b")]
 
@@ -393,41 +386,6 @@ def test_one_element_backward_is_bitwise_the_two_wide_backward(case):
         assert one_k is None or torch.equal(one_k, wide_k), "g_skip differs between the kernels"
         compared += 1
     assert compared or "two-wide" not in _case_cells(case)[1][2]
-
-
-CPT_CASES = [c for c in R.GLUE_CASES if c[0] in ("G1", "G1e", "G3a", "G3b") and (c[1], c[2]) == (8, 16)]
-
-
-def _backward_all(cases):
-    out = []
-    for case in cases:
-        d = _reference(case)
-        for group in R.glue_groups(case):
-            g_y, g_skip = _Launch(case, d, group).backward()
-            out += [g_y, g_skip]
-    return out
-
-
-def _child(path):
-    """Body of the child process of the next test: the (8, 16) cases' gradients under this process's DMH_ROI_GLUE_CPT."""
-    torch.save(_backward_all(CPT_CASES), path)
-
-
-@pytest.mark.parametrize("cpt", [4, 8])
-def test_two_wide_backward_plane_groups_are_bitwise_the_default(cpt, tmp_path):
-    """roi_glue_bwd2_kernel<4> / <8> (DMH_ROI_GLUE_CPT, read once per process: a fresh child per value) against <1> here."""
-    assert len(CPT_CASES) >= 4 and not os.environ.get("DMH_ROI_GLUE_CPT") and not os.environ.get("DMH_ROI_GLUE2")
-    path = str(tmp_path / "grads.pt")
-    t0 = time.time()
-    r = subprocess.run([sys.executable, "-c", "from tests.test_gpu_roi_anchor import _child; _child(%r)" % path], cwd=REPO,
-                       env=dict(os.environ, DMH_ROI_GLUE_CPT=str(cpt)), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                       timeout=120)
-    print("child with DMH_ROI_GLUE_CPT=%d: %.1f s" % (cpt, time.time() - t0))
-    assert r.returncode == 0, r.stdout[-3000:]
-    theirs, mine = torch.load(path), _backward_all(CPT_CASES)
-    assert len(theirs) == len(mine)
-    for a, b in zip(theirs, mine):
-        assert torch.equal(a, b)
 
 
 # ---- cost -----------------------------------------------------------------------------------------------------------------------------

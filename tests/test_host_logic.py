@@ -411,3 +411,22 @@ def test_object_attack_base_host_pieces():
     grouped = atk._draw(5)
     assert got == [(list(z), list(a)) for z, a in want[:2]]
     assert grouped == (list(want[2][0]) + list(want[3][0]), list(want[2][1]) + list(want[3][1]))
+
+
+def test_environment_switches_are_the_documented_ones():
+    """Every DMH_* environment variable the package reads -- os.environ / os.getenv in its Python, getenv( in csrc/ -- has a row
+    in INTEGRATION.md's table of environment variables, and the table names nothing else: a new switch needs a documented
+    purpose and a user (the A/B switches of rounds 1-6 were pruned once; this keeps them from growing back)."""
+    pkg = os.path.join(REPO, "depthmodelhardening_amd")
+    read = set()
+    for root, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                for line in open(os.path.join(root, f)):
+                    if "os.environ" in line or "os.getenv" in line:
+                        read |= set(re.findall(r"[\"'](DMH_[A-Z0-9_]+)[\"']", line))
+    for f in os.listdir(os.path.join(pkg, "csrc")):
+        read |= set(re.findall(r"getenv\(\s*\"(DMH_[A-Z0-9_]+)\"", open(os.path.join(pkg, "csrc", f)).read()))
+    documented = set(re.findall(r"^\s*\|\s*`(DMH_[A-Z0-9_]+)`", open(os.path.join(REPO, "INTEGRATION.md")).read(), re.M))
+    assert read and read == documented, ("read but not documented", sorted(read - documented),
+                                         "documented but not read", sorted(documented - read))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # development tool: one environment switch, two values, over the BASELINE configs on ONE box (alternating)
-#   bash tools/ab_configs.sh DMH_WINO_MIN_ITEMS 200 64 "3 4 5"
+#   bash tools/ab_configs.sh DMH_WINO_PREFETCH 0 1 "3 4 5"
 VAR=$1; A=$2; B=$3; CFGS=${4:-"2 3 4 5"}
 for c in $CFGS; do
   for v in $A $B $A $B; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of environment switches on ONE box (development tool): bench.py at the headline configuration once per setting,
 # alternating, so that box-to-box spread (~1 %) does not hide a 0.5 % effect.
-#   bash tools/ab_switches.sh "DMH_WINO_MIN_FILL=0.6 DMH_ZEROS_ONCE=0" "DMH_WINO_MIN_FILL=0.5 DMH_ZEROS_ONCE=1" [rounds=2]
+#   bash tools/ab_switches.sh "DMH_WINO_SK=0" "DMH_WINO_SK=1" [rounds=2]
 set -e
 A="$1"; B="$2"; R="${3:-2}"
 for r in $(seq 1 "$R"); do

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """K18 (Winograd-domain weight gradient) vs MIOpen at the train-pass shapes (batch 32):  python3 tools/wrw_k18_bench.py [B=32]
-[nomiopen].  Prints a checksum of the result's bits per shape: DMH_WRW_FORM=0 (the two-phase loop) and the default (the
-interleaved loop) must print the same ones."""
+[nomiopen].  Prints a checksum of the result's bits per shape: two builds of the kernel that claim the same sums in the same order
+(round 6: the two-phase chunk loop, since removed, against the interleaved one) must print the same ones."""
 import sys
 
 import torch
