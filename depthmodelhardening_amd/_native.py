@@ -78,6 +78,7 @@ _SIGNATURES = {
                                     _fp, _fp, _fp]),
     "dmh_eot_paste_fwd": (C.c_int, [C.POINTER(PasteArgs), _fp, _fp, _fp]),
     "dmh_eot_paste_bwd": (C.c_int, [C.POINTER(PasteArgs), _fp, _fp, _fp]),
+    "dmh_eot_paste_fwd_form": (C.c_int, [C.POINTER(PasteArgs), _fp, _fp]),
     "dmh_pgd_linf_step": (C.c_int, [_fp, _fp, _fp, C.c_float, C.c_float, _fp, C.c_int64, _fp]),
     "dmh_apgd_step": (C.c_int, [_fp] * 6 + [C.c_int, C.c_float, C.c_int64, _fp]),
     "dmh_apgd_commit": (C.c_int, [_fp] * 10 + [C.c_int] * 3 + [C.c_double, C.c_int64, _fp]),

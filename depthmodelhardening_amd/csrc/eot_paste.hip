@@ -496,14 +496,23 @@ int check_paste(const dmh_paste_args* a) {
 
 extern "C" {
 
-int dmh_eot_paste_fwd(const dmh_paste_args* a, float* adv, float* mask_out, void* stream) {
-    if (int rc = check_paste(a)) return rc;
-    DMH_REQUIRE(adv || mask_out, "no output requested");
+// The forward's launch form, on the host: 2 = tiled, 1 = four-wide, 0 = generic, -1 = rejected arguments.  The one copy of
+// the rule: dmh_eot_paste_fwd launches what this returns.
+int dmh_eot_paste_fwd_form(const dmh_paste_args* a, const float* adv, const float* mask_out) {
+    if (check_paste(a)) return -1;
+    if (!adv && !mask_out) return fail(-1, "%s: requirement failed: no output requested", "dmh_eot_paste_fwd");
     const bool vec4 = (a->OW % 4) == 0 && ((uintptr_t)adv % 16) == 0 && ((uintptr_t)mask_out % 16) == 0 &&
                       (a->mode == DMH_PASTE_WARP_ONLY || a->scene != nullptr);
     // the tiled kernel's LDS rectangle must hold the taps of a TH x TW output tile
     const float rh = (float)a->SH / (float)a->OH, rw = (float)a->SW / (float)a->OW;
     const bool tiled = vec4 && (int)floorf(rh * (TH - 1)) + 3 <= RMAX && (int)floorf(rw * (TW - 1)) + 3 <= CMAX;
+    return tiled ? 2 : (vec4 ? 1 : 0);
+}
+
+int dmh_eot_paste_fwd(const dmh_paste_args* a, float* adv, float* mask_out, void* stream) {
+    const int form = dmh_eot_paste_fwd_form(a, adv, mask_out);
+    if (form < 0) return DMH_EINVAL;
+    const bool tiled = form == 2, vec4 = form >= 1;
     if (tiled)
         hipLaunchKernelGGL(paste_fwd_tile_kernel, dim3((a->OW + TW - 1) / TW, (a->OH + TH - 1) / TH, a->N), dim3(NT), 0,
                            (hipStream_t)stream, *a, adv, mask_out);

@@ -192,6 +192,10 @@ typedef struct dmh_paste_args {
 
 /* adv [N,3,OH,OW], mask_out [N,1,OH,OW] (either may be NULL) */
 int dmh_eot_paste_fwd(const dmh_paste_args* a, float* adv, float* mask_out, void* stream);
+/* Host only, no launch: the kernel dmh_eot_paste_fwd takes for these arguments (it decides through this function).
+ * 2 = tiled (OW % 4 == 0, both outputs 16-byte aligned, resize ratios the LDS rectangle holds), 1 = four-wide (the same
+ * without the ratio limit), 0 = generic, -1 = arguments the forward rejects. */
+int dmh_eot_paste_fwd_form(const dmh_paste_args* a, const float* adv, const float* mask_out);
 /* g_patch [1,3,PH,PW] is overwritten (gather per patch texel over the inverse homography: no atomics, bitwise
  * reproducible; the caller does not have to zero it). */
 int dmh_eot_paste_bwd(const dmh_paste_args* a, const float* g_adv, float* g_patch, void* stream);

@@ -67,6 +67,13 @@ int main(void) {
     pa.N = 2; pa.mode = 99;
     EXPECT(dmh_eot_paste_fwd(&pa, one, one, NULL) == DMH_EINVAL);
     EXPECT(dmh_eot_paste_bwd(&pa, one, one, NULL) == DMH_EINVAL);
+    EXPECT(dmh_eot_paste_fwd_form(&pa, one, one) == -1);
+    pa.mode = DMH_PASTE_COMPOSITE;      /* the forms of the attack's resolutions, and an output 4 bytes off alignment */
+    EXPECT(dmh_eot_paste_fwd_form(&pa, one, one) == 2);
+    EXPECT(dmh_eot_paste_fwd_form(&pa, one + 1, one) == 0);
+    EXPECT(dmh_eot_paste_fwd_form(&pa, NULL, NULL) == -1);
+    pa.OH = 288; pa.OW = 960;
+    EXPECT(dmh_eot_paste_fwd_form(&pa, one, NULL) == 1);
 
     /* K4 - K6, K6b */
     EXPECT(dmh_pgd_linf_step(NULL, NULL, NULL, 0.1f, 0.1f, NULL, 0, NULL) == DMH_EINVAL);

@@ -53,6 +53,33 @@ def test_host_side_argument_checks_without_gpu():
     assert lib.dmh_photo_loss_fwd(ctypes.byref(p), (ctypes.c_void_p * 4)(), (ctypes.c_void_p * 4)(), None, None) == 1
 
 
+def test_launch_forms_of_the_eot_paste_without_gpu():
+    """K3's forward switches kernel by output width, pointer alignment and resize ratio; dmh_eot_paste_fwd decides through
+    dmh_eot_paste_fwd_form, and tests/test_gpu_paste_anchor.py asserts through it which form each of its cases reached.
+    The workload's forms (2 = tiled, 1 = four-wide, 0 = generic): a change of RMAX / CMAX shows here."""
+    from depthmodelhardening_amd import _native as N
+    lib = N.lib()
+    one, off = ctypes.c_void_p(64), ctypes.c_void_p(68)      # dummies: 16-byte aligned, and one float off
+    a = N.PasteArgs()
+    assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), one, one) == -1
+    a.scene, a.patch, a.pmask, a.coeffs = one, one, one, one
+    a.N, a.SH, a.SW, a.PH, a.PW, a.l_pad, a.t_pad = 12, 375, 1242, 260, 300, 471, 57
+    for (OH, OW), form in (((320, 1024), 2), ((330, 1100), 2), ((288, 960), 1), ((375, 1242), 0), ((192, 640), 1)):
+        a.OH, a.OW = OH, OW
+        assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), one, one) == form, (OH, OW)
+        assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), one, None) == form and lib.dmh_eot_paste_fwd_form(ctypes.byref(a), None, one) == form
+    a.OH, a.OW = 320, 1024
+    assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), off, one) == 0 and lib.dmh_eot_paste_fwd_form(ctypes.byref(a), one, off) == 0
+    assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), None, None) == -1 and b"no output" in lib.dmh_last_error()
+    a.mode = N.PASTE_WARP_ONLY
+    a.scene = None
+    assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), one, one) == 2
+    a.mode = N.PASTE_COMPOSITE
+    assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), one, one) == -1          # a composite needs its scene
+    a.mode = 7
+    assert lib.dmh_eot_paste_fwd_form(ctypes.byref(a), one, one) == -1
+
+
 def test_convolution_entry_points_reject_bad_shapes_without_gpu():
     """K10-K13 / K9 statistics: host-side argument checks and size helpers (no launch, no GPU)."""
     from depthmodelhardening_amd import _native as N
