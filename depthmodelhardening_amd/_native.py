@@ -192,6 +192,8 @@ _SIGNATURES = {
     "dmh_velo_depth_ws_size": (C.c_int64, [C.c_int64, C.c_int64]),
     "dmh_velo_depth_map": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                      _fp, _fp, _fp]),
+    "dmh_color_jitter_ws_size": (C.c_int64, [C.c_int] * 4),
+    "dmh_color_jitter": (C.c_int, [C.POINTER(_fp)] * 3 + [C.c_int] * 4 + [_fp, C.c_int, _fp, _fp]),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

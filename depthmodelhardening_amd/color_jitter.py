@@ -11,9 +11,14 @@ torchvision is absent from this image; the operations follow the published v0.8.
 [0, 1], ITU-R 601 grayscale 0.2989 / 0.587 / 0.114, per-image mean for the contrast, hue rotation in HSV).  The HSV -> RGB step is
 written in the closed form  c_n = v - v s max(0, min(k_n, 4 - k_n, 1)),  k_n = (n + 6 h) mod 6,  n = 5, 3, 1,  which equals
 torchvision's six-case table; oracle/tv082.py restates the table itself and tests/test_host_logic.py holds the two to each other.
+
+The KITTI loader's ``jitter="pil"`` applies the same drawn transform as torchvision 0.8.2 does to 8-bit PIL images, by K33
+(``ops.pil_color_jitter``); ``pil_records`` below turns ``JitterParams`` into the kernel's per-item record.  The float operations
+here stay as they are: the attack differentiates through them.
 """
 import random
 
+import numpy as np
 import torch
 
 
@@ -91,3 +96,38 @@ def _hue(img, f):
 
 
 _OPS = {"brightness": _brightness, "contrast": _contrast, "saturation": _saturation, "hue": _hue}
+
+
+PIL_OP_CODES = {"brightness": 0, "contrast": 1, "saturation": 2, "hue": 3}      # K33's operation codes (include/dmh_hip.h)
+
+
+def pil_hue_shift(hue):
+    """torchvision 0.8.2's PIL adjust_hue adds ``np.uint8(hue_factor * 255)`` to the H byte: the product truncated toward zero,
+    then wrapped to a byte (-0.1 -> 231, -0.001 -> 0)."""
+    if not (-0.5 <= hue <= 0.5):
+        raise ValueError('hue_factor ({}) is not in [-0.5, 0.5].'.format(hue))
+    return int(hue * 255) % 256
+
+
+def pil_records(params):
+    """K33's records of a batch, int32 [B, 8]: per item the count of operations (0 for ``None``: the item is only converted to
+    float), their codes in the order they are applied (one per byte, the first in the low byte), the brightness, contrast and
+    saturation factors rounded to float32 (their bits), the hue shift as a byte, and two zeros."""
+    params = list(params)
+    rec = np.zeros((len(params), 8), dtype=np.int32)
+    for i, p in enumerate(params):
+        if p is None:
+            continue
+        if len(set(p.order)) != len(p.order) or any(name not in PIL_OP_CODES for name in p.order):
+            raise RuntimeError("pil_records: the order must name each of %s at most once; got %s" % (sorted(PIL_OP_CODES), p.order))
+        rec[i, 0] = len(p.order)
+        rec[i, 1] = sum(PIL_OP_CODES[name] << (8 * k) for k, name in enumerate(p.order))
+        rec[i, 2:5] = np.array([p.factors["brightness"], p.factors["contrast"], p.factors["saturation"]], dtype=np.float32).view(np.int32)
+        rec[i, 5] = pil_hue_shift(p.factors["hue"])
+    return rec
+
+
+def records_have_contrast(rec):
+    """Whether any item of the records takes a contrast step (K33's first pass runs only then)."""
+    rec = np.asarray(rec, dtype=np.int32).reshape(-1, 8)
+    return any(((int(r[1]) >> (8 * k)) & 255) == PIL_OP_CODES["contrast"] for r in rec for k in range(min(max(int(r[0]), 0), 4)))

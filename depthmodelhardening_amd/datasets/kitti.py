@@ -19,12 +19,19 @@ Device side, ``preprocess="reference"``: what ``MonoDataset.preprocess`` does wi
 ``preprocess="fast"``: the synthetic set's path fed from files -- K3 resizes bilinearly inside the paste, benign frames are
 resized by F.interpolate, the coarse levels are 2^s box means.  Not the reference's pixels; half the launches.
 
-Departures, stated: ColorJitter (only with ``color_aug``, for half of the samples, mono_dataset.py:297,344-348) is applied to the
-float level 0 with color_jitter.py's tensor operations, not to the 8-bit PIL image, and the coarser ``color_aug`` levels are not
-built (nothing reads them).  Under
+ColorJitter (only with ``color_aug``, for half of the samples, mono_dataset.py:297,344-348): ``jitter="pil"`` keeps K31's level-0
+bytes of the keys that are jittered and runs torchvision 0.8.2's ColorJitter on them as Pillow computes it on the 8-bit image --
+a byte after each of the four operations, the grey of the saturation step as Pillow's integer L, the contrast mean of every
+image, the hue shifted on the H byte -- by ``ops.pil_color_jitter`` (K33): one call for every key of the batch, two launches, none
+when no coin fell.  ``jitter="float"`` (the default) applies color_jitter.py's tensor operations to the float level 0 in a loop
+over items and keys.
+
+Departures, stated: with ``jitter="float"`` the jittered pixels are not the reference's (``jitter="pil"`` removes this one); the
+coarser ``color_aug`` levels are not built (nothing reads them).  Under
 ``half_no_synthesis`` the samples without an object take the float round trip of the others, which returns every byte
 ((v / 255.f) * 255.f truncates to v for all 256 values: tests/test_pil_resample_ref.py).  The reference pins Pillow
-5.4.1; K31 is held to the Pillow that is installed (12.x), whose 8-bit resample is believed, not checked, to round the same way.
+5.4.1; K31 and K33 are held to the Pillow that is installed (12.x), whose 8-bit resample, blend and HSV conversions are believed,
+not checked, to round the same way.
 
 ``depth_gt`` (kitti_dataset.py:70-85): when the scan of the first split line exists (``check_depth``), the scans of a batch are read
 by the same pool with ``np.fromfile`` into a pinned float32 buffer [points, 4], ragged, the offsets from the file sizes, uploaded with
@@ -205,16 +212,21 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
     (``set_adv_train``, ``update_adv_obj``, ``begin_epoch``), ``synthesize`` and ``_camera`` are the base class's code."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, device, is_train=False, img_ext=".jpg",
-                 seed=1234, num_workers=12, preprocess="reference", color_aug=False, full_res_shape=(ori_H, ori_W)):
+                 seed=1234, num_workers=12, preprocess="reference", color_aug=False, full_res_shape=(ori_H, ori_W), jitter="float"):
         if preprocess not in ("reference", "fast"):
             raise RuntimeError("kitti_preprocess must be 'reference' or 'fast'; got %r" % (preprocess,))
+        if jitter not in ("float", "pil"):
+            raise RuntimeError("kitti_jitter must be 'float' or 'pil'; got %r" % (jitter,))
+        if jitter == "pil" and preprocess != "reference":
+            raise RuntimeError("kitti_jitter 'pil' jitters the 8-bit level 0 that kitti_preprocess 'reference' builds; "
+                               "kitti_preprocess %r has no PIL bytes" % (preprocess,))
         if not filenames:
             raise RuntimeError("KITTIRAWDataset: the split list is empty")
         self.data_path, self.filenames = data_path, list(filenames)
         # the base class's state (sizes, self.rng: the per-sample draws in __getitem__'s order, switches, camera); no pool of frames
         self._init_common(height, width, list(frame_idxs), num_scales, len(self.filenames), device, seed)
         self.is_train, self.img_ext = bool(is_train), img_ext
-        self.preprocess, self.color_aug = preprocess, bool(color_aug)
+        self.preprocess, self.color_aug, self.jitter = preprocess, bool(color_aug), jitter
         self.order_rng = random.Random(seed + 1)     # the DataLoader's shuffle: apart, so that it never moves a draw
         self.flip_augmentation = self.is_train       # mono_dataset.py:298
         self.full_res_shape = (int(full_res_shape[0]), int(full_res_shape[1]))      # depth_gt's size (kitti_dataset.py:34)
@@ -308,14 +320,18 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
             out[to_device_async(members, raw.device, torch.int64)] = x
         return out
 
-    def _levels(self, inputs, view, src, flip=None, sizes=None, full=True):
-        """("color", view, s) by K31 from ``src`` (raw uint8 HWC with sizes and flip, or a float frame)."""
+    def _levels(self, inputs, view, src, flip=None, sizes=None, full=True, keep_u8=False):
+        """("color", view, s) by K31 from ``src`` (raw uint8 HWC with sizes and flip, or a float frame); returns the level-0 bytes
+        with ``keep_u8`` (K33 jitters them)."""
         H, W = self.height, self.width
         if full:
-            for s, lvl in enumerate(ops.pil_pyramid(src, H, W, self.num_scales, "lanczos", flip, sizes)):
+            levels = ops.pil_pyramid(src, H, W, self.num_scales, "lanczos", flip, sizes)
+            for s, lvl in enumerate(levels):
                 inputs[("color", view, s)] = lvl.f32
-        else:
-            inputs[("color", view, 0)] = ops.pil_resize(src, (H, W), "lanczos", flip, sizes, want_u8=False).f32
+            return levels[0].u8
+        lvl = ops.pil_resize(src, (H, W), "lanczos", flip, sizes, want_u8=keep_u8)
+        inputs[("color", view, 0)] = lvl.f32
+        return lvl.u8
 
     def _box_levels(self, inputs, view, img):
         inputs[("color", view, 0)] = img
@@ -351,6 +367,8 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
         flip = to_device_async([int(f) for f in geo["flip"]], dev, torch.int32) if any(geo["flip"]) else None
         reference = self.preprocess == "reference"
         inputs = {}
+        pil_jitter = self.jitter == "pil" and any(geo["jitter"])
+        u8 = {}         # the level-0 bytes of the keys K33 jitters
         if self.is_adv_train:
             # frame 0 / the opposite view as a pool of float frames that K3 reads by index, as the synthetic set's pool is read
             self.raw = torch.cat([self._float_frames(view_raw[0], view_sizes[0]), self._float_frames(view_raw["s"], view_sizes["s"])], 0)
@@ -358,9 +376,10 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
             out_size = (ori_H, ori_W) if reference else (H, W)
             aug0, aug_s, ben0, mask0 = self.synthesize(None, None, geo, out_size, pool_index=(both[0], both[1]))
             if reference:
-                inputs[("color_aug", 0, 0)] = ops.pil_resize(aug0, (H, W), want_u8=False).f32
-                self._levels(inputs, 0, ben0)                                   # ("color", 0, -1) = color_ben, :257
-                self._levels(inputs, "s", aug_s, full=self.right_pyramid)       # ("color", "s", -1) = color_aug("s"), :258
+                lvl = ops.pil_resize(aug0, (H, W), want_u8=pil_jitter)
+                inputs[("color_aug", 0, 0)], u8[("color_aug", 0, 0)] = lvl.f32, lvl.u8
+                u8[("color_ben", 0, 0)] = self._levels(inputs, 0, ben0)         # ("color", 0, -1) = color_ben, :257
+                u8[("color_aug", "s", 0)] = self._levels(inputs, "s", aug_s, full=self.right_pyramid, keep_u8=pil_jitter)   # :258
                 inputs[("color_ben", 0, 0)] = inputs[("color", 0, 0)]
                 mask0 = ops.pil_resize(mask0, (H, W), want_u8=False).f32
             else:
@@ -378,7 +397,8 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
             plain = self.views
         for v in plain:
             if reference:
-                self._levels(inputs, v, view_raw[v], flip, view_sizes[v], full=(v == 0 or self.right_pyramid))
+                u8[("color_aug", v, 0)] = self._levels(inputs, v, view_raw[v], flip, view_sizes[v],
+                                                       full=(v == 0 or self.right_pyramid), keep_u8=pil_jitter)
             else:
                 img = F.interpolate(self._float_frames(view_raw[v], view_sizes[v]), [H, W], mode="bilinear", align_corners=False)
                 if flip is not None:
@@ -391,9 +411,14 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
                 raise RuntimeError("KITTIRAWDataset: depth_gt needs the camera side of every split line")
             inputs["depth_gt"] = self._depth_gt(k, idx, sides, flip)
         self._prefetch.release(k)
-        if any(geo["jitter"]):
-            # mono_dataset.py:344-348 on the float level 0 (the reference jitters the 8-bit image): one transform per item, the
-            # same for every frame of the item
+        if pil_jitter:
+            # mono_dataset.py:344-348 on the 8-bit level 0: one transform per item, the same for every frame of the item; every
+            # key of the batch in one call of K33, the items whose coin did not fall are only converted
+            keys = [q for q in inputs if q[0] in ("color_aug", "color_ben")]
+            for key, res in zip(keys, ops.pil_color_jitter([u8[q] for q in keys], geo["jitter_params"])):
+                inputs[key] = res.f32
+        elif any(geo["jitter"]):
+            # the same on the float level 0 by tensor operations: not the reference's pixels
             for i, aug in enumerate(geo["jitter_params"]):
                 if aug is None:
                     continue
@@ -521,7 +546,8 @@ def from_options(opt, device, rank=0):
     lines = read_split(os.path.join(opt.split_dir, opt.split, "train_files.txt"))
     dataset = KITTIRAWDataset(opt.data_path, lines, opt.height, opt.width, opt.frame_ids, 4, device, is_train=True,
                               img_ext=".png" if opt.png else ".jpg", seed=opt.seed + rank, num_workers=opt.num_workers,
-                              preprocess=opt.kitti_preprocess, color_aug=opt.contrastive_learning)
+                              preprocess=opt.kitti_preprocess, color_aug=opt.contrastive_learning,
+                              jitter=opt.kitti_jitter)
     if opt.adv_train:
         if not opt.scene_root:
             raise RuntimeError("--dataset kitti with --adv_train reads the attack's scenes from --scene_root")

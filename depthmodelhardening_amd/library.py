@@ -34,6 +34,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::cost_volume_into     the same, cost_volume * confidence written into channels 64 .. of ``buffer``   (K30, in place)
     dmh::pil_resample         MD2/datasets/mono_dataset.py:100-104,119-144 (PIL.Image.resize, 8-bit, bit for bit)   (K31, no autograd)
     dmh::velo_depth_map       MD2/kitti_utils.py:46-98 + datasets/kitti_dataset.py:70-85 (generate_depth_map, float32-equal) (K32, no autograd)
+    dmh::color_jitter         MD2/datasets/mono_dataset.py:344-348,133,144 (torchvision 0.8.2 ColorJitter on 8-bit PIL images, Pillow's bytes) (K33, no autograd)
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -730,8 +731,24 @@ def _(points, offsets, proj, shapes, vel_depth=False, out_size=None, flip=None):
     return points.new_empty((sum(h * w for h, w in zip(shapes[0::2], shapes[1::2])),))
 
 
+# ---------------------------------------------------------------------------------------------------------------- K33
+@custom_op("dmh::color_jitter", mutates_args=())
+def color_jitter(images: List[torch.Tensor], record: torch.Tensor, want_u8: bool = False) -> List[torch.Tensor]:
+    """``images``: up to 8 uint8 [B, 3, H, W]; ``record``: int32 [B, 8] on their device (color_jitter.pil_records).  Returns the
+    float32 results (byte / 255), one per tensor, followed with ``want_u8`` by the uint8 results.  Images carry no gradient."""
+    for t in images:
+        ops._need_cuda(t)
+    res = ops.pil_color_jitter(images, record, want_u8)
+    return [r.f32 for r in res] + ([r.u8 for r in res] if want_u8 else [])
+
+
+@color_jitter.register_fake
+def _(images, record, want_u8=False):
+    return [t.new_empty(t.shape, dtype=torch.float32) for t in images] + ([t.new_empty(t.shape) for t in images] if want_u8 else [])
+
+
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
-       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map")
+       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter")

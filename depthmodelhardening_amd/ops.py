@@ -3506,3 +3506,148 @@ def velo_depth_map(points, offsets, proj, shapes, vel_depth=False, out_size=None
         N.ptr(None if flip is None else _c(flip)), n, int(bool(vel_depth)), total_cells, total_rows, oh, ow, N.ptr(ws), N.ptr(out),
         N.stream()), points.numel() * 4 + 8 * words + out.numel() * 4))
     return out if out_size is not None else (out, cell_off)
+
+
+# ---------------------------------------------------------------------------------------------------------------- K33
+JITTER_MAX_TENSORS = 8                  # DMH_JITTER_MAX_TENSORS
+JITTER_MAX_PIXELS = (2 ** 32 - 1) // 255  # 255 H W must fit the 32-bit sum of L
+
+
+def _jitter_L(img):
+    """Pillow's ``convert("L")`` of uint8 [3, H, W] -> int32 [H, W]."""
+    r, g, b = (img[c].astype(np.int32) for c in range(3))
+    return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+
+
+def _jitter_blend(deg, img, f):
+    """``Image.blend(degenerate, image, f)`` per channel: float32, the product and the sum rounded separately; truncated to a byte
+    for 0 <= f <= 1, clipped outside."""
+    f = np.float32(f)
+    d = np.asarray(deg).astype(np.float32)
+    t = d + f * (img.astype(np.float32) - d)
+    if np.float32(0) <= f <= np.float32(1):
+        return t.astype(np.int32).astype(np.uint8)
+    with np.errstate(invalid="ignore"):
+        return np.where(t <= 0, 0, np.where(t >= 255, 255, t.astype(np.int32))).astype(np.uint8)
+
+
+def _jitter_hue(img, shift):
+    """``convert("HSV")``, the shift added to the H byte modulo 256, ``convert("RGB")`` (Pillow's Convert.c rgb2hsv / hsv2rgb)."""
+    r, g, b = (img[c].astype(np.int32) for c in range(3))
+    mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    flat = mx == mn
+    cr = np.where(flat, 1, mx - mn).astype(np.float32)
+    s = cr / np.where(flat, 1, mx).astype(np.float32)
+    rc, gc, bc = ((mx - c).astype(np.float32) / cr for c in (r, g, b))
+    rc64, gc64, bc64 = (c.astype(np.float64) for c in (rc, gc, bc))
+    h = np.where(r == mx, bc64 - gc64, np.where(g == mx, 2.0 + rc64 - bc64, 4.0 + gc64 - rc64)).astype(np.float32)
+    h = np.fmod(h.astype(np.float64) / 6.0 + 1.0, 1.0).astype(np.float32)
+    H = np.where(flat, 0, np.clip((h.astype(np.float64) * 255.0).astype(np.int32), 0, 255))
+    S = np.where(flat, 0, np.clip((s.astype(np.float64) * 255.0).astype(np.int32), 0, 255))
+    V = mx
+    H = (H + int(shift)) & 255
+    fs = S / 255.0
+    x = H * 6.0 / 255.0
+    i = np.floor(x)
+    fr = x - i
+
+    def byte(z):        # C's round (half away from zero; z >= 0 here), then CLIP8
+        return np.clip(np.floor(z + 0.5), 0, 255).astype(np.int32)
+    p, q, t = byte(V * (1.0 - fs)), byte(V * (1.0 - fs * fr)), byte(V * (1.0 - fs * (1.0 - fr)))
+    k = i.astype(np.int32) % 6
+    grey = S == 0
+    out = [np.where(grey, V, np.choose(k, table)) for table in ((V, q, p, p, t, V), (t, V, V, q, p, p), (p, p, t, V, V, q))]
+    return np.stack(out).astype(np.uint8)
+
+
+def pil_color_jitter_host(images, records, sums=None):
+    """Host twin of K33 in numpy, bit-equal to Pillow: torchvision 0.8.2's ColorJitter on 8-bit PIL images.  ``images``: uint8
+    arrays [B, 3, H, W]; ``records``: int32 [B, 8] (color_jitter.pil_records).  Every operation ends in a byte: brightness =
+    blend(0, img, f), saturation = blend(L(img), img, f), contrast = blend(m, img, f) with m = int(mean of L over this image as the
+    operations before left it + 0.5), hue = the HSV round trip with the shifted H byte.  Returns the uint8 results; ``sums`` (a
+    list) receives the integer sum of L of every image that took a contrast step."""
+    records = np.asarray(records, dtype=np.int32).reshape(-1, 8)
+    out = []
+    for img in images:
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 4 or img.shape[1] != 3 or img.shape[0] != records.shape[0]:
+            raise RuntimeError("pil_color_jitter_host: need uint8 arrays [%d, 3, H, W]; got %s %s" % (records.shape[0], img.dtype, img.shape))
+        res = np.empty_like(img)
+        for i, rec in enumerate(records):
+            x = img[i]
+            factors = rec[2:5].view(np.float32)
+            seen_contrast = False
+            for k in range(min(max(int(rec[0]), 0), 4)):
+                op = (int(rec[1]) >> (8 * k)) & 255
+                if op == 0:
+                    x = _jitter_blend(0, x, factors[0])
+                elif op == 1:
+                    L = _jitter_L(x)
+                    S = int(L.sum(dtype=np.int64))
+                    if sums is not None and not seen_contrast:
+                        sums.append(S)
+                    seen_contrast = True
+                    x = _jitter_blend(int(S / float(L.size) + 0.5), x, factors[1])
+                elif op == 2:
+                    x = _jitter_blend(_jitter_L(x)[None], x, factors[2])
+                elif op == 3:
+                    x = _jitter_hue(x, int(rec[5]) & 255)
+            res[i] = x
+        out.append(res)
+    return out
+
+
+def pil_color_jitter(images, params, want_u8=False):
+    """K33: torchvision 0.8.2's ``ColorJitter`` on 8-bit PIL images (MD2/datasets/mono_dataset.py:344-348, :133, :144), Pillow's
+    bytes, for a whole batch and all its keys in two launches (one when no item has a contrast step).
+
+    images   a list of at most 8 uint8 tensors [B, 3, H, W] on one device (K31's level-0 ``u8``): item i of every tensor takes
+             transform i; every image has its own contrast mean.
+    params   a list of B ``color_jitter.JitterParams`` or None (None: the item is only converted), or the prepared int32 record
+             [B, 8] on the images' device (``color_jitter.pil_records``; a captured graph reads it at every replay).
+    Returns  a list of PilLevel(u8 or None, f32 = u8.float() / 255), one per tensor.
+
+    CPU tensors run ``pil_color_jitter_host``, the numpy restatement the kernel is bit-equal to."""
+    from . import color_jitter
+    from .my_utils import to_device_async
+    images = list(images)
+    if not 1 <= len(images) <= JITTER_MAX_TENSORS:
+        raise RuntimeError("pil_color_jitter: one call takes 1 .. %d tensors; got %d" % (JITTER_MAX_TENSORS, len(images)))
+    first = images[0]
+    for t in images:
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[1] != 3 or t.shape != first.shape or t.device != first.device:
+            raise RuntimeError("pil_color_jitter: images must be uint8 tensors [B, 3, H, W] of one shape on one device; got %s %s"
+                               % (getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    B, _, H, W = (int(v) for v in first.shape)
+    if B < 1 or H < 1 or W < 1 or H * W > JITTER_MAX_PIXELS:
+        raise RuntimeError("pil_color_jitter: need a non-empty batch of images of at most %d pixels (255 H W must fit 32 bits); "
+                           "got %d x %d x %d" % (JITTER_MAX_PIXELS, B, H, W))
+    dev = first.device
+    if torch.is_tensor(params):
+        if params.dtype != torch.int32 or params.numel() != 8 * B or params.device != dev:
+            raise RuntimeError("pil_color_jitter: a prepared record is an int32 tensor [%d, 8] on %s" % (B, dev))
+        rec, with_contrast = params, True
+    else:
+        host = color_jitter.pil_records(params)
+        if host.shape[0] != B:
+            raise RuntimeError("pil_color_jitter: params must hold one entry per item (%d); got %d" % (B, host.shape[0]))
+        with_contrast = bool(color_jitter.records_have_contrast(host))
+        rec = host if dev.type != "cuda" else to_device_async(host, dev)
+    if dev.type != "cuda":
+        res = [torch.from_numpy(a) for a in pil_color_jitter_host([t.numpy() for t in images], rec.numpy() if torch.is_tensor(rec) else rec)]
+        return [PilLevel(u8 if want_u8 else None, u8.float().div(255)) for u8 in res]
+    images = [_c(t) for t in images]
+    rec = _c(rec)
+    f32 = [torch.empty((B, 3, H, W), device=dev, dtype=torch.float32) for _ in images]
+    u8 = [torch.empty((B, 3, H, W), device=dev, dtype=torch.uint8) for _ in images] if want_u8 else None
+    T = len(images)
+    words = N.lib().dmh_color_jitter_ws_size(T, B, H, W)
+    if words < 0:
+        raise RuntimeError("pil_color_jitter: %d tensors of %d x 3 x %d x %d are more than one call takes (T B <= 65535, "
+                           "B 3 H W < 2^31)" % (T, B, H, W))
+    ws = torch.empty(words, device=dev, dtype=torch.int32) if with_contrast else None
+    N.check(_timed("color_jitter", lambda: N.lib().dmh_color_jitter(
+        N.ptr_array(images, JITTER_MAX_TENSORS), N.ptr_array(f32, JITTER_MAX_TENSORS),
+        N.ptr_array(u8, JITTER_MAX_TENSORS) if want_u8 else None, T, B, H, W, N.ptr(rec), int(with_contrast), N.ptr(ws), N.stream()),
+        T * B * H * W * 3 * (1 + 4 + int(want_u8)) + (T * B * H * W * 3 if with_contrast else 0)))
+    return [PilLevel(u8[i] if want_u8 else None, f32[i]) for i in range(T)]

@@ -99,6 +99,10 @@ class MonodepthOptions:
                        help="--dataset kitti: reference = the loader's PIL chain on the device, bit for bit (K31: LANCZOS levels "
                             "from 8-bit levels, the 8-bit round trip of the pasted frames); fast = the synthetic set's path fed "
                             "from files (bilinear resize inside the paste, box-mean levels): NOT the reference's pixels")
+        p.add_argument("--kitti_jitter", type=str, default="float", choices=["float", "pil"],
+                       help="--dataset kitti with --contrastive_learning: float = ColorJitter by tensor operations on the float "
+                            "level 0 (NOT the reference's pixels); pil = torchvision 0.8.2's ColorJitter on the 8-bit level 0, "
+                            "Pillow's bytes, in two launches (K33); needs --kitti_preprocess reference")
         p.add_argument("--eval_gt_path", type=str,
                        help="evaluate_depth: the ground truth, an .npz with the object array ``data`` of 2-D maps (the reference "
                             "reads splits/<eval_split>/gt_depths.npz); default with --dataset synthetic: made-up LiDAR-like maps")

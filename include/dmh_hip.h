@@ -882,6 +882,35 @@ int dmh_velo_depth_map(const float* points, int64_t npts, const int32_t* offsets
                        const int32_t* flip, int n, int vel_depth, int64_t total_cells, int64_t total_rows, int out_h, int out_w,
                        uint32_t* ws, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K33 torchvision 0.8.2's ColorJitter on 8-bit PIL images (MD2/datasets/mono_dataset.py:344-348, :133, :144), Pillow's bytes: the
+ *     four operations in each item's own order, a byte after every one, for a batch and up to DMH_JITTER_MAX_TENSORS of its keys.
+ *     src / out_f32 / out_u8: host arrays of T device pointers, every tensor [B][3][H][W] (planar); out_u8 may be NULL (no byte
+ *     output).  out_f32 = (float)byte / 255.f (IEEE division, K31's expression).  Item i of every tensor takes record i; every
+ *     image (tensor, item) has its own contrast mean.
+ *     rec: int32 [B][8] in device memory per item = the count of operations (0 .. 4; 0: the image is only converted), their codes
+ *     in the order they are applied, one per byte, the first in the low byte (0 brightness, 1 contrast, 2 saturation, 3 hue; each
+ *     at most once, another code does nothing), the bits of the float32 brightness, contrast and saturation factors, the hue shift
+ *     (a byte: ((int)(hue_factor * 255)) mod 256), 0, 0.  It is read on the device only, so a captured graph replays with the
+ *     values it holds then.
+ *     L = (19595 r + 38470 g + 7471 b + 32768) >> 16.  blend(deg, v, f): t = (float)deg + f * (float)(v - deg) in float32 without
+ *     contraction; (int)t for 0 <= f <= 1, else 0 if t <= 0, 255 if t >= 255, (int)t between.  brightness = blend(0, v, f);
+ *     saturation = blend(L, v, f); contrast = blend(m, v, f) with m = (int)((double)S / (double)(H W) + 0.5), S the sum of L over
+ *     the image as the operations before the contrast left it; hue = Pillow's rgb2hsv (float32 quotients, the hue through double),
+ *     H + shift modulo 256, hsv2rgb (double, C's round).
+ *     with_contrast != 0: a first pass stores every workgroup's 32-bit sum of L into its slot of ws (uint32,
+ *     dmh_color_jitter_ws_size(T, B, H, W) words, -1 for shapes the launcher refuses; contents ignored, nothing to clear) and the
+ *     second pass adds the slots of its image; 0 promises that no record holds a contrast step (its mean would read as 0).
+ *     1 <= T <= 8, T B <= 65535, H W <= DMH_JITTER_MAX_PIXELS (255 H W fits 32 bits), B 3 H W < 2^31.  Four pixels per thread when
+ *     H W is a multiple of 4 and the pointers are aligned (src, out_u8 to 4 bytes, out_f32 to 16), one otherwise.  At most two
+ *     launches; integer sums only, no atomics, no host read: bitwise reproducible.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_JITTER_MAX_TENSORS 8
+#define DMH_JITTER_MAX_PIXELS 16843009
+int64_t dmh_color_jitter_ws_size(int T, int B, int H, int W);
+int dmh_color_jitter(const uint8_t* const* src, float* const* out_f32, uint8_t* const* out_u8, int T, int B, int H, int W,
+                     const int32_t* rec, int with_contrast, uint32_t* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
