@@ -194,6 +194,8 @@ _SIGNATURES = {
                                      _fp, _fp, _fp]),
     "dmh_color_jitter_ws_size": (C.c_int64, [C.c_int] * 4),
     "dmh_color_jitter": (C.c_int, [C.POINTER(_fp)] * 3 + [C.c_int] * 4 + [_fp, C.c_int, _fp, _fp]),
+    "dmh_depth_hint_fuse": (C.c_int, [_fp] * 3 + [C.c_int] + [_fp] * 3 + [C.c_int] * 4 + [_fp] * 3),
+    "dmh_depth_hint_prepare": (C.c_int, [_fp] * 4 + [C.c_int64] * 2 + [C.c_int] * 5 + [_fp] * 3),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

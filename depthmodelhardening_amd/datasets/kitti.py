@@ -39,6 +39,13 @@ the frames; ``ops.velo_depth_map`` (K32) projects them with the camera of the sp
 mirrors the flipped samples -> inputs["depth_gt"] [B, 1, 375, 1242].  The resize is K32's integer nearest rule, not
 scikit-image 0.17.2's fitted affine map.
 
+``depth_hint`` / ``depth_hint_mask`` (depth-hints/datasets/mono_dataset.py:368-388, with ``use_depth_hints``): the ``.npy`` hint of every
+item (``<depth_hint_path>/<folder>/image_0{2,3}/<frame:010d>.npy``, float32 [1, Hs, Ws], written by precompute_depth_hints.py) is read
+by the same pool into a pinned float32 buffer and uploaded with the frames; ``ops.depth_hint_prepare`` (K34's second kernel)
+mirrors the flipped items, resizes to (height, width) by OpenCV's INTER_NEAREST rule and forms the mask (hint > 0), one launch.
+A missing file raises the reference's ``FileNotFoundError``.  The hints of one batch must share a size (the precompute tool writes
+one size); the adversarial paste leaves hints untouched, as in the reference.
+
 PIL is imported here (and by export_gt_depth's PNG branch) and nowhere else in the package, when a file is first decoded.
 """
 import os
@@ -110,6 +117,27 @@ def decode_into(path, slot):
     return h, w
 
 
+def hint_path(depth_hint_path, folder, frame_index, side):
+    """depth-hints/datasets/mono_dataset.py:369-371."""
+    return os.path.join(depth_hint_path, folder, "image_02" if side == "l" else "image_03", str(frame_index).zfill(10) + ".npy")
+
+
+def load_hint(item):
+    """``np.load(path)[0]`` of (depth_hint_path, folder, frame_index, side) as float32 [Hs, Ws]; a missing file raises with the
+    reference's wording (mono_dataset.py:373-380)."""
+    root, folder, frame_index, side = item
+    try:
+        depth = np.load(hint_path(root, folder, frame_index, side))[0]
+    except FileNotFoundError:
+        raise FileNotFoundError("Warning - cannot find depth hint for {} {} {}! "
+                                "Either specify the correct path in option "
+                                "--depth_hint_path, or run precompute_depth_hints.py to"
+                                "train with depth hints".format(folder, "image_02" if side == "l" else "image_03", frame_index))
+    if depth.ndim != 2:
+        raise RuntimeError("depth hint %s must be an array [1, H, W]; got %s" % (hint_path(root, folder, frame_index, side), (1,) + depth.shape))
+    return np.asarray(depth, dtype=np.float32)
+
+
 class _Prefetcher(object):
     """Two pinned uint8 buffers and their device twins.  ``submit(k, paths)`` decodes batch k into buffer k % 2 on the worker pool
     and uploads it on a side stream from a loader thread; ``take(k)`` returns (device buffer, sizes) once the current stream has
@@ -131,6 +159,29 @@ class _Prefetcher(object):
         # velodyne scans: per buffer a pinned float32 [capacity, 4] and int32 offsets, their device twins; grown on demand
         self.cloud_host, self.cloud_dev = [None, None], [None, None]
         self.clouds = [None, None]       # (device points [total, 4], device offsets int32 [n + 1]) of the buffer's batch
+        # depth hints: per buffer a pinned float32 [n, 1, Hs, Ws] and its device twin; (re)allocated when the shape changes
+        self.hint_host, self.hint_dev = [None, None], [None, None]
+
+    def _load_hints(self, b, items):
+        """The hints ``items`` into buffer b.  Runs after the buffer's last upload finished."""
+        arrs = list(self.workers.map(load_hint, items))
+        if len({a.shape for a in arrs}) != 1:
+            raise RuntimeError("KITTIRAWDataset: the depth hints of one batch must share a size; got %s" % sorted({a.shape for a in arrs}))
+        shape = (len(arrs), 1) + arrs[0].shape
+        if self.hint_host[b] is None or tuple(self.hint_host[b].shape) != shape:
+            if self.cuda and self.consumed[b] is not None:
+                self.consumed[b].synchronize()      # the kernels that read the old device buffer have run
+            self.hint_host[b] = torch.empty(shape, dtype=torch.float32, pin_memory=self.cuda)
+            if self.cuda:
+                self.hint_dev[b] = torch.empty(shape, dtype=torch.float32, device=self.device)
+                fresh = torch.cuda.Event()      # the allocator may hand out memory that queued work still reads
+                fresh.record(torch.cuda.current_stream(self.device))
+                self.side.wait_event(fresh)
+            else:
+                self.hint_dev[b] = self.hint_host[b]
+        view = self.hint_host[b].numpy()
+        for i, a in enumerate(arrs):
+            view[i, 0] = a
 
     def _load_clouds(self, b, velo):
         """The scans ``velo`` into buffer b: ragged, offsets from the file sizes.  Runs after the buffer's last upload finished."""
@@ -156,7 +207,7 @@ class _Prefetcher(object):
         list(self.workers.map(lambda ip: kitti_velo.read_cloud_into(ip[1], pts[offsets[ip[0]]:offsets[ip[0] + 1]]), enumerate(velo)))
         return total, n
 
-    def _load(self, k, paths, velo=None):
+    def _load(self, k, paths, velo=None, hints=None):
         b = k % 2
         if self.cuda and self.uploaded[b] is not None:
             self.uploaded[b].synchronize()          # the pinned buffers are free once their last upload is done
@@ -164,6 +215,8 @@ class _Prefetcher(object):
         total, n = self._load_clouds(b, velo) if velo else (0, 0)
         if velo:
             self.clouds[b] = (self.cloud_dev[b][0][:total], self.cloud_dev[b][1][:n + 1])
+        if hints:
+            self._load_hints(b, hints)
         if self.cuda:
             with torch.cuda.stream(self.side):
                 if self.consumed[b] is not None:
@@ -172,14 +225,17 @@ class _Prefetcher(object):
                 if velo:
                     self.clouds[b][0].copy_(self.cloud_host[b][0][:total], non_blocking=True)
                     self.clouds[b][1].copy_(self.cloud_host[b][1][:n + 1], non_blocking=True)
+                if hints:
+                    self.hint_dev[b].copy_(self.hint_host[b], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.side)
             self.uploaded[b] = ev
         return sizes
 
-    def submit(self, k, paths, velo=None):
+    def submit(self, k, paths, velo=None, hints=None):
         if k not in self.pending:
-            self.pending[k] = (self.loader.submit(self._load, k, list(paths), None if velo is None else list(velo)), len(paths))
+            self.pending[k] = (self.loader.submit(self._load, k, list(paths), None if velo is None else list(velo),
+                                                  None if hints is None else list(hints)), len(paths))
 
     def take(self, k):
         fut, n = self.pending.pop(k)
@@ -194,6 +250,10 @@ class _Prefetcher(object):
     def take_clouds(self, k):
         """(points [total, 4], offsets int32 [n + 1]) of batch k on the device, after ``take(k)``."""
         return self.clouds[k % 2]
+
+    def take_hints(self, k):
+        """float32 [n, 1, Hs, Ws] of batch k on the device, after ``take(k)``."""
+        return self.hint_dev[k % 2]
 
     def release(self, k):
         """The current stream has queued every read of batch k's device buffer."""
@@ -212,7 +272,8 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
     (``set_adv_train``, ``update_adv_obj``, ``begin_epoch``), ``synthesize`` and ``_camera`` are the base class's code."""
 
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, device, is_train=False, img_ext=".jpg",
-                 seed=1234, num_workers=12, preprocess="reference", color_aug=False, full_res_shape=(ori_H, ori_W), jitter="float"):
+                 seed=1234, num_workers=12, preprocess="reference", color_aug=False, full_res_shape=(ori_H, ori_W), jitter="float",
+                 use_depth_hints=False, depth_hint_path=None):
         if preprocess not in ("reference", "fast"):
             raise RuntimeError("kitti_preprocess must be 'reference' or 'fast'; got %r" % (preprocess,))
         if jitter not in ("float", "pil"):
@@ -231,6 +292,11 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
         self.flip_augmentation = self.is_train       # mono_dataset.py:298
         self.full_res_shape = (int(full_res_shape[0]), int(full_res_shape[1]))      # depth_gt's size (kitti_dataset.py:34)
         self.load_depth = self.check_depth()
+        self.use_depth_hints = bool(use_depth_hints)
+        self.depth_hint_path = depth_hint_path if depth_hint_path is not None else os.path.join(data_path, "depth_hints")
+        if self.use_depth_hints and "s" not in self.frame_idxs:
+            raise RuntimeError("KITTIRAWDataset: depth hints are loaded with the stereo frame (mono_dataset.py:359-368); "
+                               "frame_idxs must hold 's' (--use_stereo)")
         self.views = [0] + (["s"] if "s" in self.frame_idxs else []) + self.neighbour_ids
         self.pool_workers = pool_workers(num_workers)
         self._prefetch = None
@@ -272,7 +338,10 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
         idx = self._next_indices(batch_size)
         # view-major: slot v * batch + i
         paths = [p for v in range(len(self.views)) for p in (self.paths_of(i)[v] for i in idx)]
-        self._prefetch.submit(k, paths, [self.velo_path(i) for i in idx] if self.load_depth else None)
+        hints = None
+        if self.use_depth_hints:
+            hints = [(self.depth_hint_path,) + parse_line(self.filenames[i]) for i in idx]
+        self._prefetch.submit(k, paths, [self.velo_path(i) for i in idx] if self.load_depth else None, hints)
         return idx
 
     def _depth_gt(self, k, idx, sides, flip):
@@ -410,6 +479,9 @@ class KITTIRAWDataset(SyntheticKITTIDataset):
             if any(sd is None for sd in sides):
                 raise RuntimeError("KITTIRAWDataset: depth_gt needs the camera side of every split line")
             inputs["depth_gt"] = self._depth_gt(k, idx, sides, flip)
+        if self.use_depth_hints:
+            # mono_dataset.py:382-388: fliplr, INTER_NEAREST to the training size, the mask; the pasted object never touches it
+            inputs["depth_hint"], inputs["depth_hint_mask"] = ops.depth_hint_prepare(self._prefetch.take_hints(k), flip, (H, W))
         self._prefetch.release(k)
         if pil_jitter:
             # mono_dataset.py:344-348 on the 8-bit level 0: one transform per item, the same for every frame of the item; every
@@ -541,13 +613,11 @@ def from_options(opt, device, rank=0):
     if opt.gt_depth:
         raise NotImplementedError("--gt_depth with --dataset kitti: the pseudo-depth term on depth_gt from velodyne points is "
                                   "not wired to this loader (depth_gt itself is built when the scans exist: load_depth)")
-    if opt.use_depth_hints:
-        raise NotImplementedError("--use_depth_hints with --dataset kitti: precomputed hints are not read from disk")
     lines = read_split(os.path.join(opt.split_dir, opt.split, "train_files.txt"))
     dataset = KITTIRAWDataset(opt.data_path, lines, opt.height, opt.width, opt.frame_ids, 4, device, is_train=True,
                               img_ext=".png" if opt.png else ".jpg", seed=opt.seed + rank, num_workers=opt.num_workers,
                               preprocess=opt.kitti_preprocess, color_aug=opt.contrastive_learning,
-                              jitter=opt.kitti_jitter)
+                              jitter=opt.kitti_jitter, use_depth_hints=opt.use_depth_hints, depth_hint_path=opt.depth_hint_path)
     if opt.adv_train:
         if not opt.scene_root:
             raise RuntimeError("--dataset kitti with --adv_train reads the attack's scenes from --scene_root")

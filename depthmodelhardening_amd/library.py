@@ -35,6 +35,7 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::pil_resample         MD2/datasets/mono_dataset.py:100-104,119-144 (PIL.Image.resize, 8-bit, bit for bit)   (K31, no autograd)
     dmh::velo_depth_map       MD2/kitti_utils.py:46-98 + datasets/kitti_dataset.py:70-85 (generate_depth_map, float32-equal) (K32, no autograd)
     dmh::color_jitter         MD2/datasets/mono_dataset.py:344-348,133,144 (torchvision 0.8.2 ColorJitter on 8-bit PIL images, Pillow's bytes) (K33, no autograd)
+    dmh::depth_hint_fuse      depth-hints/precompute_depth_hints.py:151,247-252 (warp, SSIM + L1, argmin, gather per candidate) (K34, no autograd)
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -747,8 +748,26 @@ def _(images, record, want_u8=False):
     return [t.new_empty(t.shape, dtype=torch.float32) for t in images] + ([t.new_empty(t.shape) for t in images] if want_u8 else [])
 
 
+# ---------------------------------------------------------------------------------------------------------------- K34
+@custom_op("dmh::depth_hint_fuse", mutates_args=())
+def depth_hint_fuse(base: torch.Tensor, lookup: torch.Tensor, cand: torch.Tensor, K: torch.Tensor, inv_K: torch.Tensor, T: torch.Tensor,
+                    want_losses: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(best_depth float32 [B, 1, H, W], losses float32 [B, N, H, W]; an empty tensor without ``want_losses``).  ``cand``: int16
+    [B, N, H, W] (disparity x 16) or float32 depths.  Hints are data: there is no autograd formula."""
+    ops._need_cuda(base)
+    out = ops.depth_hint_fuse(base, lookup, cand, K, inv_K, T, want_losses)
+    return (out[0], out[1]) if want_losses else (out, out.new_empty((0,)))
+
+
+@depth_hint_fuse.register_fake
+def _(base, lookup, cand, K, inv_K, T, want_losses=False):
+    B, _, H, W = base.shape
+    return (base.new_empty((B, 1, H, W), dtype=torch.float32),
+            base.new_empty((B, cand.shape[1], H, W) if want_losses else (0,), dtype=torch.float32))
+
+
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
-       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter")
+       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse")

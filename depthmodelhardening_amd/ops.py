@@ -3651,3 +3651,202 @@ def pil_color_jitter(images, params, want_u8=False):
         N.ptr_array(u8, JITTER_MAX_TENSORS) if want_u8 else None, T, B, H, W, N.ptr(rec), int(with_contrast), N.ptr(ws), N.stream()),
         T * B * H * W * 3 * (1 + 4 + int(want_u8)) + (T * B * H * W * 3 if with_contrast else 0)))
     return [PilLevel(u8[i] if want_u8 else None, f32[i]) for i in range(T)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- K34
+HINT_MAX_CANDIDATES = 16
+HINT_TABLE_CACHE = 8
+_hint_table_cache = OrderedDict()
+
+
+def hint_candidate_depths(cand, K):
+    """depth-hints/precompute_depth_hints.py:142,151 for a batch: StereoSGBM's int16 output [B, N, H, W] (disparity x 16, -16 where
+    nothing matched) -> float32 depths, fx 0.1 / (disp + 1e-7) * (disp > 0) with fx = K[b, 0, 0], as torch computes it on the CPU."""
+    disps = torch.from_numpy(cand.cpu().numpy() / 16).float()
+    fx = K.detach().cpu().float()[:, 0, 0].view(-1, 1, 1, 1)
+    return fx * 0.1 / (disps + 1e-7) * (disps > 0).float()
+
+
+def _hint_check(base, lookup, cand, K, inv_K, T):
+    if not (torch.is_tensor(base) and base.dtype == torch.uint8 and base.dim() == 4 and base.shape[1] == 3):
+        raise RuntimeError("depth_hint_fuse: base must be a uint8 tensor [B, 3, H, W]; got %s %s"
+                           % (getattr(base, "dtype", type(base)), tuple(getattr(base, "shape", ()))))
+    B, _, H, W = (int(v) for v in base.shape)
+    if not (torch.is_tensor(lookup) and lookup.dtype == torch.uint8 and lookup.shape == base.shape):
+        raise RuntimeError("depth_hint_fuse: lookup must be a uint8 tensor of base's shape %s; got %s %s"
+                           % (tuple(base.shape), getattr(lookup, "dtype", type(lookup)), tuple(getattr(lookup, "shape", ()))))
+    if not (torch.is_tensor(cand) and cand.dtype in (torch.int16, torch.float32) and cand.dim() == 4 and cand.shape[0] == B
+            and tuple(cand.shape[2:]) == (H, W)):
+        raise RuntimeError("depth_hint_fuse: cand must be int16 (disparity x 16) or float32 (depths) [%d, N, %d, %d]; got %s %s"
+                           % (B, H, W, getattr(cand, "dtype", type(cand)), tuple(getattr(cand, "shape", ()))))
+    n = int(cand.shape[1])
+    if not 1 <= n <= HINT_MAX_CANDIDATES:
+        raise RuntimeError("depth_hint_fuse: 1 <= N <= %d candidates; got %d" % (HINT_MAX_CANDIDATES, n))
+    if B < 1 or H < 2 or W < 2:
+        raise RuntimeError("depth_hint_fuse: need B >= 1 and H, W >= 2; got %d x %d x %d" % (B, H, W))
+    for name, m in (("K", K), ("inv_K", inv_K), ("T", T)):
+        if not (torch.is_tensor(m) and m.dtype == torch.float32 and tuple(m.shape) == (B, 4, 4)):
+            raise RuntimeError("depth_hint_fuse: %s must be a float32 tensor [%d, 4, 4]; got %s %s"
+                               % (name, B, getattr(m, "dtype", type(m)), tuple(getattr(m, "shape", ()))))
+    for t in (lookup, cand, K, inv_K, T):
+        if t.device != base.device:
+            raise RuntimeError("depth_hint_fuse: every operand must be on base's device %s; got %s" % (base.device, t.device))
+    return B, n, H, W
+
+
+def _hint_ssim(x, y):
+    """depth-hints/layers.py SSIM.forward."""
+    import torch.nn.functional as F
+    x, y = F.pad(x, (1, 1, 1, 1), mode="reflect"), F.pad(y, (1, 1, 1, 1), mode="reflect")
+    mu_x, mu_y = F.avg_pool2d(x, 3, 1), F.avg_pool2d(y, 3, 1)
+    sigma_x = F.avg_pool2d(x ** 2, 3, 1) - mu_x ** 2
+    sigma_y = F.avg_pool2d(y ** 2, 3, 1) - mu_y ** 2
+    sigma_xy = F.avg_pool2d(x * y, 3, 1) - mu_x * mu_y
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    n = (2 * mu_x * mu_y + C1) * (2 * sigma_xy + C2)
+    d = (mu_x ** 2 + mu_y ** 2 + C1) * (sigma_x + sigma_y + C2)
+    return torch.clamp((1 - n / d) / 2, 0, 1)
+
+
+def depth_hint_fuse_host(base, lookup, cand, K, inv_K, T, want_losses=False, dtype=torch.float32):
+    """K34 in plain torch on the CPU, the definition the kernel is held to (and the path CPU tensors take): the lines
+    precompute_depth_hints.py:247-252 with BackprojectDepth, Project3D and SSIM of depth-hints/layers.py, item by item with the
+    candidates as the batch.  The candidate depths are float32 in every form (they are inputs: ``hint_candidate_depths`` for
+    int16); ``dtype=torch.float64`` computes everything after them in float64: the anchor.  Returns best_depth float32
+    [B, 1, H, W], with ``want_losses`` (best_depth, losses ``dtype`` [B, N, H, W])."""
+    import torch.nn.functional as F
+    B, n, H, W = _hint_check(base, lookup, cand, K, inv_K, T)
+    depths = hint_candidate_depths(cand, K) if cand.dtype == torch.int16 else cand.detach().cpu()
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=dtype), torch.arange(W, dtype=dtype), indexing="ij")
+    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W, dtype=dtype)], 0).unsqueeze(0)     # [1, 3, HW]
+    ones = torch.ones(n, 1, H * W, dtype=dtype)
+    best, losses = [], []
+    for b in range(B):
+        Kb, iKb, Tb = (m[b:b + 1].detach().cpu().to(dtype) for m in (K, inv_K, T))
+        d = depths[b].to(dtype)
+        cam = torch.matmul(iKb[:, :3, :3], pix)
+        cam = torch.cat([d.reshape(n, 1, -1) * cam, ones], 1)
+        P = torch.matmul(Kb, Tb)[:, :3, :]
+        cp = torch.matmul(P, cam)
+        pc = cp[:, :2, :] / (cp[:, 2, :].unsqueeze(1) + 1e-7)
+        pc = pc.view(n, 2, H, W).permute(0, 2, 3, 1)
+        pc[..., 0] /= W - 1
+        pc[..., 1] /= H - 1
+        pc = (pc - 0.5) * 2
+        img_l = (lookup[b:b + 1].cpu().to(dtype) / 255).expand(n, -1, -1, -1)
+        img_b = (base[b:b + 1].cpu().to(dtype) / 255).expand(n, -1, -1, -1)
+        sample = F.grid_sample(img_l, pc, padding_mode="border", align_corners=False)
+        l1 = torch.abs(img_b - sample).mean(1, True)
+        loss = 0.85 * _hint_ssim(sample, img_b).mean(1, True) + 0.15 * l1
+        index = torch.argmin(loss, dim=0)
+        best.append(torch.gather(depths[b].unsqueeze(1), 0, index.unsqueeze(0))[0])
+        losses.append(loss[:, 0])
+    best = torch.stack(best).float()
+    return (best, torch.stack(losses)) if want_losses else best
+
+
+def depth_hint_fuse(base, lookup, cand, K, inv_K, T, want_losses=False):
+    """K34: DepthHints' fused hint selection (depth-hints/precompute_depth_hints.py:247-252) for a batch of stereo pairs in one
+    launch: per candidate depth map the other view warped into the base view (grid_sample's defaults, border padding), SSIM + L1
+    against the base image, the lowest loss per pixel (the lowest index among equal float32 losses), its depth.
+
+    base, lookup  uint8 [B, 3, H, W] (``pil_resize(..., want_u8=True).u8``): the view the hint is for, and the other one.
+    cand          int16 [B, N, H, W]: StereoSGBM's raw output (disparity x 16, -16 = no match), converted as the reference does;
+                  or float32 [B, N, H, W]: depths.  1 <= N <= 16.
+    K, inv_K, T   float32 [B, 4, 4]; T[b, 0, 3] = -0.1 for a left base image, +0.1 for a right one.
+    Returns       best_depth float32 [B, 1, H, W]; with ``want_losses`` (best_depth, losses float32 [B, N, H, W]).
+
+    CPU tensors run ``depth_hint_fuse_host``."""
+    B, n, H, W = _hint_check(base, lookup, cand, K, inv_K, T)
+    if base.device.type != "cuda":
+        return depth_hint_fuse_host(base, lookup, cand, K, inv_K, T, want_losses)
+    if B * n * H * W >= 2 ** 31 or B > 65535:
+        raise RuntimeError("depth_hint_fuse: B N H W must stay below 2^31 and B below 65536; got %d x %d x %d x %d" % (B, n, H, W))
+    base, lookup, cand, K, inv_K, T = (_c(t) for t in (base, lookup, cand, K, inv_K, T))
+    best = torch.empty((B, 1, H, W), device=base.device, dtype=torch.float32)
+    losses = torch.empty((B, n, H, W), device=base.device, dtype=torch.float32) if want_losses else None
+    raw = cand.dtype == torch.int16
+    N.check(_timed("depth_hint_fuse", lambda: N.lib().dmh_depth_hint_fuse(
+        N.ptr(base), N.ptr(lookup), C.c_void_p(cand.data_ptr()), int(raw), N.ptr(K), N.ptr(inv_K), N.ptr(T), B, n, H, W, N.ptr(best),
+        N.ptr(losses), N.stream()), B * H * W * (6 + n * (2 if raw else 4) + 4 + (4 * n if want_losses else 0))))
+    return (best, losses) if want_losses else best
+
+
+def cv_nearest_index(n_src, n_dst):
+    """Source index of every destination index of OpenCV's INTER_NEAREST along one axis, as its source states it (resizeNN:
+    min(floor(dst * (double)src / dst_size), src - 1)); the identity when the sizes agree."""
+    scale = float(int(n_src)) / float(int(n_dst))
+    return np.minimum(np.floor(np.arange(int(n_dst), dtype=np.float64) * scale).astype(np.int64), int(n_src) - 1)
+
+
+def _hint_prepare_check(hints, flip, out_size):
+    if not (torch.is_tensor(hints) and hints.dtype == torch.float32 and hints.dim() == 4 and hints.shape[1] == 1 and hints.numel() > 0):
+        raise RuntimeError("depth_hint_prepare: hints must be a non-empty float32 tensor [B, 1, Hs, Ws]; got %s %s"
+                           % (getattr(hints, "dtype", type(hints)), tuple(getattr(hints, "shape", ()))))
+    out_size = tuple(int(v) for v in out_size)
+    if len(out_size) != 2 or out_size[0] < 1 or out_size[1] < 1:
+        raise RuntimeError("depth_hint_prepare: out_size must be a positive (h, w); got %s" % (out_size,))
+    B = int(hints.shape[0])
+    if flip is not None:
+        n = flip.numel() if torch.is_tensor(flip) else len(flip)
+        if n != B:
+            raise RuntimeError("depth_hint_prepare: flip must have one entry per item (%d); got %d" % (B, n))
+    return B, int(hints.shape[2]), int(hints.shape[3]), out_size[0], out_size[1]
+
+
+def depth_hint_prepare_host(hints, flip, out_size):
+    """depth-hints/datasets/mono_dataset.py:382-388 for a batch in numpy: np.fliplr of the flipped items, OpenCV's INTER_NEAREST
+    to ``out_size`` (``cv_nearest_index``), the mask (hint > 0).  Returns (depth_hint, depth_hint_mask) float32 [B, 1, H, W]."""
+    B, Hs, Ws, H, W = _hint_prepare_check(hints, flip, out_size)
+    src = hints.detach().cpu().numpy()
+    flips = [False] * B if flip is None else [bool(v) for v in (flip.tolist() if hasattr(flip, "tolist") else flip)]
+    yi, xi = cv_nearest_index(Hs, H), cv_nearest_index(Ws, W)
+    out = np.empty((B, 1, H, W), dtype=np.float32)
+    for b in range(B):
+        a = np.fliplr(src[b, 0]) if flips[b] else src[b, 0]
+        out[b, 0] = a[yi][:, xi]
+    hint = torch.from_numpy(out)
+    return hint, (hint > 0).float()
+
+
+def _hint_tables_device(device, Hs, Ws, H, W):
+    key = (str(device), Hs, Ws, H, W)
+    hit = _hint_table_cache.get(key)
+    if hit is not None:
+        _hint_table_cache.move_to_end(key)
+        return hit[0], hit[1]
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("depth_hint_prepare: the first call with these sizes uploads their index tables; make it once before "
+                           "capturing a graph")
+    host = [torch.from_numpy(cv_nearest_index(a, b).astype(np.int32)).pin_memory() for a, b in ((Hs, H), (Ws, W))]
+    _hint_table_cache[key] = (host[0].to(device, non_blocking=True), host[1].to(device, non_blocking=True), host)   # pinned copies live on
+    while len(_hint_table_cache) > HINT_TABLE_CACHE:
+        _hint_table_cache.popitem(last=False)
+    return _hint_table_cache[key][:2]
+
+
+def depth_hint_prepare(hints, flip, out_size):
+    """The loader's side of a stored depth hint (depth-hints/datasets/mono_dataset.py:382-388) for a batch in one launch.
+
+    hints     float32 [B, 1, Hs, Ws]: the loaded ``.npy`` files.
+    flip      None, an int32 tensor [B] on the hints' device, or a host sequence of bools: != 0 is np.fliplr before the resize.
+    out_size  (H, W): cv2.resize(..., INTER_NEAREST) to it; at Hs, Ws == H, W a (mirrored) copy.
+    Returns   (depth_hint, depth_hint_mask = (depth_hint > 0).float()), float32 [B, 1, H, W].
+
+    CPU tensors run ``depth_hint_prepare_host``."""
+    B, Hs, Ws, H, W = _hint_prepare_check(hints, flip, out_size)
+    dev = hints.device
+    if dev.type != "cuda":
+        return depth_hint_prepare_host(hints, flip, out_size)
+    if flip is not None and not torch.is_tensor(flip):
+        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    if flip is not None and (flip.dtype != torch.int32 or flip.device != dev):
+        raise RuntimeError("depth_hint_prepare: flip must be an int32 tensor of %d entries on %s" % (B, dev))
+    ytab, xtab = _hint_tables_device(dev, Hs, Ws, H, W)
+    hints = _c(hints)
+    hint = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    mask = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    N.check(_timed("depth_hint_prepare", lambda: N.lib().dmh_depth_hint_prepare(
+        N.ptr(hints), N.ptr(None if flip is None else _c(flip)), N.ptr(ytab), N.ptr(xtab), H, W, B, Hs, Ws, H, W, N.ptr(hint),
+        N.ptr(mask), N.stream()), B * H * W * 12))
+    return hint, mask

@@ -119,7 +119,11 @@ class MonodepthOptions:
                        help="generate_images_pred also writes depth/sample/color tensors (the fused loss never reads them)")
         p.add_argument("--use_depth_hints", action="store_true",
                        help="DepthHints (DH/options.py:99-101): depth-hint reprojection candidate + proxy supervision; needs "
-                            "--loss_variant dh.  The synthetic dataset makes up hints (smooth depth with holes)")
+                            "--loss_variant dh.  The synthetic dataset makes up hints (smooth depth with holes); --dataset kitti "
+                            "reads them from --depth_hint_path (made by precompute_depth_hints.py)")
+        p.add_argument("--depth_hint_path", type=str, default=None,
+                       help="DepthHints (DH/options.py:102-106): the tree of precomputed hints, "
+                            "<path>/<sequence>/image_0{2,3}/<frame:010d>.npy; default <data_path>/depth_hints")
         p.add_argument("--reference_stale_patch", action="store_true",
                        help="paste the adversarial patch as of the epoch start, as the reference's forked DataLoader workers "
                             "do (SURVEY.md section 3.1); default: the freshly attacked patch (its num_workers=0 behaviour)")
@@ -147,4 +151,6 @@ class MonodepthOptions:
 
     def parse(self, args=None):
         self.options = self.parser.parse_args(args)
+        if self.options.depth_hint_path is None:        # DH/trainer.py: the hints live beside the data unless told otherwise
+            self.options.depth_hint_path = os.path.join(self.options.data_path, "depth_hints")
         return self.options

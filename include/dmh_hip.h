@@ -911,6 +911,33 @@ int64_t dmh_color_jitter_ws_size(int T, int B, int H, int W);
 int dmh_color_jitter(const uint8_t* const* src, float* const* out_f32, uint8_t* const* out_u8, int T, int B, int H, int W,
                      const int32_t* rec, int with_contrast, uint32_t* ws, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K34 DepthHints' fused hint selection (depth-hints/precompute_depth_hints.py:151,247-252) for a batch of B stereo pairs, and the
+ *     loader's side of a stored hint (depth-hints/datasets/mono_dataset.py:382-388).
+ *     base, lookup: uint8 [B][3][H][W] (planar; K31's byte output); a value is (float)byte / 255.f.
+ *     cand: cand_is_raw = 1: int16 [B][N][H][W], StereoSGBM's output (disparity x 16, -16 = no match),
+ *           depth = fx 0.1f / (raw / 16 + 1e-7f) * (raw / 16 > 0), fx = K[b][0][0], float32 operations in that order, IEEE division;
+ *           cand_is_raw = 0: float32 [B][N][H][W], the depths.  1 <= N <= DMH_HINT_MAX_CANDIDATES.
+ *     K, inv_K, T: float32 [B][4][4].  Per candidate and pixel: BackprojectDepth and Project3D of depth-hints/layers.py
+ *     (eps 1e-7, normalised by W - 1 and H - 1), F.grid_sample's defaults with padding_mode='border' (bilinear,
+ *     align_corners=False; the coordinate is clamped to [0, size - 1] before it becomes an integer), SSIM over 3 x 3 windows with
+ *     reflection padding 1 on both images, loss = 0.85 mean_c SSIM + 0.15 mean_c |base - sample|.
+ *     best_depth: float32 [B][1][H][W], the depth of the candidate with the lowest loss, the lowest index among equal losses.
+ *     losses: NULL, or float32 [B][N][H][W] that receives every loss (tests, diagnosis).
+ *     H, W >= 2; B N H W < 2^31.  One launch, no atomics, no workspace, no host read: bitwise reproducible.
+ *
+ *     dmh_depth_hint_prepare: src float32 [B][Hs][Ws] -> hint, mask float32 [B][H][W]: np.fliplr where flip[b] != 0 (int32 [B],
+ *     may be NULL), then nearest resize through the index tables ytab int32 [H] and xtab int32 [W] (device memory, entries in
+ *     [0, Hs - 1] and [0, Ws - 1]; an entry outside is clamped): hint(y, x) = src(ytab[y], flip ? Ws - 1 - xtab[x] : xtab[x]),
+ *     mask = hint > 0 as 0 / 1 (a -0.0 is not > 0).  ytab_len, xtab_len: the tables' lengths, which must be H and W.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_HINT_MAX_CANDIDATES 16
+int dmh_depth_hint_fuse(const uint8_t* base, const uint8_t* lookup, const void* cand, int cand_is_raw, const float* K,
+                        const float* inv_K, const float* T, int B, int N, int H, int W, float* best_depth, float* losses,
+                        void* stream);
+int dmh_depth_hint_prepare(const float* src, const int32_t* flip, const int32_t* ytab, const int32_t* xtab, int64_t ytab_len,
+                           int64_t xtab_len, int B, int Hs, int Ws, int H, int W, float* hint, float* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
