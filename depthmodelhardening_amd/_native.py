@@ -14,6 +14,7 @@ MAX_FRAMES = 4
 VARIANT_MD2, VARIANT_DH = 0, 1
 NOISE_NONE, NOISE_TENSOR, NOISE_PHILOX = 0, 1, 2
 PASTE_COMPOSITE, PASTE_WARP_ONLY = 0, 1
+SGM_COST, SGM_PATHS, SGM_SELECT, SGM_SPECKLE, SGM_ALL = 1, 2, 4, 8, 15       # DMH_SGM_*: the phases of K35
 PIL_LANCZOS, PIL_BILINEAR, PIL_TILE_ROWS = 1, 2, 8      # PIL.Image.LANCZOS / BILINEAR; DMH_PIL_TILE_ROWS
 FIN_LOSS, FIN_LOSS_S, FIN_REPROJ_S, FIN_COUNT_S, FIN_SMOOTH_S, FIN_HINT_S, FIN_HINTCOUNT_S, FIN_SIZE = 0, 1, 5, 9, 13, 20, 24, 28
 
@@ -53,6 +54,11 @@ class RoiGlueArgs(C.Structure):
 
 class WinoWtJob(C.Structure):
     _fields_ = [("w", _fp), ("scale", _fp), ("U", _fp), ("K", C.c_int), ("C", C.c_int), ("backward", C.c_int)]
+
+
+class SgmParams(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("num_disparities", "block_size", "P1", "P2", "pre_filter_cap", "uniqueness_ratio",
+                                         "disp12_max_diff", "speckle_window_size", "speckle_range", "min_disparity")]
 
 
 _PtrArr = _fp * MAX_SCALES
@@ -196,6 +202,8 @@ _SIGNATURES = {
     "dmh_color_jitter": (C.c_int, [C.POINTER(_fp)] * 3 + [C.c_int] * 4 + [_fp, C.c_int, _fp, _fp]),
     "dmh_depth_hint_fuse": (C.c_int, [_fp] * 3 + [C.c_int] + [_fp] * 3 + [C.c_int] * 4 + [_fp] * 3),
     "dmh_depth_hint_prepare": (C.c_int, [_fp] * 4 + [C.c_int64] * 2 + [C.c_int] * 5 + [_fp] * 3),
+    "dmh_sgm_plan": (C.c_int64, [C.c_int] * 3 + [C.POINTER(SgmParams), C.c_int, C.c_int64, C.POINTER(C.c_int)]),
+    "dmh_sgm_disparity": (C.c_int, [_fp] * 3 + [C.c_int] * 3 + [C.POINTER(SgmParams), C.c_int, _fp, _fp, C.c_int64, C.c_int, _fp]),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -36,6 +36,8 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::velo_depth_map       MD2/kitti_utils.py:46-98 + datasets/kitti_dataset.py:70-85 (generate_depth_map, float32-equal) (K32, no autograd)
     dmh::color_jitter         MD2/datasets/mono_dataset.py:344-348,133,144 (torchvision 0.8.2 ColorJitter on 8-bit PIL images, Pillow's bytes) (K33, no autograd)
     dmh::depth_hint_fuse      depth-hints/precompute_depth_hints.py:151,247-252 (warp, SSIM + L1, argmin, gather per candidate) (K34, no autograd)
+    dmh::sgm_disparity        the stereo matchers of depth-hints/precompute_depth_hints.py:42-63,128-147 as this package's own integer
+                              semi-global matcher (not OpenCV's output)   (K35, no autograd)
 """
 import ctypes as C
 from typing import List, Optional, Tuple
@@ -766,8 +768,36 @@ def _(base, lookup, cand, K, inv_K, T, want_losses=False):
             base.new_empty((B, cand.shape[1], H, W) if want_losses else (0,), dtype=torch.float32))
 
 
+# ---------------------------------------------------------------------------------------------------------------- K35
+@custom_op("dmh::sgm_disparity", mutates_args=())
+def sgm_disparity(base: torch.Tensor, lookup: torch.Tensor, params: List[int], reverse: Optional[torch.Tensor] = None,
+                  workspace_cap: int = ops.SGM_WORKSPACE_CAP) -> torch.Tensor:
+    """int16 [B, N, H, W], disparity x 16, -16 = no match.  ``params``: the N parameter sets flattened, ten integers each in the order
+    of ``ops._SGM_KEYS`` (``sgm_params_flat`` makes them from the dicts).  Disparities are data: there is no autograd formula."""
+    ops._need_cuda(base)
+    return ops.sgm_disparity(base, lookup, sgm_params_unflat(params), reverse, workspace_cap)
+
+
+@sgm_disparity.register_fake
+def _(base, lookup, params, reverse=None, workspace_cap=ops.SGM_WORKSPACE_CAP):
+    B, _, H, W = base.shape
+    return base.new_empty((B, len(params) // len(ops._SGM_KEYS), H, W), dtype=torch.int16)
+
+
+def sgm_params_flat(params):
+    """A list of parameter dicts as the flat integer list ``torch.ops.dmh.sgm_disparity`` takes."""
+    return [int(v) for t in ops._sgm_params(params) for v in t]
+
+
+def sgm_params_unflat(flat):
+    k = len(ops._SGM_KEYS)
+    if len(flat) == 0 or len(flat) % k != 0:
+        raise RuntimeError("sgm_disparity: params must hold %d integers per parameter set; got %d" % (k, len(flat)))
+    return [dict(zip(ops._SGM_KEYS, flat[i:i + k])) for i in range(0, len(flat), k)]
+
+
 OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt_depth_mse", "gt_depth_mse_bwd", "pgd_linf_step", "l0_compose", "l0_compose_bwd",
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
-       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse")
+       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity")

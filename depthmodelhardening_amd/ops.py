@@ -3850,3 +3850,268 @@ def depth_hint_prepare(hints, flip, out_size):
         N.ptr(hints), N.ptr(None if flip is None else _c(flip)), N.ptr(ytab), N.ptr(xtab), H, W, B, Hs, Ws, H, W, N.ptr(hint),
         N.ptr(mask), N.stream()), B * H * W * 12))
     return hint, mask
+
+
+# ---------------------------------------------------------------------------------------------------------------- K35
+SGM_MAX_MATCHERS = 16
+SGM_MAX_WIDTH = 4096
+SGM_WORKSPACE_CAP = 2 << 30
+SGM_PC_MAX = 567                    # 3 channels x (126 prefiltered + 255 >> 2 raw): the largest pixel cost
+_SGM_KEYS = ("numDisparities", "blockSize", "P1", "P2", "preFilterCap", "uniquenessRatio", "disp12MaxDiff", "speckleWindowSize",
+             "speckleRange", "minDisparity")
+_SGM_DEFAULTS = dict(disp12MaxDiff=0, minDisparity=0)
+
+
+def _sgm_params(params):
+    """The parameter sets as tuples in ``_SGM_KEYS`` order, each refused where the matcher does not serve it."""
+    if isinstance(params, dict):
+        params = [params]
+    params = list(params)
+    if not 1 <= len(params) <= SGM_MAX_MATCHERS:
+        raise RuntimeError("sgm_disparity: 1 <= N <= %d parameter sets; got %d" % (SGM_MAX_MATCHERS, len(params)))
+    out = []
+    for p in params:
+        unknown = set(p) - set(_SGM_KEYS)
+        if unknown:
+            raise RuntimeError("sgm_disparity: unknown parameter(s) %s; the keys are %s" % (sorted(unknown), list(_SGM_KEYS)))
+        missing = [k for k in _SGM_KEYS if k not in p and k not in _SGM_DEFAULTS]
+        if missing:
+            raise RuntimeError("sgm_disparity: a parameter set lacks %s" % missing)
+        D, b, P1, P2, cap, uniq, d12, spw, spr, mind = t = tuple(int(p.get(k, _SGM_DEFAULTS.get(k, 0))) for k in _SGM_KEYS)
+        if mind != 0:
+            raise RuntimeError("sgm_disparity: minDisparity must be 0; got %d" % mind)
+        if D % 16 != 0 or not 16 <= D <= 256:
+            raise RuntimeError("sgm_disparity: numDisparities must be a multiple of 16 in [16, 256]; got %d" % D)
+        if not 1 <= b <= 3:
+            raise RuntimeError("sgm_disparity: blockSize must be 1, 2 or 3 (radius <= 1, for which int16 sums are exact); got %d" % b)
+        side = 2 * (b // 2) + 1
+        if P1 < 0 or P2 < 0 or 5 * (side * side * SGM_PC_MAX + P2) >= 32767:
+            raise RuntimeError("sgm_disparity: P1, P2 >= 0 and 5 ((2r+1)^2 %d + P2) < 32767 (int16 sums); got P1 %d, P2 %d at "
+                               "blockSize %d" % (SGM_PC_MAX, P1, P2, b))
+        if not 1 <= cap <= 63 or not 0 <= uniq <= 100 or not 0 <= d12 <= 32767 or spw < 0 or not 0 <= spr <= 4096:
+            raise RuntimeError("sgm_disparity: need preFilterCap in [1, 63], uniquenessRatio in [0, 100], disp12MaxDiff in [0, 32767], "
+                               "speckleWindowSize >= 0 and speckleRange in [0, 4096]; got %s" % (dict(zip(_SGM_KEYS, t)),))
+        out.append(t)
+    return out
+
+
+def _sgm_check(base, lookup, params, reverse):
+    if not (torch.is_tensor(base) and base.dtype == torch.uint8 and base.dim() == 4 and base.shape[1] == 3 and base.numel() > 0):
+        raise RuntimeError("sgm_disparity: base must be a non-empty uint8 tensor [B, 3, H, W]; got %s %s"
+                           % (getattr(base, "dtype", type(base)), tuple(getattr(base, "shape", ()))))
+    if not (torch.is_tensor(lookup) and lookup.dtype == torch.uint8 and lookup.shape == base.shape and lookup.device == base.device):
+        raise RuntimeError("sgm_disparity: lookup must be a uint8 tensor of base's shape %s on its device; got %s %s"
+                           % (tuple(base.shape), getattr(lookup, "dtype", type(lookup)), tuple(getattr(lookup, "shape", ()))))
+    B, _, H, W = (int(v) for v in base.shape)
+    plist = _sgm_params(params)
+    if W > SGM_MAX_WIDTH or H > 65535 or B * len(plist) * H * W >= 2 ** 31:
+        raise RuntimeError("sgm_disparity: need W <= %d, H <= 65535 and B N H W < 2^31; got %d x %d x %d x %d"
+                           % (SGM_MAX_WIDTH, B, len(plist), H, W))
+    if reverse is not None:
+        n = reverse.numel() if torch.is_tensor(reverse) else len(reverse)
+        if n != B:
+            raise RuntimeError("sgm_disparity: reverse must have one entry per item (%d); got %d" % (B, n))
+    return B, H, W, plist
+
+
+def _sgm_lo_hi(A):
+    left = np.concatenate([A[..., :1], A[..., :-1]], -1)
+    right = np.concatenate([A[..., 1:], A[..., -1:]], -1)
+    hl, hr = (A + left) >> 1, (A + right) >> 1
+    return np.minimum(A, np.minimum(hl, hr)), np.maximum(A, np.maximum(hl, hr))
+
+
+def _sgm_block_cost(base, lookup, D, r, cap):
+    """Steps 1-3 for one pair: C int32 [H, Wv, D]."""
+    _, H, W = base.shape
+    kinds = []
+    for img in (base.astype(np.int32), lookup.astype(np.int32)):
+        rows = np.pad(img, ((0, 0), (1, 1), (0, 0)), mode="edge")
+        dx = rows[:, :, 2:] - rows[:, :, :-2]                           # [3, H + 2, W - 2]
+        g = np.full(img.shape, cap, dtype=np.int32)
+        g[:, :, 1:W - 1] = np.clip(dx[:, :-2] + 2 * dx[:, 1:-1] + dx[:, 2:], -cap, cap) + cap
+        A = np.concatenate([g, img], 0)                                 # [6, H, W]
+        kinds.append((A,) + _sgm_lo_hi(A))
+    (u, lo_u, hi_u), (v, lo_v, hi_v) = kinds
+    cols = np.arange(D, W)[:, None] - np.arange(D)[None, :]             # [Wv, D]: the lookup column of (x, d)
+    pc = np.zeros((H, W - D, D), dtype=np.int32)
+    for k in range(6):                                                  # g of the three channels, then their bytes
+        a, lo_a, hi_a = (t[k][:, D:, None] for t in (u, lo_u, hi_u))
+        b, lo_b, hi_b = (t[k][:, cols] for t in (v, lo_v, hi_v))
+        bt = np.minimum(np.maximum(0, np.maximum(a - hi_b, lo_b - a)), np.maximum(0, np.maximum(b - hi_a, lo_a - b)))
+        pc += bt if k < 3 else bt >> 2
+    if r == 0:
+        return pc
+    pad = np.pad(pc, ((r, r), (r, r), (0, 0)), mode="edge")
+    Wv = W - D
+    return sum(pad[dy:dy + H, dx:dx + Wv] for dy in range(2 * r + 1) for dx in range(2 * r + 1))
+
+
+def _sgm_step(C, q, P1, P2):
+    """One step of a path for a whole front: C, q [..., D] -> L."""
+    big = np.int32(1 << 28)
+    m = q.min(-1, keepdims=True)
+    down = np.concatenate([np.full_like(q[..., :1], big), q[..., :-1]], -1)
+    up = np.concatenate([q[..., 1:], np.full_like(q[..., :1], big)], -1)
+    return C + np.minimum(np.minimum(q, np.minimum(down, up) + P1), m + P2) - m
+
+
+def _sgm_aggregate(C, P1, P2):
+    H, Wv, D = C.shape
+    S = np.zeros_like(C)
+    for cols in (range(Wv), range(Wv - 1, -1, -1)):                     # from the left, from the right: all rows at once
+        L = None
+        for x in cols:
+            L = C[:, x] if L is None else _sgm_step(C[:, x], L, P1, P2)
+            S[:, x] += L
+    for dx in (-1, 0, 1):                                               # from above: all columns at once
+        L = C[0]
+        S[0] += L
+        for y in range(1, H):
+            q = L if dx == 0 else np.roll(L, -dx, axis=0)               # q[x] = L[x + dx]
+            new = _sgm_step(C[y], q, P1, P2)
+            if dx == -1:
+                new[0] = C[y, 0]
+            elif dx == 1:
+                new[Wv - 1] = C[y, Wv - 1]
+            L = new
+            S[y] += L
+    return S
+
+
+def _sgm_select(S, W, uniq, d12):
+    """Steps 5 and 6: S [H, Wv, D] -> int32 [H, W]."""
+    H, Wv, D = S.shape
+    out = np.full((H, W), -16, dtype=np.int32)
+    d_star = S.argmin(-1)
+    min_s = np.take_along_axis(S, d_star[..., None], -1)[..., 0]
+    far = np.abs(np.arange(D)[None, None, :] - d_star[..., None]) > 1
+    unique = ~((S * (100 - uniq) < 100 * min_s[..., None]) & far).any(-1)
+    sm = np.take_along_axis(S, np.maximum(d_star - 1, 0)[..., None], -1)[..., 0]
+    sp = np.take_along_axis(S, np.minimum(d_star + 1, D - 1)[..., None], -1)[..., 0]
+    den = np.maximum(sm + sp - 2 * min_s, 1)
+    num = (sm - sp) * 16 + den
+    frac = np.sign(num) * (np.abs(num) // (2 * den))                    # C's division
+    value = 16 * d_star + np.where((d_star == 0) | (d_star == D - 1), 0, frac)
+    out[:, D:] = np.where(unique, value, -16)
+    xs = np.broadcast_to(np.arange(D, W)[None, :], (H, Wv))
+    ys = np.broadcast_to(np.arange(H)[:, None], (H, Wv))
+    none = np.int64(1) << 40
+    keys = np.full((H, W), none, dtype=np.int64)
+    np.minimum.at(keys, (ys[unique], (xs - d_star)[unique]), (min_s.astype(np.int64)[unique] << 16) | xs[unique])
+    owner = np.where(keys == none, D, keys & 0xffff).astype(np.int64)   # the proposer's column (D where nobody proposed)
+    disp2 = np.take_along_axis(d_star, owner - D, 1)
+    is_set = keys != none
+    xa = np.broadcast_to(np.arange(W)[None, :], (H, W))
+    bad = np.zeros((H, W), dtype=np.int32)
+    for k in (0, 15):
+        dd = (out + k) >> 4
+        x2 = xa - dd
+        inside = (x2 >= 0) & (x2 < W)
+        x2c = np.clip(x2, 0, W - 1)
+        hit = inside & np.take_along_axis(is_set, x2c, 1) & (np.abs(np.take_along_axis(disp2, x2c, 1) - dd) > d12)
+        bad += hit
+    out[(out >= 0) & (bad == 2)] = -16
+    return out
+
+
+def _sgm_speckle(disp, window, rng16):
+    """Step 7 by label propagation with pointer jumping; components do not depend on the order."""
+    H, W = disp.shape
+    valid = disp >= 0
+    lab = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    right = valid[:, :-1] & valid[:, 1:] & (np.abs(disp[:, :-1] - disp[:, 1:]) <= rng16)
+    down = valid[:-1] & valid[1:] & (np.abs(disp[:-1] - disp[1:]) <= rng16)
+    while True:
+        new = lab.copy()
+        np.minimum(new[:, :-1], np.where(right, lab[:, 1:], new[:, :-1]), out=new[:, :-1])
+        np.minimum(new[:, 1:], np.where(right, lab[:, :-1], new[:, 1:]), out=new[:, 1:])
+        np.minimum(new[:-1], np.where(down, lab[1:], new[:-1]), out=new[:-1])
+        np.minimum(new[1:], np.where(down, lab[:-1], new[1:]), out=new[1:])
+        flat = new.reshape(-1)
+        for _ in range(4):
+            flat = flat[flat]
+        new = flat.reshape(H, W)
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    sizes = np.bincount(lab[valid], minlength=H * W)
+    out = disp.copy()
+    out[valid & (sizes[lab] <= window)] = -16
+    return out
+
+
+def sgm_disparity_host(base, lookup, params, reverse=None):
+    """K35 in whole-image numpy on the CPU (the path CPU tensors take), bit-equal to the pixel-by-pixel statement of the matcher
+    in tests/sgm_ref.py.  Returns int16 [B, N, H, W]."""
+    B, H, W, plist = _sgm_check(base, lookup, params, reverse)
+    flips = [False] * B if reverse is None else [bool(v) for v in (reverse.tolist() if hasattr(reverse, "tolist") else reverse)]
+    b_np, l_np = base.detach().cpu().numpy(), lookup.detach().cpu().numpy()
+    out = np.full((B, len(plist), H, W), -16, dtype=np.int16)
+    for b in range(B):
+        ib, il = (a[b, :, :, ::-1] if flips[b] else a[b] for a in (b_np, l_np))
+        done = {}
+        for n, (D, blk, P1, P2, cap, uniq, d12, spw, spr, _) in enumerate(plist):
+            key = (D, blk // 2, P1, P2, cap, uniq, d12, spw, spr)
+            if key not in done:
+                disp = np.full((H, W), -16, dtype=np.int32)
+                if W > D:
+                    S = _sgm_aggregate(_sgm_block_cost(ib, il, D, blk // 2, cap), P1, P2)
+                    disp = _sgm_select(S, W, uniq, d12)
+                if spw > 0:
+                    disp = _sgm_speckle(disp, spw, 16 * spr)
+                done[key] = disp[:, ::-1] if flips[b] else disp
+            out[b, n] = done[key]
+    return torch.from_numpy(out)
+
+
+def _sgm_native_params(plist):
+    arr = (N.SgmParams * len(plist))()
+    for i, (D, blk, P1, P2, cap, uniq, d12, spw, spr, mind) in enumerate(plist):
+        arr[i] = N.SgmParams(D, blk, P1, P2, cap, uniq, d12, spw, spr, mind)
+    return arr
+
+
+def sgm_plan(B, H, W, params, workspace_cap=SGM_WORKSPACE_CAP):
+    """(workspace bytes, sequences of launches) of ``sgm_disparity`` for a batch under ``workspace_cap`` bytes; host only."""
+    plist = _sgm_params(params)
+    chunks = C.c_int(0)
+    nbytes = N.lib().dmh_sgm_plan(int(B), int(H), int(W), _sgm_native_params(plist), len(plist), int(workspace_cap), C.byref(chunks))
+    if nbytes < 0:
+        raise RuntimeError("libdmh_hip: " + N.lib().dmh_last_error().decode())
+    return int(nbytes), int(chunks.value)
+
+
+def sgm_disparity(base, lookup, params, reverse=None, workspace_cap=SGM_WORKSPACE_CAP, phases=N.SGM_ALL):
+    """K35: the integer semi-global stereo matcher of DESIGN.md section 3 (K35) for a batch of stereo pairs on the device; every
+    parameter set of ``params`` gives one map.
+
+    base, lookup   uint8 [B, 3, H, W] (``pil_resize(..., want_u8=True).u8``): the view the disparity is for, and the other one.
+    params         a list of at most 16 dicts with the keys of ``precompute_depth_hints.stereo_matcher_params()`` (and optionally
+                   ``disp12MaxDiff``, 0 by default).  numDisparities a multiple of 16 in [16, 256], blockSize <= 3, minDisparity 0.
+    reverse        None, an int32 tensor [B] on base's device, or a host sequence of bools: != 0 where the base image is the right
+                   view (the pair is matched mirrored and the result mirrored back).
+    workspace_cap  bytes the workspace may take (2 GiB by default); the batch is split into sequences of launches that fit.
+    phases         ``N.SGM_ALL``; a subset launches only those phases, for tools/sgm_bench.py (the result is then undefined).
+    Returns        int16 [B, N, H, W]: disparity x 16, -16 where nothing matched -- what ``depth_hint_fuse`` takes.
+
+    CPU tensors run ``sgm_disparity_host``."""
+    B, H, W, plist = _sgm_check(base, lookup, params, reverse)
+    dev = base.device
+    if dev.type != "cuda":
+        return sgm_disparity_host(base, lookup, params, reverse)
+    if reverse is not None and not torch.is_tensor(reverse):
+        reverse = torch.tensor([int(bool(v)) for v in reverse], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    if reverse is not None and (reverse.dtype != torch.int32 or reverse.device != dev):
+        raise RuntimeError("sgm_disparity: reverse must be an int32 tensor of %d entries on %s" % (B, dev))
+    native = _sgm_native_params(plist)
+    nbytes = N.lib().dmh_sgm_plan(B, H, W, native, len(plist), int(workspace_cap), None)
+    if nbytes < 0:
+        raise RuntimeError("libdmh_hip: " + N.lib().dmh_last_error().decode())
+    base, lookup = _c(base), _c(lookup)
+    out = torch.empty((B, len(plist), H, W), device=dev, dtype=torch.int16)
+    ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
+    N.check(_timed("sgm_disparity", lambda: N.lib().dmh_sgm_disparity(
+        N.ptr(base), N.ptr(lookup), N.ptr(None if reverse is None else _c(reverse)), B, H, W, native, len(plist),
+        C.c_void_p(out.data_ptr()), N.ptr(ws), int(nbytes), int(phases), N.stream()), B * H * W * (6 + 2 * len(plist))))
+    return out

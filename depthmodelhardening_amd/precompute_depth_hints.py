@@ -1,20 +1,31 @@
-"""Precompute depth hints by the 'fused SGM' method: depth-hints/precompute_depth_hints.py with its device half as one launch (K34).
+"""Precompute depth hints by the 'fused SGM' method: depth-hints/precompute_depth_hints.py with its device half as one launch (K34)
+and, with ``--matcher device``, its stereo matchers on the device too (K35).
 
     python -m depthmodelhardening_amd.precompute_depth_hints --data_path DIR --filenames LIST [--save_path DIR]
-        [--height 320] [--width 1024] [--overwrite_saved_depths] [--candidates_dir DIR] [--batch_size 8] [--num_workers 12]
+        [--height 320] [--width 1024] [--overwrite_saved_depths] [--matcher auto|opencv|device|files] [--candidates_dir DIR]
+        [--save_candidates DIR] [--batch_size 8] [--num_workers 12]
 
 For every line "sequence frame side" of the list: both views are decoded by the KITTI loader's pool (at most 16 threads) and
 resized by ``ops.pil_resize(..., "lanczos", want_u8=True)`` (the reference's ANTIALIAS is LANCZOS); twelve candidate disparity
-maps come from the matchers of ``generate_stereo_matchers`` (blockSize 1 / 2 / 3 x numDisparities 64 / 96 / 128 / 160) on the host
-through OpenCV **if cv2 can be imported**, with the reference's left-right reversal for a right base image -- or, without OpenCV
-(or whenever the option is given: it says where the candidates are), from ``--candidates_dir``, one int16 [N, H, W] ``.npy`` per
-line laid out as the output is (StereoSGBM's raw output, disparity x 16); without either source the tool stops and says so; ``ops.depth_hint_fuse`` picks the candidate with the lowest reprojection loss per pixel, a batch of pairs per launch; the
-result is saved as ``save_path/<sequence>/image_0{2,3}/<frame:010d>.npy``, float32 [1, H, W].  Files that exist are skipped unless
+maps come from the matchers of ``generate_stereo_matchers`` (blockSize 1 / 2 / 3 x numDisparities 64 / 96 / 128 / 160);
+``ops.depth_hint_fuse`` picks the candidate with the lowest reprojection loss per pixel, a batch of pairs per launch; the result is
+saved as ``save_path/<sequence>/image_0{2,3}/<frame:010d>.npy``, float32 [1, H, W].  Files that exist are skipped unless
 ``--overwrite_saved_depths``.  The files of a batch are written after the next batch has been enqueued, so the device never waits
 for the disk.
 
-With OpenCV the whole stage is bound by the host matchers (twelve SGBM runs per pair); the fused kernel removes the device half's
-~60 launches and ~1 GB of traffic per image, not that.  A device SGBM is not part of this package.
+Where the candidates come from (``--matcher``):
+
+    device   ``ops.sgm_disparity`` (K35) on the resized bytes already on the device, with the same twelve parameter sets and the
+             reference's left-right reversal for a right base image as a per-item flag; the int16 tensor goes straight into the
+             fusion, and nothing comes back to the host before the hints do.  PNG files in, hints out, with this package alone.
+             K35 is this package's own matcher, modelled on StereoSGBM's structure; its maps are not OpenCV's.
+             With ``--device cpu`` its host twin runs.
+    opencv   OpenCV's StereoSGBM on host threads (the resized bytes come back for it): bound by twelve SGBM runs per pair.
+    files    ``--candidates_dir``: one int16 [N, H, W] ``.npy`` per line laid out as the output is (disparity x 16, -16 = no match).
+    auto     (default) opencv **if cv2 can be imported** and no ``--candidates_dir`` is given, files if it is given; without either
+             the tool stops and says so.
+
+``--save_candidates DIR`` also writes the candidates of every line in the ``--candidates_dir`` layout.
 """
 import argparse
 import os
@@ -91,14 +102,22 @@ def run(opt):
     print("Saving depth hints to {}".format(opt.save_path))
     device = torch.device(opt.device)
     H, W = int(opt.height), int(opt.width)
-    cv2 = import_cv2()
-    if cv2 is None and not opt.candidates_dir:
-        raise RuntimeError("precompute_depth_hints: no source of candidate disparities: OpenCV (cv2) cannot be imported for the "
-                           "stereo matchers, and no --candidates_dir with precomputed int16 [N, H, W] .npy files was given")
+    mode = getattr(opt, "matcher", "auto")
+    cv2 = import_cv2() if mode in ("auto", "opencv") else None
+    if mode == "auto":
+        if cv2 is None and not opt.candidates_dir:
+            raise RuntimeError("precompute_depth_hints: no source of candidate disparities: OpenCV (cv2) cannot be imported for the "
+                               "stereo matchers, and no --candidates_dir with precomputed int16 [N, H, W] .npy files was given")
+        mode = "files" if opt.candidates_dir else "opencv"
+    if mode == "opencv" and cv2 is None:
+        raise RuntimeError("precompute_depth_hints: --matcher opencv, but OpenCV (cv2) cannot be imported")
+    if mode == "files" and not opt.candidates_dir:
+        raise RuntimeError("precompute_depth_hints: --matcher files needs --candidates_dir")
     matchers = None
-    if cv2 is not None and not opt.candidates_dir:
+    if mode == "opencv":
         cv2.setNumThreads(0)
         matchers = generate_stereo_matchers(cv2)
+    save_candidates = getattr(opt, "save_candidates", None)
     lines = [tuple(ln.split()) for ln in kitti.read_split(opt.filenames) if ln.strip()]
     todo = [ln for ln in lines if opt.overwrite_saved_depths or not os.path.isfile(output_path(opt.save_path, *ln))]
     batch = max(1, int(opt.batch_size))
@@ -114,6 +133,9 @@ def run(opt):
         return [one(s, f, sd) for s, f, sd in chunk] + [one(s, f, "r" if sd == "l" else "l") for s, f, sd in chunk]
 
     def candidates(chunk, base_u8, lookup_u8):
+        if mode == "device":
+            # K35: from the bytes on the device to the fusion on the device (the flags go up through pinned memory)
+            return ops.sgm_disparity(base_u8, lookup_u8, stereo_matcher_params(), reverse=[ln[2] != "l" for ln in chunk])
         if matchers is None:
             arrs = list(pool.map(lambda ln: np.load(output_path(opt.candidates_dir, *ln)), chunk))
         else:
@@ -128,13 +150,14 @@ def run(opt):
 
     def flush(pending):
         """write the files of a batch whose result has reached the host"""
-        chunk, host, event = pending
+        chunk, host, event, cand_host = pending
         if event is not None:
             event.synchronize()
-        for ln, depth in zip(chunk, host.numpy()):
-            path = output_path(opt.save_path, *ln)
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-            np.save(path, depth)
+        for i, (ln, depth) in enumerate(zip(chunk, host.numpy())):
+            for root, array in ((opt.save_path, depth),) + (((save_candidates, cand_host[i].numpy()),) if cand_host is not None else ()):
+                path = output_path(root, *ln)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                np.save(path, array)
         return len(chunk)
 
     written, pending = 0, None
@@ -150,7 +173,12 @@ def run(opt):
             n = len(chunk)
             base_u8, lookup_u8 = u8[:n], u8[n:]
             K, inv_K, T = camera(H, W, [ln[2] for ln in chunk], device)
-            best = ops.depth_hint_fuse(base_u8, lookup_u8, candidates(chunk, base_u8, lookup_u8), K, inv_K, T)
+            cand = candidates(chunk, base_u8, lookup_u8)
+            best = ops.depth_hint_fuse(base_u8, lookup_u8, cand, K, inv_K, T)
+            cand_host = None
+            if save_candidates:
+                cand_host = torch.empty(cand.shape, dtype=cand.dtype, pin_memory=device.type == "cuda")
+                cand_host.copy_(cand, non_blocking=True)
             if device.type == "cuda":
                 host = torch.empty(best.shape[:1] + best.shape[2:], dtype=torch.float32, pin_memory=True)
                 host.copy_(best[:, 0], non_blocking=True)
@@ -161,7 +189,7 @@ def run(opt):
             # this batch is enqueued: now the previous one's files are written
             if pending is not None:
                 written += flush(pending)
-            pending = (chunk, host.unsqueeze(1), event)
+            pending = (chunk, host.unsqueeze(1), event, cand_host)
         if pending is not None:
             written += flush(pending)
     finally:
@@ -186,6 +214,12 @@ def get_opts(argv=None):
     parser.add_argument("--candidates_dir", type=str, default=None,
                         help="read the candidate disparities from here instead of running OpenCV's matchers: one int16 [N, H, W] "
                              ".npy per line (disparity x 16, -16 = no match), laid out as the output is")
+    parser.add_argument("--matcher", type=str, default="auto", choices=["auto", "opencv", "device", "files"],
+                        help="where the candidate disparities come from: this package's matcher on the device (K35; its host twin "
+                             "with --device cpu), OpenCV's StereoSGBM on the host, --candidates_dir, or (auto) OpenCV if it can be "
+                             "imported and no --candidates_dir is given, else the files")
+    parser.add_argument("--save_candidates", type=str, default=None,
+                        help="also write every line's candidates here, int16 [N, H, W] .npy in the --candidates_dir layout")
     parser.add_argument("--batch_size", type=int, default=8, help="stereo pairs per launch of the fusion")
     parser.add_argument("--num_workers", type=int, default=12, help="decode / matcher threads (at most 16)")
     parser.add_argument("--img_ext", type=str, default=".png", help="the reference reads data/<frame>.png")

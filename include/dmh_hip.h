@@ -938,6 +938,44 @@ int dmh_depth_hint_fuse(const uint8_t* base, const uint8_t* lookup, const void* 
 int dmh_depth_hint_prepare(const float* src, const int32_t* flip, const int32_t* ytab, const int32_t* xtab, int64_t ytab_len,
                            int64_t xtab_len, int B, int Hs, int Ws, int H, int W, float* hint, float* mask, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K35 A semi-global stereo matcher in integers for the depth-hint candidates (states the matcher; it is
+ *     modelled on the structure of OpenCV's StereoSGBM in its single-pass mode, and nothing is claimed about equality with it).
+ *     base, lookup: uint8 [B][3][H][W] (planar; K31's byte output).  reverse: NULL, or int32 [B] in device memory: != 0 matches
+ *     the item on the mirrored pair (column W - 1 - x of both views) and stores the result mirrored back.
+ *     params: N parameter sets in HOST memory, 1 <= N <= DMH_SGM_MAX_MATCHERS.  num_disparities D: a multiple of 16 in [16, 256];
+ *     block_size 1, 2 or 3 (it enters through its radius r = block_size / 2 only); min_disparity 0; P1, P2 >= 0 with
+ *     5 ((2r+1)^2 567 + P2) < 32767 (int16 sums stay exact); pre_filter_cap in [1, 63]; uniqueness_ratio in [0, 100];
+ *     disp12_max_diff >= 0; speckle_window_size >= 0 (0: no speckle filter); speckle_range in [0, 4096].
+ *     out: int16 [B][N][H][W], disparity x 16, -16 where nothing matched (columns x < D always; everything when W <= D): the form
+ *     dmh_depth_hint_fuse takes as raw candidates.  Parameter sets that differ in nothing but a block_size of the same radius are
+ *     computed once and stored into each of their slots.
+ *     Workspace: per item and distinct parameter set two int16 volumes [H][W - D][D] and, with the speckle filter, 8 H W bytes of
+ *     labels, each rounded up to 256 bytes.  dmh_sgm_plan returns the bytes to allocate so that the call stays under cap_bytes
+ *     (at least 256; -1 with dmh_last_error() for arguments the launcher refuses, or when one parameter set of one item alone is
+ *     over the cap) and, through n_chunks (may be NULL), into how many sequences of launches the cap splits the batch.
+ *     dmh_sgm_disparity packs as many (item, parameter set) pairs as ws_bytes holds (at most 32) into each sequence of launches
+ *     (cost, five path directions, selection, four speckle passes), one sequence after the other on the stream.
+ *     phases: DMH_SGM_ALL.  A subset launches only those phases (tools/sgm_bench.py times the prefixes COST, COST | PATHS, ... to
+ *     attribute the time); out is defined only after a call whose phases include SELECT (and SPECKLE where a window is set).
+ *     W <= DMH_SGM_MAX_WIDTH, H <= 65535, B N H W < 2^31.  Integers only; integer atomics only where the result is unique (the
+ *     disp2 tie rule, union-find labels, component sizes); no host read: bitwise reproducible, capturable.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_SGM_MAX_MATCHERS 16
+#define DMH_SGM_MAX_WIDTH 4096
+#define DMH_SGM_COST 1
+#define DMH_SGM_PATHS 2
+#define DMH_SGM_SELECT 4
+#define DMH_SGM_SPECKLE 8
+#define DMH_SGM_ALL 15
+typedef struct dmh_sgm_params {
+    int32_t num_disparities, block_size, P1, P2, pre_filter_cap, uniqueness_ratio, disp12_max_diff, speckle_window_size,
+        speckle_range, min_disparity;
+} dmh_sgm_params;
+int64_t dmh_sgm_plan(int B, int H, int W, const dmh_sgm_params* params, int N, int64_t cap_bytes, int* n_chunks);
+int dmh_sgm_disparity(const uint8_t* base, const uint8_t* lookup, const int32_t* reverse, int B, int H, int W,
+                      const dmh_sgm_params* params, int N, int16_t* out, void* ws, int64_t ws_bytes, int phases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
