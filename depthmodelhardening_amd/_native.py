@@ -203,6 +203,11 @@ _SIGNATURES = {
     "dmh_depth_hint_fuse": (C.c_int, [_fp] * 3 + [C.c_int] + [_fp] * 3 + [C.c_int] * 4 + [_fp] * 3),
     "dmh_depth_hint_prepare": (C.c_int, [_fp] * 4 + [C.c_int64] * 2 + [C.c_int] * 5 + [_fp] * 3),
     "dmh_sgm_plan": (C.c_int64, [C.c_int] * 3 + [C.POINTER(SgmParams), C.c_int, C.c_int64, C.POINTER(C.c_int)]),
+    "dmh_reduce_bias_relu": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [_fp, _fp]),
+    "dmh_reduce_bwd_partials_size": (C.c_int64, [C.c_int] * 4),
+    "dmh_reduce_bwd_rounds": (C.c_int, [C.c_int] * 4),
+    "dmh_reduce_bwd_mask": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [_fp, _fp, _fp]),
+    "dmh_reduce_bwd_finish": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp, _fp, _fp]),
     "dmh_sgm_disparity": (C.c_int, [_fp] * 3 + [C.c_int] * 3 + [C.POINTER(SgmParams), C.c_int, _fp, _fp, C.c_int64, C.c_int, _fp]),
 }
 

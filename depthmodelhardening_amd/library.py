@@ -36,6 +36,9 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::velo_depth_map       MD2/kitti_utils.py:46-98 + datasets/kitti_dataset.py:70-85 (generate_depth_map, float32-equal) (K32, no autograd)
     dmh::color_jitter         MD2/datasets/mono_dataset.py:344-348,133,144 (torchvision 0.8.2 ColorJitter on 8-bit PIL images, Pillow's bytes) (K33, no autograd)
     dmh::depth_hint_fuse      depth-hints/precompute_depth_hints.py:151,247-252 (warp, SSIM + L1, argmin, gather per candidate) (K34, no autograd)
+    dmh::reduce_conv_degenerate   manydepth2/networks/resnet_encoder.py:124-129,321 in the degenerate call of manydepth2/trainer.py:371-385
+                              (reduce_conv over 64 features + D zero channels: conv3x3 with weight[:, :C], bias, ReLU)   (K36)
+                                                                                       + dmh::reduce_conv_degenerate_bwd
     dmh::sgm_disparity        the stereo matchers of depth-hints/precompute_depth_hints.py:42-63,128-147 as this package's own integer
                               semi-global matcher (not OpenCV's output)   (K35, no autograd)
 """
@@ -699,6 +702,49 @@ def _(current_feats, lookup_feats, poses, K, invK, depth_bins, buffer, set_missi
     return current_feats.new_empty((B, H, W)), current_feats.new_empty((B, H, W), dtype=torch.int32)
 
 
+# ---------------------------------------------------------------------------------------------------------------- K36
+@custom_op("dmh::reduce_conv_degenerate", mutates_args=())
+def reduce_conv_degenerate(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    ops._reduce_operands(x, weight, bias)       # the checks of ops.reduce_conv_degenerate; the launches below are its launches too
+    return ops.reduce_conv_fwd_launch(_cu(x), weight, bias)
+
+
+@reduce_conv_degenerate.register_fake
+def _(x, weight, bias):
+    return x.new_empty((x.shape[0], weight.shape[0], x.shape[2], x.shape[3]))
+
+
+@custom_op("dmh::reduce_conv_degenerate_bwd", mutates_args=())
+def reduce_conv_degenerate_bwd(g: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, y: torch.Tensor,
+                               need_params: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(g_x, g_weight, g_bias); without ``need_params`` the last two are empty tensors (no launch made for them)."""
+    g_x, g_w, g_b = ops.reduce_conv_bwd_launch(_cu(g), _cu(x), weight, _cu(y), True, need_params)
+    return g_x, (g_w if need_params else g.new_empty(0)), (g_b if need_params else g.new_empty(0))
+
+
+@reduce_conv_degenerate_bwd.register_fake
+def _(g, x, weight, y, need_params):
+    if need_params:
+        return torch.empty_like(x), weight.new_empty(weight.shape), weight.new_empty((weight.shape[0],))
+    return torch.empty_like(x), g.new_empty(0), g.new_empty(0)
+
+
+def _reduce_setup(ctx, inputs, output):
+    x, weight, bias = inputs
+    ctx.save_for_backward(x, weight, output)
+    ctx.need_params = not ops.weights_frozen()      # as ops.conv3x3: parameters are constants of an attack
+
+
+def _reduce_backward(ctx, g):
+    x, weight, y = ctx.saved_tensors
+    need_params = ctx.need_params and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+    g_x, g_w, g_b = torch.ops.dmh.reduce_conv_degenerate_bwd(g, x, weight, y, need_params)
+    return g_x, (g_w if need_params and ctx.needs_input_grad[1] else None), (g_b if need_params and ctx.needs_input_grad[2] else None)
+
+
+reduce_conv_degenerate.register_autograd(_reduce_backward, setup_context=_reduce_setup)
+
+
 # ---------------------------------------------------------------------------------------------------------------- K31
 @custom_op("dmh::pil_resample", mutates_args=())
 def pil_resample(src: torch.Tensor, out_h: int, out_w: int, filter: str = "lanczos", flip: Optional[torch.Tensor] = None,
@@ -800,4 +846,5 @@ OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
-       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity")
+       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity",
+       "reduce_conv_degenerate", "reduce_conv_degenerate_bwd")

@@ -7,8 +7,14 @@ The first two ResNet stages run on the current frame and on every lookup frame; 
 
 In eval() mode on CUDA fp32 tensors the stages run the fused paths ``ResnetEncoder`` uses for whole frames (K14, K9, K10 / K15),
 the cost volume is K30 (``ops.cost_volume``: one transposing pass and one launch, no host read, so the forward can be captured
-into a graph) and ``reduce_conv`` goes through ``ops.conv3x3``.  train() mode and CPU tensors take the module path: plain PyTorch
-expressions of the reference's arithmetic, which also serve as the CPU restatement the GPU tests compare with.
+into a graph) and ``reduce_conv`` goes through ``ops.conv3x3``.  CPU tensors take the module path: plain PyTorch expressions of
+the reference's arithmetic, which also serve as the CPU restatement the GPU tests compare with.
+
+In train() mode with gradients enabled, on CUDA fp32 tensors, the degenerate call -- the one the reference trains
+(manydepth2/trainer.py:371-385) -- runs the fused train path of ``ResnetEncoder.forward``: K14 for the stem (weight gradient K21),
+``ops.stem_bn_relu_pool_train`` on ``layer0.1``, the BasicBlocks' train-fused branch, the K10 filter prefetch, and ``reduce_conv`` as
+one autograd node (K36, ``ops.reduce_conv_degenerate``).  ``fuse_train = False`` switches that off (the module path; the blocks keep
+their own train-fused branch).  The multi-frame call keeps the module path in train mode: the reference does not train it.
 
 Two call forms.  Multi-frame: real lookup frames and relative poses.  Degenerate: the reference's wrapper, trainer and evaluation
 call the encoder with ``lookup_images * 0`` and a [1,1,4,4] zero pose, so every lookup is "missing", the volume and the confidence
@@ -22,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .resnet_encoder import _CONFIGS, ResNet
+from .resnet_encoder import _CONFIGS, ResNet, _plain3x3, _train_fused
 
 
 class _PixelGrid(nn.Module):
@@ -58,6 +64,7 @@ class ResnetEncoderMatching(nn.Module):
         self.num_depth_bins = num_depth_bins
         self.matching_height, self.matching_width = input_height // 4, input_width // 4     # the volume is built at 1/4 resolution
         self.roi_backward = False       # the windowed attack path (K19) is not extended to this encoder
+        self.fuse_train = True          # train(): the fused stem / reduce_conv path of the degenerate call (False: module path)
 
         block, layers = _CONFIGS[num_layers]
         trunk = ResNet(block, layers)
@@ -198,6 +205,48 @@ class ResnetEncoderMatching(nn.Module):
             y = blk.forward_fused(y, aff)
         return [f0, y]
 
+    def _stem_is_standard(self, image):
+        c = self.layer0[0]
+        return (image.dim() == 4 and image.shape[1] == 3 and image.shape[2] % 4 == 0 and image.shape[3] % 4 == 0
+                and tuple(c.weight.shape) == (64, 3, 7, 7) and c.stride == (2, 2) and c.padding == (3, 3) and c.dilation == (1, 1)
+                and c.groups == 1 and c.bias is None)
+
+    def _train_fused_ok(self, image):
+        """The conditions of ResnetEncoder.forward's train branch (its _stem and _train_fused), and reduce_conv as declared."""
+        r = self.reduce_conv[0]
+        return (self.fuse_train and _train_fused(self.layer0[1], image) and self._stem_is_standard(image)
+                and r.kernel_size == (3, 3) and r.stride == (1, 1) and r.padding == (1, 1) and r.dilation == (1, 1) and r.groups == 1
+                and r.bias is not None and r.out_channels % 8 == 0)
+
+    def _k10_convs(self):
+        """The 3x3 stride-1 convolutions of the residual blocks: the filters K10 may be asked for (ResnetEncoder._k10_convs)."""
+        if self.__dict__.get("_k10_list") is None:
+            out = []
+            for layer in (self.layer1[1], self.layer2, self.layer3, self.layer4):
+                for blk in layer:
+                    for conv in (getattr(blk, "conv1", None), getattr(blk, "conv2", None)):
+                        if conv is not None and conv.kernel_size == (3, 3) and _plain3x3(conv):
+                            out.append(conv)
+            self.__dict__["_k10_list"] = out
+        return self.__dict__["_k10_list"]
+
+    def _prefetch_filters(self):
+        """All K10 filters of the train pass in one launch, as ResnetEncoder._prefetch_filters does (inside ops.wino_pass() a pose
+        encoder's prefetch leaves them in place): the blocks' and reduce_conv's ``weight[:, :64]``."""
+        dirs = (False, True) if torch.is_grad_enabled() else (False,)
+        jobs = [(c.weight, bw, None) for c in self._k10_convs() for bw in dirs]
+        w = self.reduce_conv[0].weight
+        if w.is_cuda and w.dtype == torch.float32:
+            wc = ops._reduce_slice(w, int(self.num_ch_enc[1]), fresh=True)      # every forward, like the transforms below
+            jobs += [(wc, bw, None) for bw in dirs]
+        ops.wino_prefetch(jobs, fresh=True)
+
+    def _head_train(self, image):
+        """[features 0, features 1] on the fused train path: K14, K9's train-mode stem pass, the layer-1 blocks."""
+        z = ops.stem_conv_norm(image, self.layer0[0].weight, 0.45, 0.225)
+        f0, p = ops.stem_bn_relu_pool_train(self.layer0[1], z)
+        return [f0, self.layer1[1](p)]
+
     def feature_extraction(self, image, return_all_feats=False):
         """The first two ResNet stages on ``(image - 0.45) / 0.225``."""
         if self._fused_ok(image):
@@ -236,9 +285,14 @@ class ResnetEncoderMatching(nn.Module):
         """(features, lowest_cost, confidence_mask).  ``lookup_images`` [B,L,3,H,W], or None: the caller states that there are no
         lookup frames (the degenerate call; ``poses`` is then not read)."""
         fused = self._fused_ok(current_image)
+        train_fused = not fused and lookup_images is None and self._train_fused_ok(current_image)
         if self.adaptive_bins and min_depth_bin is not None and max_depth_bin is not None:
             self.compute_depth_bins(min_depth_bin, max_depth_bin)
-        self.features = self.feature_extraction(current_image, return_all_feats=True)
+        if train_fused:
+            self._prefetch_filters()
+            self.features = self._head_train(current_image)
+        else:
+            self.features = self.feature_extraction(current_image, return_all_feats=True)
         current_feats = self.features[-1]
         B, C, H, W = current_feats.shape
         D = self.num_depth_bins
@@ -248,7 +302,10 @@ class ResnetEncoderMatching(nn.Module):
         if lookup_images is None:
             confidence_mask = current_feats.new_zeros((B, H, W))
             lowest_cost = (1 / bins[:1]).to(current_feats.dtype).expand(B, H * W).reshape(B, H, W)
-            post = self._reduce(current_feats, weight[:, :C].contiguous())
+            if train_fused:
+                post = ops.reduce_conv_degenerate(current_feats, weight, self.reduce_conv[0].bias)       # K36: one autograd node
+            else:
+                post = self._reduce(current_feats, weight[:, :C].contiguous())
             return self._tail(post, fused), lowest_cost, confidence_mask
 
         if lookup_images.dim() != 5 or lookup_images.shape[0] != B or lookup_images.shape[2:] != current_image.shape[1:]:

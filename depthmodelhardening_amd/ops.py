@@ -1844,6 +1844,177 @@ def conv3x3(x, weight, bias=None, padding=1):
     return _Conv3x3.apply(_c(x), weight, bias, int(padding))
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# K36: ManyDepth's reduce_conv in the degenerate call (no lookup frames: the D cost-volume channels are exact zeros)
+# ---------------------------------------------------------------------------------------------------------------
+_reduce_slices = {}     # weight pointer -> (weight version, weight[:, :C] contiguous, weight): kept like the Winograd filters
+
+
+def _reduce_slice(weight, Cc, fresh=False):
+    """The contiguous ``weight[:, :C]`` of a [K, C + D, 3, 3] filter, cached on (data_ptr, _version) so that a pass slices it
+    once (forward; the backward finds it).  ``fresh``: slice again whatever the cache says -- the train pass's prefetch asks for
+    that on every forward, as wino_prefetch re-transforms every filter, because a write through ``p.data`` (ddp.broadcast_parameters,
+    a weight swap) changes the weight without changing its version.  An entry keeps its weight tensor alive, so the pointer cannot
+    come to name another tensor's data; at most 8 entries."""
+    key = (weight.data_ptr(), Cc)
+    hit = _reduce_slices.get(key)
+    if not fresh and hit is not None and hit[0] == weight._version and hit[1].device == weight.device:
+        return hit[1]
+    if len(_reduce_slices) >= 8:
+        _reduce_slices.clear()
+    wc = weight.detach()[:, :Cc].contiguous()
+    _reduce_slices[key] = (weight._version, wc, weight)
+    return wc
+
+
+def _reduce_act_ok(B, Cc, K, H, W):
+    """K10 with its fused bias + ReLU epilogue takes the shape (the rule of conv3x3_bn_act)."""
+    return _wino_ok(B, Cc, K, H, W, allow_split=False, allow_sk=True)
+
+
+def reduce_bwd_mask(g, y, Cc=None):
+    """(g * [y > 0], per-(channel, slab) partial sums of it): K36's first backward launch.  ``Cc``: the node's input channels
+    (the C of the entry points' checks; K when the pass is used on its own)."""
+    lib = N.lib()
+    B, K = g.shape[0], g.shape[1]
+    Cc = K if Cc is None else Cc
+    HW = g.numel() // (B * K)
+    n = lib.dmh_reduce_bwd_partials_size(B, Cc, K, HW)
+    if n < 0:
+        N.check(1)
+    part = torch.empty(n, device=g.device, dtype=torch.float32)
+    g_pre = torch.empty_like(g)
+    N.check(_timed("reduce_bwd_mask", lambda: lib.dmh_reduce_bwd_mask(N.ptr(g), N.ptr(y), B, Cc, K, HW, N.ptr(g_pre), N.ptr(part),
+                                                                      N.stream()), 12 * g.numel()))
+    return g_pre, part
+
+
+def reduce_bwd_rounds(B, K, HW):
+    """fp32 roundings on the longest path of one bias-gradient sum of K36 (csrc/reduce_node.hip's header derives it)."""
+    return int(N.lib().dmh_reduce_bwd_rounds(B, K, K, HW))
+
+
+def _lib_deterministic():
+    """Scope for K36's library fall-backs (shapes K10 / K18 do not take): the library's deterministic algorithms only -- its
+    default weight-gradient and backward-data solvers for small maps add with atomics, and the node promises the same bits twice."""
+    cd = torch.backends.cudnn
+    return cd.flags(enabled=cd.enabled, benchmark=cd.benchmark, deterministic=True, allow_tf32=cd.allow_tf32)
+
+
+def reduce_conv_fwd_launch(x, weight, bias):
+    """K36 forward on contiguous fp32 CUDA tensors: one K10 launch with the bias + ReLU epilogue where the shape fills the chip,
+    else the convolution ops.conv3x3 would pick + K36's bias_relu pass (in place)."""
+    B, Cc, H, W = x.shape
+    K = weight.shape[0]
+    wc = _reduce_slice(weight, Cc)
+    b = _c(bias.detach())
+    if _reduce_act_ok(B, Cc, K, H, W):
+        return _k10(x, wc, None, backward=False, bias=b, flag=1, workspace=True, count_filter=True)
+    if _wino_ok(B, Cc, K, H, W):
+        z = _wino_conv(x, _wino_filter(wc, False), None, K, 1)
+    else:
+        with _lib_deterministic():
+            z = torch.conv2d(x, wc, None, 1, 1)
+    N.check(_timed("reduce_bias_relu", lambda: N.lib().dmh_reduce_bias_relu(N.ptr(z), N.ptr(b), B, Cc, K, H * W, N.ptr(z), N.stream()),
+                   8 * z.numel()))
+    return z
+
+
+def reduce_conv_bwd_launch(g, x, weight, y, need_x=True, need_params=True):
+    """K36 backward: (g_x, g_weight, g_bias).  The mask pass (g_pre and the bias gradient's partial sums in one read of g and y),
+    K10 backward-data and K18 on g_pre (the library's kernels for shapes they do not take), and the finish launch: the bias
+    gradient, and the [K, C, 3, 3] gradient laid into the [K, C + D, 3, 3] layout with exact zeros behind it.  Without
+    ``need_params`` (inside frozen_weights()) the mask pass alone precedes backward-data; g_weight and g_bias are None."""
+    B, Cc, H, W = x.shape
+    K, D = weight.shape[0], weight.shape[1] - Cc
+    lib = N.lib()
+    if need_params:
+        g_pre, part = reduce_bwd_mask(g, y, Cc)
+    else:
+        g_pre = _relu_mask_bwd(y, g)
+    wc = _reduce_slice(weight, Cc)
+    g_x = g_w = g_b = None
+    if need_x:
+        if _wino_ok(B, K, Cc, H, W):
+            g_x = _wino_conv(g_pre, _wino_filter(wc, True), None, Cc, 1)
+        else:
+            with _lib_deterministic():
+                g_x = torch.ops.aten.convolution_backward(g_pre, x, wc, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                                          [True, False, False])[0]
+    if need_params:
+        if _wrw_ok(x, g_pre, K, Cc):
+            ws = torch.empty(lib.dmh_wino_wrw_workspace_size(B, Cc, K, H, W, 1), device=g.device, dtype=torch.float32)
+            dw = torch.empty((K, Cc, 3, 3), device=g.device, dtype=torch.float32)
+            N.check(_timed("wino_wrw", lambda: lib.dmh_wino_wrw(N.ptr(x), N.ptr(g_pre), B, Cc, K, H, W, 1, N.ptr(ws), N.ptr(dw),
+                                                                N.stream()), 4 * (x.numel() + g.numel()), 18 * Cc * g.numel()))
+        else:
+            with _lib_deterministic():
+                dw = _c(torch.ops.aten.convolution_backward(g_pre, x, wc, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                                            [False, True, False])[1])
+        g_w = torch.empty(tuple(weight.shape), device=g.device, dtype=torch.float32)
+        g_b = torch.empty(K, device=g.device, dtype=torch.float32)
+        N.check(_timed("reduce_bwd_finish", lambda: lib.dmh_reduce_bwd_finish(N.ptr(part), N.ptr(dw), B, Cc, K, D, H * W, N.ptr(g_b),
+                                                                              N.ptr(g_w), N.stream()),
+                       4 * (g_w.numel() + dw.numel())))
+    return g_x, g_w, g_b
+
+
+class _ReduceConvDegenerate(torch.autograd.Function):
+    """relu(conv3x3(x, weight[:, :C]) + bias) as one node (reduce_conv_fwd_launch / reduce_conv_bwd_launch).  Neither x with D
+    zero channels nor a zero-padded filter ever exists."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        y = reduce_conv_fwd_launch(x, weight, bias)
+        ctx.save_for_backward(x, weight, y)
+        ctx.params_const = _wino_frozen > 0
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, y = ctx.saved_tensors
+        need_params = (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and not ctx.params_const
+        g_x, g_w, g_b = reduce_conv_bwd_launch(_c(g), x, weight, y, ctx.needs_input_grad[0], need_params)
+        return g_x, (g_w if ctx.needs_input_grad[1] else None), (g_b if ctx.needs_input_grad[2] else None)
+
+
+def reduce_conv_degenerate_host(x, weight, bias):
+    """The definition in torch, any device and dtype: relu(conv3x3(x, weight[:, :C]) + bias) == the reference's
+    ``reduce_conv(cat([x, zeros(B, D, H, W)], 1))`` (manydepth2/networks/resnet_encoder.py:321 in the degenerate call).  The path
+    of CPU tensors and the yardstick of the fused node."""
+    Cc = x.shape[1]
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] < Cc:
+        raise RuntimeError("reduce_conv_degenerate: weight must be [K, C + D, 3, 3] with C = x.shape[1]; got %s for %s"
+                           % (tuple(weight.shape), tuple(x.shape)))
+    return torch.relu(torch.nn.functional.conv2d(x, weight[:, :Cc], bias, 1, 1))
+
+
+def _reduce_operands(x, weight, bias):
+    """What K36 takes, checked once for ops.reduce_conv_degenerate and torch.ops.dmh.reduce_conv_degenerate alike."""
+    _need_cuda(x)
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] < x.shape[1] or bias is None \
+            or tuple(bias.shape) != (weight.shape[0],):
+        raise RuntimeError("reduce_conv_degenerate: x [B,C,H,W], weight [K,C+D,3,3], bias [K] expected; got %s, %s, %s" % (
+            tuple(x.shape), tuple(weight.shape), None if bias is None else tuple(bias.shape)))
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or bias.dtype != torch.float32:
+        raise RuntimeError("libdmh_hip ops compute in fp32; got %s, %s, %s" % (x.dtype, weight.dtype, bias.dtype))
+    if not (weight.is_cuda and bias.is_cuda):
+        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got weight on %s, bias on %s" % (weight.device, bias.device))
+    if x.shape[1] % 8 or weight.shape[0] % 8:
+        raise RuntimeError("reduce_conv_degenerate: C and K must be multiples of 8; got C = %d, K = %d" % (x.shape[1], weight.shape[0]))
+
+
+def reduce_conv_degenerate(x, weight, bias):
+    """ManyDepth's ``reduce_conv`` when every lookup frame is missing -- the call the reference's trainer, wrapper and evaluation
+    make: x [B, C, H, W], weight [K, C + D, 3, 3], bias [K] -> relu(conv3x3(x, weight[:, :C]) + bias) [B, K, H, W].  CUDA fp32
+    tensors take K36 (one autograd node; weight.grad has the full [K, C + D, 3, 3] layout with exact zeros in [:, C:], sums in a
+    fixed order); CPU tensors take reduce_conv_degenerate_host.  Inside frozen_weights() no parameter gradient is produced."""
+    if not x.is_cuda:
+        return reduce_conv_degenerate_host(x, weight, bias)
+    _reduce_operands(x, weight, bias)
+    return _ReduceConvDegenerate.apply(_c(x), weight, bias)
+
+
 def _stem_wrw(x, g, weight, mean, std):
     """K21: dW of the 7x7/2 first convolution on (x - mean) / std, fixed-order sums on the fp32 MFMA; None when the shape is
     not the kernel's (3 -> 64 channels, even H, W a multiple of 8): the caller then takes ATen's."""

@@ -133,6 +133,12 @@ class MonodepthOptions:
                        help="build the pose networks (MD2/trainer.py:97-121) and serve the monocular frame ids of --frame_ids "
                             "(the default 0 -1 1): --pose_model_type separate_resnet / shared, --pose_model_input pairs / all; "
                             "the pose head is one HIP launch (K29).  Without it the trainer refuses monocular frame ids")
+        p.add_argument("--depth_net", type=str, default="resnet", choices=["resnet", "manydepth"],
+                       help="the depth network: Monodepth2's / DepthHints' ResNet U-Net (resnet), or ManyDepth's cost-volume encoder "
+                            "as the reference hardens it (manydepth2/trainer.py): the degenerate single-frame call, disparities / "
+                            "8.6437, built by import_depth_model(..., 'manydepth', matching=True) from --load_weights_folder (random "
+                            "initialisation without one); reduce_conv runs as one HIP node (K36).  Refuses --contrastive_learning, "
+                            "--pose_model_type shared, --graph_attack and --num_layers other than 18")
         p.add_argument("--max_steps", type=int, default=0, help="stop after this many iterations (0 = full epochs)")
         p.add_argument("--graph_attack", action="store_true",
                        help="L_inf attack: one set of window sizes for all steps, step 1 captured in a HIP graph and replayed "

@@ -27,7 +27,7 @@ from . import networks, ops
 from .contrastive import SimSiam
 from .datasets import SyntheticKITTIDataset, make_object
 from .ddp import GradBucket, average_buffers, broadcast_parameters
-from .depth_model import DepthModelWrapper, import_depth_model
+from .depth_model import MANYDEPTH_DISP_SCALE, DepthModelWrapper, import_depth_model
 from .layers import SSIM, compute_depth_errors, disp_to_depth, get_smooth_loss
 from .my_utils import ori_H, ori_W
 
@@ -239,7 +239,27 @@ class Trainer:
             raise RuntimeError("--use_depth_hints is the DepthHints trainer's option: use --loss_variant dh with "
                                "auto-masking (DH/trainer.py:71-75,557-590)")
 
-        if self.opt.fine_tune:
+        self.manydepth = getattr(self.opt, "depth_net", "resnet") == "manydepth"
+        if self.manydepth:
+            # ManyDepth as the reference hardens it (manydepth2/trainer.py:70-95,371-385): the cost-volume encoder in the
+            # degenerate single-frame call, disparities / 8.6437
+            if self.opt.contrastive_learning:
+                raise NotImplementedError("--depth_net manydepth with --contrastive_learning: the benign pass calls the matching "
+                                          "encoder with one argument (the reference dies with a TypeError, manydepth2/trainer.py:390)")
+            if self.use_pose_net and self.opt.pose_model_type == "shared":
+                raise NotImplementedError("--depth_net manydepth with --pose_model_type shared: the reference's shared branch feeds "
+                                          "every frame through the matching encoder and skips the 8.6437 disparity scale "
+                                          "(manydepth2/trainer.py:352-370); use separate_resnet")
+            if getattr(self.opt, "graph_attack", False):
+                raise NotImplementedError("--depth_net manydepth with --graph_attack: graph capture of ManyDepthModelWrapper inside "
+                                          "the training attack is not built")
+            if self.opt.num_layers != 18:
+                raise NotImplementedError("--depth_net manydepth is the ResNet-18 model of import_depth_model(..., 'manydepth'); "
+                                          "got --num_layers %d" % self.opt.num_layers)
+            # --fine_tune selects the same call (manydepth2/trainer.py:70-80); without a folder the initialisation is random
+            m = import_depth_model((1024, 320), 'manydepth', pre_model_path=self.opt.load_weights_folder, matching=True)
+            self.models["encoder"], self.models["depth"] = m.encoder, m.decoder
+        elif self.opt.fine_tune:
             m = import_depth_model((1024, 320), pre_model_path=self.opt.load_weights_folder)
             self.models["encoder"], self.models["depth"] = m.encoder, m.decoder
         else:
@@ -249,7 +269,10 @@ class Trainer:
         self.models["depth"].to(self.device)
         self.parameters_to_train += list(self.models["encoder"].parameters())
         self.parameters_to_train += list(self.models["depth"].parameters())
-        self.models["DepthModelWrapper"] = DepthModelWrapper(self.models["encoder"], self.models["depth"]).to(self.device)
+        if self.manydepth:
+            self.models["DepthModelWrapper"] = m.to(self.device)
+        else:
+            self.models["DepthModelWrapper"] = DepthModelWrapper(self.models["encoder"], self.models["depth"]).to(self.device)
         if self.opt.predictive_mask:
             # "the same architecture as our depth decoder", one mask per source frame (MD2/trainer.py:127-133)
             self.models["predictive_mask"] = networks.DepthDecoder(self.models["encoder"].num_ch_enc, self.opt.scales,
@@ -286,7 +309,12 @@ class Trainer:
         self.model_lr_scheduler = optim.lr_scheduler.StepLR(self.model_optimizer, self.opt.scheduler_step_size, 0.1)
         # the encoder's ImageNet ``fc`` is in parameters_to_train (trainer.py:85) but never gets a gradient:
         # it is left out of the all-reduce bucket
-        fc_ids = {id(p) for p in self.models["encoder"].encoder.fc.parameters()}
+        if self.manydepth:
+            # ... as do prematching_conv (declared and unused, in the reference too) and the frozen pixel grid of the backprojector
+            enc = self.models["encoder"]
+            fc_ids = {id(p) for mod in (enc.prematching_conv, enc.backprojector) for p in mod.parameters()}
+        else:
+            fc_ids = {id(p) for p in self.models["encoder"].encoder.fc.parameters()}
         if "pose_encoder" in self.models:
             fc_ids |= {id(p) for p in self.models["pose_encoder"].encoder.fc.parameters()}
         self.bucket = GradBucket([p for p in self.parameters_to_train if id(p) not in fc_ids], self.world_size)
@@ -489,9 +517,20 @@ class Trainer:
             all_features = [torch.split(f, self.opt.batch_size) for f in all_features]
             features = {k: [f[i] for f in all_features] for i, k in enumerate(self.opt.frame_ids)}
             depth_features = features[0]
+        elif self.manydepth:
+            # the reference's degenerate call (manydepth2/trainer.py:371-385: lookup_images * 0, zero pose), stated as "no lookups"
+            w = self.models["DepthModelWrapper"]
+            x = inputs["color_aug", 0, 0]
+            bs = x.shape[0]
+            features, _, _ = self.models["encoder"](x, None, w.zero_pose, w.K.expand(bs, 4, 4), w.invK.expand(bs, 4, 4),
+                                                    w.min_depth_bin, w.max_depth_bin)
+            depth_features = features
         else:
             features = depth_features = self.models["encoder"](inputs["color_aug", 0, 0])
         outputs = LazyOutputs(self.models["depth"](depth_features))
+        if self.manydepth:
+            for k in [k for k in outputs if isinstance(k, tuple) and k[0] == "disp"]:        # manydepth2/trainer.py:383-385
+                outputs[k] = outputs[k] / MANYDEPTH_DISP_SCALE
         outputs["middle_features_aug"] = depth_features
         if self.opt.contrastive_learning:
             outputs["middle_features_ben"] = self.models["encoder"](inputs["color_ben", 0, 0])
@@ -828,7 +867,8 @@ class Trainer:
             json.dump({k: v for k, v in self.opt.__dict__.items()}, f, indent=2, default=str)
 
     def save_model(self):
-        """weights_{epoch}/{model}.pth state_dicts (+ height/width/use_stereo in the encoder) and adam.pth --
+        """weights_{epoch}/{model}.pth state_dicts (+ height/width/use_stereo in the encoder; --depth_net manydepth: also
+        min_depth_bin/max_depth_bin) and adam.pth --
         the reference's on-disk format (MD2/trainer.py:765-785), written by rank 0 only."""
         save_folder = os.path.join(self.log_path, "models", "weights_{}".format(self.epoch))
         os.makedirs(save_folder, exist_ok=True)
@@ -840,6 +880,13 @@ class Trainer:
                 to_save['height'] = self.opt.height
                 to_save['width'] = self.opt.width
                 to_save['use_stereo'] = self.opt.use_stereo
+                if self.manydepth:
+                    # manydepth2/trainer.py:812; height / width are the frame the file's pixel grid (backprojector.*) was built
+                    # for, which is what import_depth_model(..., matching=True) rebuilds the encoder from.  The reference can
+                    # only train at that size (its degenerate call still back-projects), so there this IS --height / --width
+                    to_save['height'], to_save['width'] = 4 * model.matching_height, 4 * model.matching_width
+                    to_save['min_depth_bin'] = self.models["DepthModelWrapper"].min_depth_bin
+                    to_save['max_depth_bin'] = self.models["DepthModelWrapper"].max_depth_bin
             torch.save(to_save, os.path.join(save_folder, "{}.pth".format(model_name)))
         torch.save(self.model_optimizer.state_dict(), os.path.join(save_folder, "adam.pth"))
 

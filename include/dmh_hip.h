@@ -976,6 +976,28 @@ int64_t dmh_sgm_plan(int B, int H, int W, const dmh_sgm_params* params, int N, i
 int dmh_sgm_disparity(const uint8_t* base, const uint8_t* lookup, const int32_t* reverse, int B, int H, int W,
                       const dmh_sgm_params* params, int N, int16_t* out, void* ws, int64_t ws_bytes, int phases, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K36 ManyDepth's reduce_conv in the degenerate call its trainer and wrapper make (manydepth2/trainer.py:371-385,
+ *     depth_model.py:42-58: lookup_images * 0, zero pose -> the D cost-volume channels are exact zeros):
+ *       y = relu(corr3x3(zero_pad(x, 1), w[:, :C]) + bias),  w [K][C+D][3][3]  (manydepth2/networks/resnet_encoder.py:124-129,321)
+ *     The convolutions are K10 / K18 (or the library's); these are the passes around them.  x [B,C,H,W], y / g / g_pre
+ *     [B,K,H,W], HW = H * W.  All refuse null pointers, C % 8, K % 8, K > 65535 and B * max(C, K) * HW >= 2^31 (C is the
+ *     node's input channel count everywhere: the element-wise passes check it as part of the node's shape and index by K only).
+ *   dmh_reduce_bias_relu : y = relu(z + bias[k]); y may be z.
+ *   dmh_reduce_bwd_mask  : g_pre = g * [y > 0]; partials[k][s] = the sum of g_pre over slab s of channel k, all images
+ *                          (dmh_reduce_bwd_partials_size floats).  With HW % 4 == 0 the planes must be 16-byte aligned.
+ *   dmh_reduce_bwd_finish: g_bias[k] = sum_s partials[k][s] in index order (float64, rounded once);
+ *                          g_weight [K][C+D][3][3] = dw [K][C][3][3] in channels < C, exact zeros in the D others.
+ *   dmh_reduce_bwd_rounds: the fp32 roundings on the longest path of one g_bias sum (csrc/reduce_node.hip derives it); no launch.
+ *     No atomics, no host read, fixed order: two runs give the same bits.
+ * ---------------------------------------------------------------------------------- */
+int dmh_reduce_bias_relu(const float* z, const float* bias, int B, int C, int K, int HW, float* y, void* stream);
+int64_t dmh_reduce_bwd_partials_size(int B, int C, int K, int HW);
+int dmh_reduce_bwd_rounds(int B, int C, int K, int HW);
+int dmh_reduce_bwd_mask(const float* g, const float* y, int B, int C, int K, int HW, float* g_pre, float* partials, void* stream);
+int dmh_reduce_bwd_finish(const float* partials, const float* dw, int B, int C, int K, int D, int HW, float* g_bias,
+                          float* g_weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
