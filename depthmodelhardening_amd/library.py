@@ -3,10 +3,12 @@
 SURVEY.md section 8b asks for "PyTorch-ROCm custom ops": operators the dispatcher knows, with a fake-tensor (meta)
 implementation, so that they can be traced, exported and compiled (``torch.compile`` / ``torch.export`` see an opaque
 ``dmh::...`` call with known output shapes instead of a ctypes call they cannot look into) and an autograd formula that is
-itself a registered op.  Each operator below is a thin schema around the same launches ``ops.py`` makes through
-``libdmh_hip.so`` (include/dmh_hip.h); ``ops.py``'s ``torch.autograd.Function`` wrappers remain the path the Trainer and the
-attacks use (they carry the per-attack caches and the fused multi-launch nodes), and tests/test_gpu_library.py holds the two
-to the same bits.  There is no CPU kernel behind any of them: the CUDA implementations reject CPU tensors like ``ops.py`` does.
+itself a registered op.  Each operator below is a schema, a fake implementation and an autograd formula around a launcher of
+``ops.py`` (``ops.*_fwd_launch`` / ``ops.*_bwd_launch``, or the ``ops.*`` function itself): this module makes no call into
+``libdmh_hip.so`` of its own, so the two surfaces cannot drift.  ``ops.py``'s ``torch.autograd.Function`` wrappers, around the
+same launchers, remain the path the Trainer and the attacks use (they carry the per-attack caches and the fused multi-launch
+nodes); tests/test_gpu_library.py holds the wrappers of both surfaces -- argument order, saved tensors, gradient slots -- to
+the same bits.  There is no CPU kernel behind any of them: CPU tensors are rejected as ``ops.py`` rejects them.
 
     dmh::eot_paste            physicalTrans.py:156-165 + phy_obj_atk.py:88-90   (K3)   + dmh::eot_paste_bwd
     dmh::masked_sq_mean       phy_obj_atk.py:94, pgd_depth.py:68-70             (K6)   + dmh::masked_sq_mean_bwd
@@ -42,7 +44,6 @@ to the same bits.  There is no CPU kernel behind any of them: the CUDA implement
     dmh::sgm_disparity        the stereo matchers of depth-hints/precompute_depth_hints.py:42-63,128-147 as this package's own integer
                               semi-global matcher (not OpenCV's output)   (K35, no autograd)
 """
-import ctypes as C
 from typing import List, Optional, Tuple
 
 import torch
@@ -56,16 +57,15 @@ def _cu(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _cul(ts):
+    return [_cu(t) for t in ts]
+
+
 # ----------------------------------------------------------------------------------------------------------------- K3
 @custom_op("dmh::eot_paste", mutates_args=())
 def eot_paste(scene: torch.Tensor, patch: torch.Tensor, pmask: torch.Tensor, coeffs: torch.Tensor, l_pad: int, t_pad: int,
               oh: int, ow: int, flip: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    scene, patch, pmask, coeffs = _cu(scene), _cu(patch), _cu(pmask), _cu(coeffs)
-    a = ops._paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, oh, ow, N.PASTE_COMPOSITE, flip)
-    adv = torch.empty((a.N, 3, oh, ow), device=scene.device, dtype=torch.float32)
-    mask_out = torch.empty((a.N, 1, oh, ow), device=scene.device, dtype=torch.float32)
-    N.check(N.lib().dmh_eot_paste_fwd(C.byref(a), N.ptr(adv), N.ptr(mask_out), N.stream()))
-    return adv, mask_out
+    return ops.eot_paste_fwd_launch(_cu(scene), _cu(patch), _cu(pmask), _cu(coeffs), l_pad, t_pad, oh, ow, N.PASTE_COMPOSITE, flip)
 
 
 @eot_paste.register_fake
@@ -77,11 +77,8 @@ def _(scene, patch, pmask, coeffs, l_pad, t_pad, oh, ow, flip=None):
 @custom_op("dmh::eot_paste_bwd", mutates_args=())
 def eot_paste_bwd(scene: torch.Tensor, patch: torch.Tensor, pmask: torch.Tensor, coeffs: torch.Tensor, l_pad: int, t_pad: int,
                   oh: int, ow: int, flip: Optional[torch.Tensor], g_adv: torch.Tensor) -> torch.Tensor:
-    scene, patch, pmask, coeffs, g_adv = _cu(scene), _cu(patch), _cu(pmask), _cu(coeffs), _cu(g_adv)
-    a = ops._paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, oh, ow, N.PASTE_COMPOSITE, flip)
-    g_patch = torch.empty_like(patch)
-    N.check(N.lib().dmh_eot_paste_bwd(C.byref(a), N.ptr(g_adv), N.ptr(g_patch), N.stream()))
-    return g_patch
+    return ops.eot_paste_bwd_launch(_cu(scene), _cu(patch), _cu(pmask), _cu(coeffs), l_pad, t_pad, oh, ow, N.PASTE_COMPOSITE, flip,
+                                    None, _cu(g_adv))
 
 
 @eot_paste_bwd.register_fake
@@ -108,16 +105,7 @@ eot_paste.register_autograd(_paste_backward, setup_context=_paste_setup)
 # ----------------------------------------------------------------------------------------------------------------- K6
 @custom_op("dmh::masked_sq_mean", mutates_args=())
 def masked_sq_mean(disp: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    disp = _cu(disp)
-    mask = None if mask is None else _cu(mask)
-    lib = N.lib()
-    n = disp.numel()
-    if mask is not None and mask.numel() != n:
-        raise RuntimeError("masked_sq_mean: mask and disp sizes differ")
-    part = torch.empty(lib.dmh_sq_mean_partials_size(n), device=disp.device, dtype=torch.float32)
-    cost = torch.empty((), device=disp.device, dtype=torch.float32)
-    N.check(lib.dmh_masked_sq_mean_fwd(N.ptr(disp), N.ptr(mask), n, N.ptr(part), N.ptr(cost), N.stream()))
-    return cost
+    return ops.masked_sq_mean_fwd_launch(_cu(disp), None if mask is None else _cu(mask))
 
 
 @masked_sq_mean.register_fake
@@ -127,12 +115,7 @@ def _(disp, mask=None):
 
 @custom_op("dmh::masked_sq_mean_bwd", mutates_args=())
 def masked_sq_mean_bwd(disp: torch.Tensor, mask: Optional[torch.Tensor], g: torch.Tensor) -> torch.Tensor:
-    disp = _cu(disp)
-    mask = None if mask is None else _cu(mask)
-    g_disp = torch.empty_like(disp)
-    N.check(N.lib().dmh_masked_sq_mean_bwd(N.ptr(disp), N.ptr(mask), disp.numel(), N.ptr(_cu(g.to(torch.float32))), N.ptr(g_disp),
-                                           N.stream()))
-    return g_disp
+    return ops.masked_sq_mean_bwd_launch(_cu(disp), None if mask is None else _cu(mask), g)
 
 
 @masked_sq_mean_bwd.register_fake
@@ -158,13 +141,7 @@ masked_sq_mean.register_autograd(_msm_backward, setup_context=_msm_setup)
 @custom_op("dmh::gt_depth_mse", mutates_args=())
 def gt_depth_mse(disp: torch.Tensor, disp_gt: torch.Tensor, objmask: torch.Tensor, objdepth: torch.Tensor, min_depth: float,
                  max_depth: float) -> torch.Tensor:
-    disp, disp_gt, objmask, bstride, objdepth, B, HW = ops._gt_depth_operands(disp, disp_gt, objmask, objdepth)
-    lib = N.lib()
-    part = torch.empty(lib.dmh_sq_mean_partials_size(B * HW), device=disp.device, dtype=torch.float32)
-    cost = torch.empty((), device=disp.device, dtype=torch.float32)
-    N.check(lib.dmh_gt_depth_mse_fwd(N.ptr(disp), N.ptr(disp_gt), C.c_void_p(objmask.data_ptr()), bstride, N.ptr(objdepth), B, HW,
-                                     float(min_depth), float(max_depth), N.ptr(part), N.ptr(cost), N.stream()))
-    return cost
+    return ops.gt_depth_mse_fwd_launch(*ops._gt_depth_operands(disp, disp_gt, objmask, objdepth), min_depth, max_depth)
 
 
 @gt_depth_mse.register_fake
@@ -175,12 +152,7 @@ def _(disp, disp_gt, objmask, objdepth, min_depth, max_depth):
 @custom_op("dmh::gt_depth_mse_bwd", mutates_args=())
 def gt_depth_mse_bwd(disp: torch.Tensor, disp_gt: torch.Tensor, objmask: torch.Tensor, objdepth: torch.Tensor, min_depth: float,
                      max_depth: float, g: torch.Tensor) -> torch.Tensor:
-    disp, disp_gt, objmask, bstride, objdepth, B, HW = ops._gt_depth_operands(disp, disp_gt, objmask, objdepth)
-    g_disp = torch.empty_like(disp)
-    N.check(N.lib().dmh_gt_depth_mse_bwd(N.ptr(disp), N.ptr(disp_gt), C.c_void_p(objmask.data_ptr()), bstride, N.ptr(objdepth), B, HW,
-                                         float(min_depth), float(max_depth), N.ptr(_cu(g.to(torch.float32))), N.ptr(g_disp),
-                                         N.stream()))
-    return g_disp
+    return ops.gt_depth_mse_bwd_launch(*ops._gt_depth_operands(disp, disp_gt, objmask, objdepth), min_depth, max_depth, g)
 
 
 @gt_depth_mse_bwd.register_fake
@@ -204,13 +176,7 @@ gt_depth_mse.register_autograd(_gtd_backward, setup_context=_gtd_setup)
 # ----------------------------------------------------------------------------------------------------------------- K4
 @custom_op("dmh::pgd_linf_step", mutates_args=())
 def pgd_linf_step(x: torch.Tensor, x0: torch.Tensor, grad: torch.Tensor, alpha: float, eps: float) -> torch.Tensor:
-    x, x0, grad = _cu(x), _cu(x0), _cu(grad)
-    if x.shape != x0.shape or x.shape != grad.shape:
-        raise RuntimeError("pgd_linf_step: shape mismatch")
-    out = torch.empty_like(x)
-    N.check(N.lib().dmh_pgd_linf_step(N.ptr(x), N.ptr(x0), N.ptr(grad), float(alpha), float(eps), N.ptr(out), x.numel(),
-                                      N.stream()))
-    return out
+    return ops.pgd_linf_step(x, x0, grad, alpha, eps)
 
 
 @pgd_linf_step.register_fake
@@ -356,14 +322,7 @@ def _(x0, x_best, x_new, table, stripes, state, eps):
 # ----------------------------------------------------------------------------------------------------------------- K5
 @custom_op("dmh::l0_compose", mutates_args=())
 def l0_compose(obj: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, l0_clip: float, finalize: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    obj, pos, neg = _cu(obj), _cu(pos), _cu(neg)
-    if obj.dim() != 4 or obj.shape[0] != 1 or obj.shape != pos.shape or obj.shape != neg.shape:
-        raise RuntimeError("l0_compose: obj/pos/neg must all be [1,C,H,W]")
-    adv = torch.empty_like(obj)
-    count = torch.zeros(1, device=obj.device, dtype=torch.int32)
-    N.check(N.lib().dmh_l0_compose_fwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), obj.shape[1], obj.shape[2] * obj.shape[3],
-                                       float(l0_clip), int(finalize), N.ptr(adv), N.ptr(count), N.stream()))
-    return adv, count
+    return ops.l0_compose_fwd_launch(_cu(obj), _cu(pos), _cu(neg), l0_clip, finalize)
 
 
 @l0_compose.register_fake
@@ -373,11 +332,7 @@ def _(obj, pos, neg, l0_clip, finalize):
 
 @custom_op("dmh::l0_compose_bwd", mutates_args=())
 def l0_compose_bwd(obj: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, g_adv: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    obj, pos, neg, g_adv = _cu(obj), _cu(pos), _cu(neg), _cu(g_adv)
-    g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
-    N.check(N.lib().dmh_l0_compose_bwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), N.ptr(g_adv), obj.shape[1], obj.shape[2] * obj.shape[3],
-                                       N.ptr(g_pos), N.ptr(g_neg), 0, N.stream()))
-    return g_pos, g_neg
+    return ops.l0_compose_bwd_launch(_cu(obj), _cu(pos), _cu(neg), _cu(g_adv))
 
 
 @l0_compose_bwd.register_fake
@@ -400,15 +355,7 @@ l0_compose.register_autograd(_l0c_backward, setup_context=_l0c_setup)
 
 @custom_op("dmh::l0_mask_cost", mutates_args=())
 def l0_mask_cost(pos: torch.Tensor, neg: torch.Tensor) -> torch.Tensor:
-    pos, neg = _cu(pos), _cu(neg)
-    if pos.dim() != 4 or pos.shape[0] != 1 or pos.shape != neg.shape:
-        raise RuntimeError("l0_mask_cost: pos/neg must be [1,C,H,W]")
-    lib = N.lib()
-    Cc, HW = pos.shape[1], pos.shape[2] * pos.shape[3]
-    part = torch.empty(lib.dmh_l0_mask_partials_size(HW), device=pos.device, dtype=torch.float32)
-    cost = torch.empty((), device=pos.device, dtype=torch.float32)
-    N.check(lib.dmh_l0_mask_cost_fwd(N.ptr(pos), N.ptr(neg), Cc, HW, N.ptr(part), N.ptr(cost), N.stream()))
-    return cost
+    return ops.l0_mask_cost_fwd_launch(_cu(pos), _cu(neg))
 
 
 @l0_mask_cost.register_fake
@@ -418,11 +365,7 @@ def _(pos, neg):
 
 @custom_op("dmh::l0_mask_cost_bwd", mutates_args=())
 def l0_mask_cost_bwd(pos: torch.Tensor, neg: torch.Tensor, g: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    pos, neg = _cu(pos), _cu(neg)
-    g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
-    N.check(N.lib().dmh_l0_mask_cost_bwd(N.ptr(pos), N.ptr(neg), pos.shape[1], pos.shape[2] * pos.shape[3],
-                                         N.ptr(_cu(g.to(torch.float32))), None, N.ptr(g_pos), N.ptr(g_neg), 0, N.stream()))
-    return g_pos, g_neg
+    return ops.l0_mask_cost_bwd_launch(_cu(pos), _cu(neg), g)
 
 
 @l0_mask_cost_bwd.register_fake
@@ -460,25 +403,7 @@ def photo_smooth_loss(target: torch.Tensor, sources: List[torch.Tensor], Ts: Lis
     if noise_mode not in (N.NOISE_NONE, N.NOISE_PHILOX):
         raise RuntimeError("dmh::photo_smooth_loss: noise_mode must be 0 (none) or 2 (Philox)")
     cfg = _loss_cfg(sources, disps, min_depth, max_depth, variant, automask, no_ssim, smooth_wt, noise_mode, seed, offset)
-    target, K, inv_K = _cu(target), _cu(K), _cu(inv_K)
-    sources, Ts, disps, colors = [_cu(t) for t in sources], [_cu(t) for t in Ts], [_cu(t) for t in disps], [_cu(t) for t in colors]
-    lib = N.lib()
-    B, _, H, W = target.shape
-    dev = target.device
-    NS = len(disps)
-    a = ops._photo_args(cfg, target, sources, Ts, K, inv_K, disps, ())
-    sm = ops._smooth_args(disps, colors)
-    sel = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
-    pp = torch.empty(lib.dmh_photo_partials_size(B, H, W, NS), device=dev, dtype=torch.float32)
-    sp = torch.empty(lib.dmh_smooth_partials_size(C.byref(sm)), device=dev, dtype=torch.float32)
-    fin = torch.empty(N.FIN_SIZE, device=dev, dtype=torch.float32)
-    sstats = torch.empty((NS, B, 2), device=dev, dtype=torch.float32)
-    st = N.stream()
-    N.check(lib.dmh_photo_loss_fwd(C.byref(a), N.ptr(sel), N.ptr_array([None] * NS), N.ptr(pp), st))
-    N.check(lib.dmh_smooth_loss_fwd(C.byref(sm), N.ptr(sp), st))
-    N.check(lib.dmh_loss_finalize(N.ptr(pp), N.ptr(sp), B, H, W, C.byref(sm), a.variant, cfg["smooth_wt"], N.ptr(fin),
-                                  N.ptr(sstats), st))
-    return fin, sel, sstats
+    return ops.photo_smooth_fwd_launch(cfg, _cu(target), _cul(sources), _cul(Ts), _cu(K), _cu(inv_K), _cul(disps), _cul(colors))[:3]
 
 
 @photo_smooth_loss.register_fake
@@ -495,19 +420,8 @@ def photo_smooth_loss_bwd(target: torch.Tensor, sources: List[torch.Tensor], Ts:
                           max_depth: float, variant: int, automask: bool, no_ssim: bool, smooth_wt: float, fin: torch.Tensor,
                           sel: torch.Tensor, sstats: torch.Tensor, g_fin: torch.Tensor) -> List[torch.Tensor]:
     cfg = _loss_cfg(sources, disps, min_depth, max_depth, variant, automask, no_ssim, smooth_wt, N.NOISE_NONE, 0, 0)
-    target, K, inv_K = _cu(target), _cu(K), _cu(inv_K)
-    sources, Ts, disps, colors = [_cu(t) for t in sources], [_cu(t) for t in Ts], [_cu(t) for t in disps], [_cu(t) for t in colors]
-    lib = N.lib()
-    a = ops._photo_args(cfg, target, sources, Ts, K, inv_K, disps, ())
-    sm = ops._smooth_args(disps, colors)
-    gvec = _cu(g_fin.to(torch.float32))
-    g_disp = [torch.empty_like(d) for d in disps]
-    stage = torch.empty(lib.dmh_photo_stage_size(C.byref(a)), device=target.device, dtype=torch.float32)
-    gp = N.ptr_array(g_disp)
-    st = N.stream()
-    N.check(lib.dmh_photo_loss_bwd(C.byref(a), N.ptr(_cu(sel)), N.ptr(gvec), N.ptr(_cu(fin)), N.ptr(stage), gp, st))
-    N.check(lib.dmh_smooth_loss_bwd(C.byref(sm), N.ptr(gvec), N.ptr(_cu(sstats)), cfg["smooth_wt"], gp, 1, st))
-    return g_disp
+    return ops.photo_smooth_bwd_launch(cfg, _cu(target), _cul(sources), _cul(Ts), _cu(K), _cu(inv_K), _cul(disps), _cul(colors), None,
+                                       _cu(fin), _cu(sel), _cu(sstats), g_fin, [False] * len(sources))[0]
 
 
 @photo_smooth_loss_bwd.register_fake
@@ -544,13 +458,7 @@ photo_smooth_loss.register_autograd(_psl_backward, setup_context=_psl_setup)
 @custom_op("dmh::ssim_map", mutates_args=())
 def ssim_map(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """clamp((1 - SSIM(x, y)) / 2, 0, 1) per channel with 3x3 reflection-padded means: MD2/layers.py:223-253."""
-    x, y = _cu(x), _cu(y)
-    if x.dim() != 4 or x.shape != y.shape:
-        raise RuntimeError("ssim_map: x and y must be [B,C,H,W] of the same shape")
-    B, Cc, H, W = x.shape
-    out = torch.empty_like(x)
-    N.check(N.lib().dmh_ssim_map(N.ptr(x), N.ptr(y), B * Cc, H, W, N.ptr(out), N.stream()))
-    return out
+    return ops.ssim_map_fwd_launch(_cu(x), _cu(y))
 
 
 @ssim_map.register_fake
@@ -560,13 +468,7 @@ def _(x, y):
 
 @custom_op("dmh::ssim_map_bwd", mutates_args=())
 def ssim_map_bwd(x: torch.Tensor, y: torch.Tensor, g_out: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    x, y, g_out = _cu(x), _cu(y), _cu(g_out)
-    B, Cc, H, W = x.shape
-    ws = torch.empty(5 * x.numel(), device=x.device, dtype=torch.float32)
-    g_x, g_y = torch.empty_like(x), torch.empty_like(y)
-    N.check(N.lib().dmh_ssim_map_bwd(N.ptr(x), N.ptr(y), N.ptr(g_out), B * Cc, H, W, N.ptr(ws), N.ptr(g_x), N.ptr(g_y),
-                                     N.stream()))
-    return g_x, g_y
+    return ops.ssim_map_bwd_launch(_cu(x), _cu(y), _cu(g_out))
 
 
 @ssim_map_bwd.register_fake
@@ -591,15 +493,7 @@ ssim_map.register_autograd(_ssim_backward, setup_context=_ssim_setup)
 def smooth_loss(disp: torch.Tensor, img: torch.Tensor) -> torch.Tensor:
     """mean(|d_x disp| exp(-mean_c |d_x img|)) + mean(|d_y disp| exp(-mean_c |d_y img|)): MD2/layers.py:207-220 on the
     disparity as given (the caller applies the mean normalisation of MD2/trainer.py:662-664)."""
-    disp, img = _cu(disp), _cu(img)
-    if disp.dim() != 4 or disp.shape[1] != 1 or img.dim() != 4 or img.shape[0] != disp.shape[0] or img.shape[2:] != disp.shape[2:]:
-        raise RuntimeError("smooth_loss: disp [B,1,H,W] and img [B,C,H,W] expected")
-    B, Cc, H, W = img.shape
-    lib = N.lib()
-    part = torch.empty(lib.dmh_edge_smooth_partials_size(B, H, W), device=disp.device, dtype=torch.float32)
-    out = torch.empty((), device=disp.device, dtype=torch.float32)
-    N.check(lib.dmh_edge_smooth(N.ptr(disp), N.ptr(img), B, Cc, H, W, N.ptr(part), N.ptr(out), N.stream()))
-    return out
+    return ops.edge_smooth_fwd_launch(_cu(disp), _cu(img))
 
 
 @smooth_loss.register_fake
@@ -609,12 +503,7 @@ def _(disp, img):
 
 @custom_op("dmh::smooth_loss_bwd", mutates_args=())
 def smooth_loss_bwd(disp: torch.Tensor, img: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
-    disp, img = _cu(disp), _cu(img)
-    B, Cc, H, W = img.shape
-    g_disp = torch.empty_like(disp)
-    N.check(N.lib().dmh_edge_smooth_bwd(N.ptr(disp), N.ptr(img), B, Cc, H, W, N.ptr(_cu(g.to(torch.float32))), N.ptr(g_disp),
-                                        N.stream()))
-    return g_disp
+    return ops.edge_smooth_bwd_launch(_cu(disp), _cu(img), g)
 
 
 @smooth_loss_bwd.register_fake

@@ -140,6 +140,66 @@ def _smooth_args(disps, colors):
     return a
 
 
+def photo_smooth_fwd_launch(cfg, target, sources, Ts, K, inv_K, disps, colors, noises=(), hint=None):
+    """K1 + K2 + finalise on checked, contiguous tensors: (fin [FIN_SIZE], packed selection bytes [B,H,W], smoothness statistics
+    [NS,B,2], to_opt: NS tensors [B,H,W] with cfg["want_to_opt"], else NS times None)."""
+    lib = N.lib()
+    B, _, H, W = target.shape
+    dev = target.device
+    NS = len(disps)
+    a = _photo_args(cfg, target, sources, Ts, K, inv_K, disps, noises, hint)
+    sm = _smooth_args(disps, colors)
+    sel = torch.empty((B, H, W), device=dev, dtype=torch.uint8)    # 2 bits per scale: 0 identity, 1+f frame f
+    to_opt = [torch.empty((B, H, W), device=dev, dtype=torch.float32) if cfg["want_to_opt"] else None
+              for _ in range(NS)]
+    pp = torch.empty(lib.dmh_photo_partials_size(B, H, W, NS), device=dev, dtype=torch.float32)
+    sp = torch.empty(lib.dmh_smooth_partials_size(C.byref(sm)), device=dev, dtype=torch.float32)
+    fin = torch.empty(N.FIN_SIZE, device=dev, dtype=torch.float32)
+    sstats = torch.empty((NS, B, 2), device=dev, dtype=torch.float32)
+    st = N.stream()
+    optp = N.ptr_array(to_opt)
+    N.check(_timed("photo_fwd", lambda: lib.dmh_photo_loss_fwd(C.byref(a), N.ptr(sel), optp, N.ptr(pp), st)))
+    N.check(lib.dmh_smooth_loss_fwd(C.byref(sm), N.ptr(sp), st))
+    N.check(lib.dmh_loss_finalize(N.ptr(pp), N.ptr(sp), B, H, W, C.byref(sm), a.variant, cfg["smooth_wt"],
+                                  N.ptr(fin), N.ptr(sstats), st))
+    return fin, sel, sstats, to_opt
+
+
+def photo_smooth_bwd_launch(cfg, target, sources, Ts, K, inv_K, disps, colors, hint, fin, sel, sstats, g_fin, want_pose):
+    """The backward of photo_smooth_fwd_launch: (g_disp: one per scale, g_T: per source frame [B,4,4] where ``want_pose[f]``,
+    else None)."""
+    lib = N.lib()
+    dev = target.device
+    F, NS = len(sources), len(disps)
+    gvec = _c(g_fin.to(torch.float32))
+    a = _photo_args(dict(cfg, noise_mode=N.NOISE_NONE), target, sources, Ts, K, inv_K, disps, (), hint)
+    sm = _smooth_args(disps, colors)
+    st = N.stream()
+    g_disp = [torch.empty_like(d) for d in disps]
+    stage = torch.empty(lib.dmh_photo_stage_size(C.byref(a)), device=dev, dtype=torch.float32)
+    gp = N.ptr_array(g_disp)
+    g_T = [None] * F
+    if any(want_pose):
+        # monocular frames: K1's backward also leaves twelve sums per (scale, strip, frame), from which
+        # d loss / d P_f (P_f = (K T_f)[:3,:]) and d loss / d T_f = K[:3,:]^T dP_f follow (include/dmh_hip.h)
+        B = target.shape[0]
+        part = torch.empty(lib.dmh_photo_pose_partials_size(C.byref(a)), device=dev, dtype=torch.float32)
+        N.check(_timed("photo_bwd", lambda: lib.dmh_photo_loss_bwd_pose(C.byref(a), N.ptr(sel), N.ptr(gvec), N.ptr(fin),
+                                                                       N.ptr(stage), gp, N.ptr(part), st)))
+        sums = part.view(NS, B, -1, F, 3, 4).double().sum((0, 2))               # [B, F, 3, (S_i0, S_i1, S_i2, s_i)]
+        Kd, iKd = K.double(), inv_K.double()
+        for f in range(F):
+            if not want_pose[f]:
+                continue
+            dP = torch.cat([torch.matmul(sums[:, f, :, :3], iKd[:, :3, :3].transpose(1, 2)), sums[:, f, :, 3:4]], 2)
+            g_T[f] = torch.matmul(Kd[:, :3, :].transpose(1, 2), dP).to(Ts[f].dtype)     # [B, 4, 4]
+    else:
+        N.check(_timed("photo_bwd", lambda: lib.dmh_photo_loss_bwd(C.byref(a), N.ptr(sel), N.ptr(gvec), N.ptr(fin),
+                                                                  N.ptr(stage), gp, st)))
+    N.check(lib.dmh_smooth_loss_bwd(C.byref(sm), N.ptr(gvec), N.ptr(sstats), cfg["smooth_wt"], gp, 1, st))
+    return g_disp, g_T
+
+
 class _PhotoSmoothLoss(torch.autograd.Function):
     """K1 + K2 + finalise.  Tensor args: target, K, inv_K, then F sources, F Ts, NS colors,
     (NS noises), NS disps."""
@@ -156,24 +216,7 @@ class _PhotoSmoothLoss(torch.autograd.Function):
             pos += NS
         disps = rest[pos:pos + NS]
         hint = tuple(rest[pos + NS:pos + NS + 2]) if cfg["hints"] else None
-        lib = N.lib()
-        B, _, H, W = target.shape
-        dev = target.device
-        a = _photo_args(cfg, target, sources, Ts, K, inv_K, disps, noises, hint)
-        sm = _smooth_args(disps, colors)
-        sel = torch.empty((B, H, W), device=dev, dtype=torch.uint8)    # 2 bits per scale: 0 identity, 1+f frame f
-        to_opt = [torch.empty((B, H, W), device=dev, dtype=torch.float32) if cfg["want_to_opt"] else None
-                  for _ in range(NS)]
-        pp = torch.empty(lib.dmh_photo_partials_size(B, H, W, NS), device=dev, dtype=torch.float32)
-        sp = torch.empty(lib.dmh_smooth_partials_size(C.byref(sm)), device=dev, dtype=torch.float32)
-        fin = torch.empty(N.FIN_SIZE, device=dev, dtype=torch.float32)
-        sstats = torch.empty((NS, B, 2), device=dev, dtype=torch.float32)
-        st = N.stream()
-        optp = N.ptr_array(to_opt)
-        N.check(_timed("photo_fwd", lambda: lib.dmh_photo_loss_fwd(C.byref(a), N.ptr(sel), optp, N.ptr(pp), st)))
-        N.check(lib.dmh_smooth_loss_fwd(C.byref(sm), N.ptr(sp), st))
-        N.check(lib.dmh_loss_finalize(N.ptr(pp), N.ptr(sp), B, H, W, C.byref(sm), a.variant, cfg["smooth_wt"],
-                                      N.ptr(fin), N.ptr(sstats), st))
+        fin, sel, sstats, to_opt = photo_smooth_fwd_launch(cfg, target, sources, Ts, K, inv_K, disps, colors, noises, hint)
         ctx.cfg = cfg
         ctx.save_for_backward(target, K, inv_K, fin, sstats, sel, *sources, *Ts, *colors, *disps, *(hint or ()))
         outs = [fin, sel] + [t for t in to_opt if t is not None]
@@ -190,36 +233,9 @@ class _PhotoSmoothLoss(torch.autograd.Function):
         colors = sv[6 + 2 * F:6 + 2 * F + NS]
         disps = sv[6 + 2 * F + NS:6 + 2 * F + 2 * NS]
         hint = tuple(sv[6 + 2 * F + 2 * NS:6 + 2 * F + 2 * NS + 2]) if cfg["hints"] else None
-        lib = N.lib()
-        dev = target.device
-        gvec = _c(g_fin.to(torch.float32))
-        cfg_b = dict(cfg, noise_mode=N.NOISE_NONE)
-        a = _photo_args(cfg_b, target, sources, Ts, K, inv_K, disps, (), hint)
-        sm = _smooth_args(disps, colors)
-        st = N.stream()
-        g_disp = [torch.empty_like(d) for d in disps]
-        stage = torch.empty(lib.dmh_photo_stage_size(C.byref(a)), device=dev, dtype=torch.float32)
-        gp = N.ptr_array(g_disp)
         want_pose = [bool(ctx.needs_input_grad[4 + F + f]) for f in range(F)]      # cam_T_cam of source frame f
-        g_T = [None] * F
-        if any(want_pose):
-            # monocular frames: K1's backward also leaves twelve sums per (scale, strip, frame), from which
-            # d loss / d P_f (P_f = (K T_f)[:3,:]) and d loss / d T_f = K[:3,:]^T dP_f follow (include/dmh_hip.h)
-            B = target.shape[0]
-            part = torch.empty(lib.dmh_photo_pose_partials_size(C.byref(a)), device=dev, dtype=torch.float32)
-            N.check(_timed("photo_bwd", lambda: lib.dmh_photo_loss_bwd_pose(C.byref(a), N.ptr(sel), N.ptr(gvec), N.ptr(fin),
-                                                                           N.ptr(stage), gp, N.ptr(part), st)))
-            sums = part.view(NS, B, -1, F, 3, 4).double().sum((0, 2))               # [B, F, 3, (S_i0, S_i1, S_i2, s_i)]
-            Kd, iKd = K.double(), inv_K.double()
-            for f in range(F):
-                if not want_pose[f]:
-                    continue
-                dP = torch.cat([torch.matmul(sums[:, f, :, :3], iKd[:, :3, :3].transpose(1, 2)), sums[:, f, :, 3:4]], 2)
-                g_T[f] = torch.matmul(Kd[:, :3, :].transpose(1, 2), dP).to(Ts[f].dtype)     # [B, 4, 4]
-        else:
-            N.check(_timed("photo_bwd", lambda: lib.dmh_photo_loss_bwd(C.byref(a), N.ptr(sel), N.ptr(gvec), N.ptr(fin),
-                                                                      N.ptr(stage), gp, st)))
-        N.check(lib.dmh_smooth_loss_bwd(C.byref(sm), N.ptr(gvec), N.ptr(sstats), cfg["smooth_wt"], gp, 1, st))
+        g_disp, g_T = photo_smooth_bwd_launch(cfg, target, sources, Ts, K, inv_K, disps, colors, hint, fin, sel, sstats, g_fin,
+                                              want_pose)
         n_tail = NS + (NS if cfg["noise_mode"] == N.NOISE_TENSOR else 0)
         return ((None, None, None, None) + (None,) * F + tuple(g_T) + (None,) * n_tail + tuple(g_disp)
                 + ((None, None) if cfg["hints"] else ()))
@@ -340,6 +356,47 @@ def warp_view(source, disp, K, inv_K, T, H, W, min_depth=0.1, max_depth=100.0):
                            float(max_depth))
 
 
+def ssim_map_fwd_launch(x, y):
+    """clamp((1 - SSIM(x, y)) / 2, 0, 1) per channel with 3x3 reflection-padded means (MD2/layers.py:223-253): K1's window sums
+    stand-alone, on contiguous tensors."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise RuntimeError("ssim_map: x and y must be [B,C,H,W] of the same shape")
+    B, Cc, H, W = x.shape
+    out = torch.empty_like(x)
+    N.check(N.lib().dmh_ssim_map(N.ptr(x), N.ptr(y), B * Cc, H, W, N.ptr(out), N.stream()))
+    return out
+
+
+def ssim_map_bwd_launch(x, y, g_out):
+    B, Cc, H, W = x.shape
+    ws = torch.empty(5 * x.numel(), device=x.device, dtype=torch.float32)
+    g_x, g_y = torch.empty_like(x), torch.empty_like(y)
+    N.check(N.lib().dmh_ssim_map_bwd(N.ptr(x), N.ptr(y), N.ptr(g_out), B * Cc, H, W, N.ptr(ws), N.ptr(g_x), N.ptr(g_y),
+                                     N.stream()))
+    return g_x, g_y
+
+
+def edge_smooth_fwd_launch(disp, img):
+    """mean(|d_x disp| exp(-mean_c |d_x img|)) + mean(|d_y disp| exp(-mean_c |d_y img|)) (MD2/layers.py:207-220): K2 on one scale,
+    on contiguous tensors."""
+    if disp.dim() != 4 or disp.shape[1] != 1 or img.dim() != 4 or img.shape[0] != disp.shape[0] or img.shape[2:] != disp.shape[2:]:
+        raise RuntimeError("smooth_loss: disp [B,1,H,W] and img [B,C,H,W] expected")
+    B, Cc, H, W = img.shape
+    lib = N.lib()
+    part = torch.empty(lib.dmh_edge_smooth_partials_size(B, H, W), device=disp.device, dtype=torch.float32)
+    out = torch.empty((), device=disp.device, dtype=torch.float32)
+    N.check(lib.dmh_edge_smooth(N.ptr(disp), N.ptr(img), B, Cc, H, W, N.ptr(part), N.ptr(out), N.stream()))
+    return out
+
+
+def edge_smooth_bwd_launch(disp, img, g):
+    B, Cc, H, W = img.shape
+    g_disp = torch.empty_like(disp)
+    N.check(N.lib().dmh_edge_smooth_bwd(N.ptr(disp), N.ptr(img), B, Cc, H, W, N.ptr(_c(g.to(torch.float32))), N.ptr(g_disp),
+                                        N.stream()))
+    return g_disp
+
+
 def _paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode=N.PASTE_COMPOSITE, flip=None, scene_index=None):
     a = N.PasteArgs()
     if flip is not None:
@@ -367,18 +424,32 @@ def _paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode=N.PASTE_
     return a
 
 
+def eot_paste_fwd_launch(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode=N.PASTE_COMPOSITE, flip=None, scene_index=None):
+    """K3 on contiguous tensors: (adv [N,3,OH,OW], mask_out [N,1,OH,OW])."""
+    a = _paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode, flip, scene_index)
+    adv = torch.empty((a.N, 3, OH, OW), device=scene.device, dtype=torch.float32)
+    mask_out = torch.empty((a.N, 1, OH, OW), device=scene.device, dtype=torch.float32)
+    # algorithmic bytes (SURVEY 8d): the scene read once (one copy when it is broadcast) + patch and mask + the two outputs
+    n_scene = scene.numel() if scene_index is None else a.N * 3 * a.SH * a.SW      # frames read, not the pool's size
+    nb = 4 * (n_scene + patch.numel() + pmask.numel() + adv.numel() + mask_out.numel()) if mode == N.PASTE_COMPOSITE \
+        else 4 * (patch.numel() + pmask.numel() + adv.numel() + mask_out.numel())
+    N.check(_timed("paste_fwd", lambda: N.lib().dmh_eot_paste_fwd(C.byref(a), N.ptr(adv), N.ptr(mask_out), N.stream()), nb))
+    return adv, mask_out
+
+
+def eot_paste_bwd_launch(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode, flip, scene_index, g_adv):
+    """K3's adjoint: the gradient w.r.t. ``patch`` for ``g_adv`` (contiguous)."""
+    a = _paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode, flip, scene_index)
+    g_patch = torch.empty_like(patch)
+    N.check(_timed("paste_bwd", lambda: N.lib().dmh_eot_paste_bwd(C.byref(a), N.ptr(g_adv), N.ptr(g_patch), N.stream()),
+                   4 * (g_adv.numel() + g_patch.numel())))
+    return g_patch
+
+
 class _EotPaste(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode, flip=None, scene_index=None):
-        lib = N.lib()
-        a = _paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode, flip, scene_index)
-        adv = torch.empty((a.N, 3, OH, OW), device=scene.device, dtype=torch.float32)
-        mask_out = torch.empty((a.N, 1, OH, OW), device=scene.device, dtype=torch.float32)
-        # algorithmic bytes: the scene read once (one copy when it is broadcast) + patch and mask + the two outputs
-        n_scene = scene.numel() if scene_index is None else a.N * 3 * a.SH * a.SW      # frames read, not the pool's size
-        nb = 4 * (n_scene + patch.numel() + pmask.numel() + adv.numel() + mask_out.numel()) if mode == N.PASTE_COMPOSITE \
-            else 4 * (patch.numel() + pmask.numel() + adv.numel() + mask_out.numel())
-        N.check(_timed("paste_fwd", lambda: lib.dmh_eot_paste_fwd(C.byref(a), N.ptr(adv), N.ptr(mask_out), N.stream()), nb))
+        adv, mask_out = eot_paste_fwd_launch(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode, flip, scene_index)
         ctx.save_for_backward(scene, patch, pmask, coeffs)
         ctx.geo = (l_pad, t_pad, OH, OW, mode)
         ctx.flip = flip
@@ -389,13 +460,7 @@ class _EotPaste(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_adv, g_mask):
         scene, patch, pmask, coeffs = ctx.saved_tensors
-        l_pad, t_pad, OH, OW, mode = ctx.geo
-        lib = N.lib()
-        a = _paste_args(scene, patch, pmask, coeffs, l_pad, t_pad, OH, OW, mode, ctx.flip, ctx.scene_index)
-        g_patch = torch.empty_like(patch)
-        g_adv = _c(g_adv)
-        N.check(_timed("paste_bwd", lambda: lib.dmh_eot_paste_bwd(C.byref(a), N.ptr(g_adv), N.ptr(g_patch), N.stream()),
-                       4 * (g_adv.numel() + g_patch.numel())))
+        g_patch = eot_paste_bwd_launch(scene, patch, pmask, coeffs, *ctx.geo, ctx.flip, ctx.scene_index, _c(g_adv))
         return None, g_patch, None, None, None, None, None, None, None, None, None
 
 
@@ -418,27 +483,36 @@ def perspective_warp(patch, pmask, coeffs, l_pad, t_pad, frame_size):
                            N.PASTE_WARP_ONLY)
 
 
+def masked_sq_mean_fwd_launch(disp, mask):
+    """K6 on contiguous tensors (``mask`` may be None): the cost, a float32 scalar on the device."""
+    lib = N.lib()
+    n = disp.numel()
+    if mask is not None and mask.numel() != n:
+        raise RuntimeError("masked_sq_mean: mask and disp sizes differ")
+    part = torch.empty(lib.dmh_sq_mean_partials_size(n), device=disp.device, dtype=torch.float32)
+    cost = torch.empty((), device=disp.device, dtype=torch.float32)
+    N.check(lib.dmh_masked_sq_mean_fwd(N.ptr(disp), N.ptr(mask), n, N.ptr(part), N.ptr(cost), N.stream()))
+    return cost
+
+
+def masked_sq_mean_bwd_launch(disp, mask, g):
+    g_disp = torch.empty_like(disp)
+    N.check(N.lib().dmh_masked_sq_mean_bwd(N.ptr(disp), N.ptr(mask), disp.numel(), N.ptr(_c(g.to(torch.float32))),
+                                           N.ptr(g_disp), N.stream()))
+    return g_disp
+
+
 class _MaskedSqMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, disp, mask):
-        lib = N.lib()
-        n = disp.numel()
-        if mask is not None and mask.numel() != n:
-            raise RuntimeError("masked_sq_mean: mask and disp sizes differ")
-        part = torch.empty(lib.dmh_sq_mean_partials_size(n), device=disp.device, dtype=torch.float32)
-        cost = torch.empty((), device=disp.device, dtype=torch.float32)
-        N.check(lib.dmh_masked_sq_mean_fwd(N.ptr(disp), N.ptr(mask), n, N.ptr(part), N.ptr(cost), N.stream()))
+        cost = masked_sq_mean_fwd_launch(disp, mask)
         ctx.save_for_backward(disp, mask)
         return cost
 
     @staticmethod
     def backward(ctx, g):
         disp, mask = ctx.saved_tensors
-        lib = N.lib()
-        g_disp = torch.empty_like(disp)
-        N.check(lib.dmh_masked_sq_mean_bwd(N.ptr(disp), N.ptr(mask), disp.numel(), N.ptr(_c(g.to(torch.float32))),
-                                           N.ptr(g_disp), N.stream()))
-        return g_disp, None
+        return masked_sq_mean_bwd_launch(disp, mask, g), None
 
 
 def masked_sq_mean(disp, mask=None):
@@ -466,28 +540,38 @@ def _gt_depth_operands(disp, disp_gt, objmask, objdepth):
     return disp, disp_gt, objmask, int(objmask.stride(0)), objdepth, B, H * W
 
 
+def gt_depth_mse_fwd_launch(disp, disp_gt, objmask, bstride, objdepth, B, HW, min_depth, max_depth):
+    """K6b on the output of _gt_depth_operands: the cost, a float32 scalar on the device."""
+    lib = N.lib()
+    part = torch.empty(lib.dmh_sq_mean_partials_size(B * HW), device=disp.device, dtype=torch.float32)
+    cost = torch.empty((), device=disp.device, dtype=torch.float32)
+    # channel 0 of the mask is read in place through its batch stride (layout validated by _gt_depth_operands)
+    N.check(lib.dmh_gt_depth_mse_fwd(N.ptr(disp), N.ptr(disp_gt), C.c_void_p(objmask.data_ptr()), bstride, N.ptr(objdepth), B, HW,
+                                     float(min_depth), float(max_depth), N.ptr(part), N.ptr(cost), N.stream()))
+    return cost
+
+
+def gt_depth_mse_bwd_launch(disp, disp_gt, objmask, bstride, objdepth, B, HW, min_depth, max_depth, g):
+    g_disp = torch.empty_like(disp)
+    N.check(N.lib().dmh_gt_depth_mse_bwd(N.ptr(disp), N.ptr(disp_gt), C.c_void_p(objmask.data_ptr()), bstride, N.ptr(objdepth), B, HW,
+                                         float(min_depth), float(max_depth), N.ptr(_c(g.to(torch.float32))), N.ptr(g_disp),
+                                         N.stream()))
+    return g_disp
+
+
 class _GtDepthMse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, disp, disp_gt, objmask, objdepth, min_depth, max_depth):
-        lib = N.lib()
         disp, disp_gt, objmask, bstride, objdepth, B, HW = _gt_depth_operands(disp, disp_gt, objmask, objdepth)
-        part = torch.empty(lib.dmh_sq_mean_partials_size(B * HW), device=disp.device, dtype=torch.float32)
-        cost = torch.empty((), device=disp.device, dtype=torch.float32)
-        # channel 0 of the mask is read in place through its batch stride (layout validated by _gt_depth_operands)
-        N.check(lib.dmh_gt_depth_mse_fwd(N.ptr(disp), N.ptr(disp_gt), C.c_void_p(objmask.data_ptr()), bstride, N.ptr(objdepth), B, HW,
-                                         float(min_depth), float(max_depth), N.ptr(part), N.ptr(cost), N.stream()))
         ctx.save_for_backward(disp, disp_gt, objmask, objdepth)
         ctx.geo = (bstride, B, HW, float(min_depth), float(max_depth))
-        return cost
+        return gt_depth_mse_fwd_launch(disp, disp_gt, objmask, bstride, objdepth, B, HW, min_depth, max_depth)
 
     @staticmethod
     def backward(ctx, g):
         disp, disp_gt, objmask, objdepth = ctx.saved_tensors
         bstride, B, HW, min_depth, max_depth = ctx.geo
-        g_disp = torch.empty_like(disp)
-        N.check(N.lib().dmh_gt_depth_mse_bwd(N.ptr(disp), N.ptr(disp_gt), C.c_void_p(objmask.data_ptr()), bstride, N.ptr(objdepth), B, HW,
-                                             min_depth, max_depth, N.ptr(_c(g.to(torch.float32))), N.ptr(g_disp), N.stream()))
-        return g_disp, None, None, None, None, None
+        return gt_depth_mse_bwd_launch(disp, disp_gt, objmask, bstride, objdepth, B, HW, min_depth, max_depth, g), None, None, None, None, None
 
 
 def gt_depth_mse(disp, disp_gt, objmask, objdepth, min_depth=0.1, max_depth=100.0):
@@ -904,15 +988,28 @@ def square_host(x0, x_best, x_new, table, stripes, q, accept, eps):
     return x_best, x_new
 
 
+def l0_compose_fwd_launch(obj, pos, neg, l0_clip, finalize):
+    """K5 on contiguous tensors: (adv, count int32 [1])."""
+    if obj.dim() != 4 or obj.shape[0] != 1 or obj.shape != pos.shape or obj.shape != neg.shape:
+        raise RuntimeError("l0_compose: obj/pos/neg must all be [1,C,H,W]")
+    adv = torch.empty_like(obj)
+    count = torch.zeros(1, device=obj.device, dtype=torch.int32)
+    N.check(N.lib().dmh_l0_compose_fwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), obj.shape[1], obj.shape[2] * obj.shape[3],
+                                       float(l0_clip), int(finalize), N.ptr(adv), N.ptr(count), N.stream()))
+    return adv, count
+
+
+def l0_compose_bwd_launch(obj, pos, neg, g_adv):
+    g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
+    N.check(N.lib().dmh_l0_compose_bwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), N.ptr(g_adv), obj.shape[1], obj.shape[2] * obj.shape[3],
+                                       N.ptr(g_pos), N.ptr(g_neg), 0, N.stream()))
+    return g_pos, g_neg
+
+
 class _L0Compose(torch.autograd.Function):
     @staticmethod
     def forward(ctx, obj, pos, neg, l0_clip, finalize):
-        lib = N.lib()
-        Cc, HW = obj.shape[1], obj.shape[2] * obj.shape[3]
-        adv = torch.empty_like(obj)
-        count = torch.zeros(1, device=obj.device, dtype=torch.int32)
-        N.check(lib.dmh_l0_compose_fwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), Cc, HW, l0_clip, int(finalize),
-                                       N.ptr(adv), N.ptr(count), N.stream()))
+        adv, count = l0_compose_fwd_launch(obj, pos, neg, l0_clip, finalize)
         ctx.save_for_backward(obj, pos, neg)
         ctx.mark_non_differentiable(count)
         return adv, count
@@ -920,48 +1017,47 @@ class _L0Compose(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_adv, g_count):
         obj, pos, neg = ctx.saved_tensors
-        lib = N.lib()
-        Cc, HW = obj.shape[1], obj.shape[2] * obj.shape[3]
-        g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
-        N.check(lib.dmh_l0_compose_bwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), N.ptr(_c(g_adv)), Cc, HW, N.ptr(g_pos),
-                                       N.ptr(g_neg), 0, N.stream()))
+        g_pos, g_neg = l0_compose_bwd_launch(obj, pos, neg, _c(g_adv))
         return None, g_pos, g_neg, None, None
 
 
 def l0_compose(obj, pos, neg, l0_clip=1.0 / 255.0, finalize=False):
     """adv = clamp(obj + clamp(pos,0,1) - clamp(neg,0,1), 0, 1) and the L0 count of the thresholded
     pattern (phy_obj_atk_l0.py:94-99, 43-52; finalize=True applies :143-150).  Returns (adv, count[int32,1])."""
-    if obj.dim() != 4 or obj.shape[0] != 1 or obj.shape != pos.shape or obj.shape != neg.shape:
-        raise RuntimeError("l0_compose: obj/pos/neg must all be [1,C,H,W]")
     return _L0Compose.apply(_c(obj), _c(pos), _c(neg), float(l0_clip), bool(finalize))
+
+
+def l0_mask_cost_fwd_launch(pos, neg):
+    if pos.dim() != 4 or pos.shape[0] != 1 or pos.shape != neg.shape:
+        raise RuntimeError("l0_mask_cost: pos/neg must be [1,C,H,W]")
+    lib = N.lib()
+    Cc, HW = pos.shape[1], pos.shape[2] * pos.shape[3]
+    part = torch.empty(lib.dmh_l0_mask_partials_size(HW), device=pos.device, dtype=torch.float32)
+    cost = torch.empty((), device=pos.device, dtype=torch.float32)
+    N.check(lib.dmh_l0_mask_cost_fwd(N.ptr(pos), N.ptr(neg), Cc, HW, N.ptr(part), N.ptr(cost), N.stream()))
+    return cost
+
+
+def l0_mask_cost_bwd_launch(pos, neg, g):
+    g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
+    N.check(N.lib().dmh_l0_mask_cost_bwd(N.ptr(pos), N.ptr(neg), pos.shape[1], pos.shape[2] * pos.shape[3],
+                                         N.ptr(_c(g.to(torch.float32))), None, N.ptr(g_pos), N.ptr(g_neg), 0, N.stream()))
+    return g_pos, g_neg
 
 
 class _L0MaskCost(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, neg):
-        lib = N.lib()
-        Cc, HW = pos.shape[1], pos.shape[2] * pos.shape[3]
-        part = torch.empty(lib.dmh_l0_mask_partials_size(HW), device=pos.device, dtype=torch.float32)
-        cost = torch.empty((), device=pos.device, dtype=torch.float32)
-        N.check(lib.dmh_l0_mask_cost_fwd(N.ptr(pos), N.ptr(neg), Cc, HW, N.ptr(part), N.ptr(cost), N.stream()))
         ctx.save_for_backward(pos, neg)
-        return cost
+        return l0_mask_cost_fwd_launch(pos, neg)
 
     @staticmethod
     def backward(ctx, g):
-        pos, neg = ctx.saved_tensors
-        lib = N.lib()
-        Cc, HW = pos.shape[1], pos.shape[2] * pos.shape[3]
-        g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
-        N.check(lib.dmh_l0_mask_cost_bwd(N.ptr(pos), N.ptr(neg), Cc, HW, N.ptr(_c(g.to(torch.float32))), None,
-                                         N.ptr(g_pos), N.ptr(g_neg), 0, N.stream()))
-        return g_pos, g_neg
+        return l0_mask_cost_bwd_launch(*ctx.saved_tensors, g)
 
 
 def l0_mask_cost(pos, neg):
     """mean(max_c(tanh(pos/10)/(2-1e-7)+0.5)) + same for neg (phy_obj_atk_l0.py:130-132)."""
-    if pos.dim() != 4 or pos.shape[0] != 1 or pos.shape != neg.shape:
-        raise RuntimeError("l0_mask_cost: pos/neg must be [1,C,H,W]")
     return _L0MaskCost.apply(_c(pos), _c(neg))
 
 
@@ -3244,12 +3340,68 @@ def cost_volume(current_feats, lookup_feats, poses, K, invK, depth_bins, set_mis
     return cost_volume_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max, into, volume=into is None)
 
 
+# ------------------------------------------------------------------------------------ the loader operators (K31, K32, K34)
+class _UploadCache(object):
+    """The last ``cap`` sets of small tables a loader operator has uploaded, by key, so that a repeated batch shape launches with
+    the same device buffers and no copy.  An entry keeps the event of its upload -- a hit on another stream a moment later waits
+    for it -- and the pinned host copies, which live as long as the upload may.  A key a captured graph has launched with is
+    ``held``: a replay reads its buffers, so it is never evicted.  ``what``: the error a miss raises inside a capture."""
+
+    def __init__(self, cap, what):
+        self.cap, self.what, self.entries, self.held = cap, what, OrderedDict(), set()
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __contains__(self, key):
+        return key in self.entries
+
+    def get(self, key, device, make):
+        """(device tensors, payload) of ``key``; at a miss ``make()`` gives (host tensors, payload): the tensors are pinned and
+        uploaded without a wait, the payload (host values that go with them) is kept as it is."""
+        hit = self.entries.get(key)
+        if hit is not None:
+            self.entries.move_to_end(key)
+            if torch.cuda.is_current_stream_capturing():
+                self.held.add(key)
+            elif not hit[1].query():
+                torch.cuda.current_stream(device).wait_event(hit[1])        # uploaded on another stream a moment ago
+            return hit[0], hit[3]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(self.what)
+        host, payload = make()
+        host = [h.pin_memory() for h in host]
+        on_device = [h.to(device, non_blocking=True) for h in host]
+        uploaded = torch.cuda.Event()
+        uploaded.record(torch.cuda.current_stream(device))
+        self.entries[key] = (on_device, uploaded, host, payload)
+        for old in [k for k in self.entries if k not in self.held][:max(0, len(self.entries) - self.cap)]:
+            del self.entries[old]
+        return on_device, payload
+
+
+def _flip_operand(name, flip, n, dev):
+    """The per-item ``flip`` of a loader operator as the kernel reads it: None, or a contiguous int32 tensor of ``n`` entries on
+    ``dev`` (a host sequence of bools is uploaded from pinned memory)."""
+    if flip is None:
+        return None
+    if not torch.is_tensor(flip):
+        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    if flip.dtype != torch.int32 or flip.numel() != n or flip.device != dev:
+        raise RuntimeError("%s: flip must be an int32 tensor of %d entries on %s" % (name, n, dev))
+    return _c(flip)
+
+
 # ----------------------------------------------------------------------------------------------------------------- K31
 PIL_FILTERS = {"lanczos": (N.PIL_LANCZOS, 3.0), "bilinear": (N.PIL_BILINEAR, 1.0)}      # name -> (PIL's number, support)
 PIL_PRECISION_BITS = 22
+PIL_DESC_CACHE = 64         # descriptor sets kept per process (a few hundred bytes each); the tables themselves are never repeated
 PilLevel = namedtuple("PilLevel", ["u8", "f32"])
 _pil_axis_cache = {}
-_pil_device_cache = OrderedDict()      # (device, sizes, out, filter) -> descriptors on the device; bounded, see PIL_DESC_CACHE
+# (device, sizes, out, filter) -> descriptors on the device
+_pil_device_cache = _UploadCache(PIL_DESC_CACHE, "pil_resize: the first call with these source sizes uploads their descriptors; "
+                                                 "make it once before capturing a graph")
+_pil_graph_keys = _pil_device_cache.held
 
 
 def _pil_filter(filter):
@@ -3356,9 +3508,6 @@ def pil_resize_host(img, out_size, filter="lanczos", flip=False, sums=None):
     return np.ascontiguousarray(img)
 
 
-PIL_DESC_CACHE = 64         # descriptor sets kept per process (a few hundred bytes each); the tables themselves are never repeated
-
-
 class _PilArena(object):
     """The axis tables of one device: one int32 tensor that holds every distinct (in, out, filter) table once, at a word offset
     that never changes.  KITTI raw has about five frame sizes, so the arena stops growing after the first batches; when a new
@@ -3404,48 +3553,29 @@ class _PilArena(object):
 
 
 _pil_arenas = {}
-_pil_graph_keys = set()     # descriptor sets a captured graph has launched with: a replay reads them, so they are never evicted
 
 
 def _pil_tables_device(device, sizes, oh, ow, number, filter):
     """(tables int32 [words], desc int32 [N, 8], lds_rows) on ``device`` for a batch whose images have the source sizes
     ``sizes`` (a tuple of (h, w)).  The tables live once per distinct (in, out, filter) in the device's arena; what depends on
-    the batch is the descriptor set alone (32 bytes per image), uploaded from pinned memory without a wait.  The last
-    PIL_DESC_CACHE descriptor sets are kept, with the event of their upload, so that a repeated batch shape -- a captured graph's,
-    a pyramid's coarser levels -- launches with the same device buffer and no copy."""
+    the batch is the descriptor set alone (32 bytes per image), kept in ``_pil_device_cache``: a repeated batch shape -- a
+    captured graph's, a pyramid's coarser levels -- launches with the same device buffer and no copy."""
     arena = _pil_arenas.get(str(device))
     if arena is None:
         arena = _pil_arenas[str(device)] = _PilArena(device)
-    key = (str(device), sizes, oh, ow, number)
-    hit = _pil_device_cache.get(key)
-    if hit is not None:
-        _pil_device_cache.move_to_end(key)
-        desc_d, lds_rows, uploaded, _ = hit
-        if torch.cuda.is_current_stream_capturing():
-            _pil_graph_keys.add(key)
-        elif not uploaded.query():
-            torch.cuda.current_stream(device).wait_event(uploaded)      # uploaded on another stream a moment ago
-        return arena.sync(), desc_d, lds_rows
-    desc, lds_rows = np.zeros((len(sizes), 8), dtype=np.int32), 1
-    for i, (h, w) in enumerate(sizes):
-        (ho, hk), (vo, vk) = arena.place(w, ow, number, filter), arena.place(h, oh, number, filter)
-        desc[i, :6] = (h, w, ho, hk, vo, vk)
-        lds_rows = max(lds_rows, arena.rows(h, oh, filter, number))
-    if lds_rows * ow > 65536:
-        raise RuntimeError("pil_resize: %d source rows of %d output columns per tile exceed the 64 KiB LDS tile; resize in two "
-                           "steps" % (lds_rows, ow))
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("pil_resize: the first call with these source sizes uploads their descriptors; make it once before "
-                           "capturing a graph")
-    tables = arena.sync()
-    host = torch.from_numpy(desc.reshape(-1)).pin_memory()
-    desc_d = host.to(device, non_blocking=True).view(-1, 8)
-    uploaded = torch.cuda.Event()
-    uploaded.record(torch.cuda.current_stream(device))
-    _pil_device_cache[key] = (desc_d, lds_rows, uploaded, host)     # the pinned copy lives as long as the upload may
-    for old in [k for k in _pil_device_cache if k not in _pil_graph_keys][:max(0, len(_pil_device_cache) - PIL_DESC_CACHE)]:
-        del _pil_device_cache[old]
-    return tables, desc_d, lds_rows
+
+    def make():
+        desc, lds_rows = np.zeros((len(sizes), 8), dtype=np.int32), 1
+        for i, (h, w) in enumerate(sizes):
+            (ho, hk), (vo, vk) = arena.place(w, ow, number, filter), arena.place(h, oh, number, filter)
+            desc[i, :6] = (h, w, ho, hk, vo, vk)
+            lds_rows = max(lds_rows, arena.rows(h, oh, filter, number))
+        if lds_rows * ow > 65536:
+            raise RuntimeError("pil_resize: %d source rows of %d output columns per tile exceed the 64 KiB LDS tile; resize in two "
+                               "steps" % (lds_rows, ow))
+        return [torch.from_numpy(desc)], lds_rows
+    (desc_d,), lds_rows = _pil_device_cache.get((str(device), sizes, oh, ow, number), device, make)
+    return arena.sync(), desc_d, lds_rows
 
 
 def _pil_sizes(sizes, n, H, W):
@@ -3491,17 +3621,14 @@ def pil_resize(src, out_size, filter="lanczos", flip=None, sizes=None, want_floa
         return PilLevel(u8 if want_u8 else None, u8.float().div(255) if want_float else None)
     src = _c(src)
     dev = src.device
-    if flip is not None and not torch.is_tensor(flip):
-        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-    if flip is not None and (flip.dtype != torch.int32 or flip.numel() != n or flip.device != dev):
-        raise RuntimeError("pil_resize: flip must be an int32 tensor of %d entries on %s" % (n, dev))
+    flip = _flip_operand("pil_resize", flip, n, dev)
     tables, desc, lds_rows = _pil_tables_device(dev, sizes, oh, ow, number, filter)
     u8 = torch.empty((n, C_, oh, ow), device=dev, dtype=torch.uint8) if want_u8 else None
     f32 = torch.empty((n, C_, oh, ow), device=dev, dtype=torch.float32) if want_float else None
     strides = (H * W * C_, 1, W * C_, C_) if layout == "hwc" else (C_ * H * W, H * W, W, 1)
     N.check(_timed("pil_resample", lambda: N.lib().dmh_pil_resample(
         N.ptr(src), int(src.dtype == torch.float32), *strides, H, W, N.ptr(tables), int(tables.numel()), N.ptr(desc),
-        N.ptr(None if flip is None else _c(flip)), n, C_, oh, ow, lds_rows, N.ptr(u8), N.ptr(f32), N.stream()),
+        N.ptr(flip), n, C_, oh, ow, lds_rows, N.ptr(u8), N.ptr(f32), N.stream()),
         src.numel() * src.element_size() + n * C_ * oh * ow * (int(want_u8) + 4 * int(want_float))))
     return PilLevel(u8, f32)
 
@@ -3524,7 +3651,8 @@ def pil_pyramid(src, height, width, num_scales=4, filter="lanczos", flip=None, s
 
 # ---------------------------------------------------------------------------------------------------------------- K32
 VELO_EMPTY, VELO_DESC_CACHE = 0xFFFFFFFF, 16
-_velo_desc_cache = OrderedDict()      # (device, shapes) -> descriptors on the device
+_velo_desc_cache = _UploadCache(VELO_DESC_CACHE, "velo_depth_map: the first call with these shapes uploads their descriptors; make "
+                                                 "it once before capturing a graph")     # (device, shapes) -> descriptors
 
 
 def nearest_index(n_in, n_out):
@@ -3604,21 +3732,11 @@ def velo_depth_map_host(points, offsets, proj, shapes, vel_depth=False, out_size
 
 
 def _velo_desc_device(device, shapes):
-    key = (str(device), shapes)
-    hit = _velo_desc_cache.get(key)
-    if hit is not None:
-        _velo_desc_cache.move_to_end(key)
-        return hit[0]
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("velo_depth_map: the first call with these shapes uploads their descriptors; make it once before "
-                           "capturing a graph")
-    cells = np.cumsum([0] + [h * w for h, w in shapes])
-    rows = np.cumsum([0] + [h for h, _ in shapes])
-    host = torch.tensor([[h, w, int(cells[i]), int(rows[i])] for i, (h, w) in enumerate(shapes)], dtype=torch.int32).pin_memory()
-    _velo_desc_cache[key] = (host.to(device, non_blocking=True), host)      # the pinned copy lives as long as the upload may
-    while len(_velo_desc_cache) > VELO_DESC_CACHE:
-        _velo_desc_cache.popitem(last=False)
-    return _velo_desc_cache[key][0]
+    def make():
+        cells = np.cumsum([0] + [h * w for h, w in shapes])
+        rows = np.cumsum([0] + [h for h, _ in shapes])
+        return [torch.tensor([[h, w, int(cells[i]), int(rows[i])] for i, (h, w) in enumerate(shapes)], dtype=torch.int32)], None
+    return _velo_desc_cache.get((str(device), shapes), device, make)[0][0]
 
 
 def velo_depth_map(points, offsets, proj, shapes, vel_depth=False, out_size=None, flip=None):
@@ -3658,10 +3776,7 @@ def velo_depth_map(points, offsets, proj, shapes, vel_depth=False, out_size=None
         if out_size is not None:
             return torch.from_numpy(res)
         return torch.from_numpy(np.concatenate([m.reshape(-1) for m in res])), cell_off
-    if flip is not None and not torch.is_tensor(flip):
-        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-    if flip is not None and (flip.dtype != torch.int32 or flip.numel() != n or flip.device != dev):
-        raise RuntimeError("velo_depth_map: flip must be an int32 tensor of %d entries on %s" % (n, dev))
+    flip = _flip_operand("velo_depth_map", flip, n, dev)
     lib = N.lib()
     total_cells, total_rows = cell_off[-1], sum(h for h, _ in shapes)
     words = lib.dmh_velo_depth_ws_size(total_cells, total_rows)
@@ -3674,7 +3789,7 @@ def velo_depth_map(points, offsets, proj, shapes, vel_depth=False, out_size=None
     oh, ow = out_size if out_size is not None else (0, 0)
     N.check(_timed("velo_depth_map", lambda: lib.dmh_velo_depth_map(
         N.ptr(points) if points.numel() else None, int(points.shape[0]), N.ptr(_c(offsets)), N.ptr_f64(proj), N.ptr(desc),
-        N.ptr(None if flip is None else _c(flip)), n, int(bool(vel_depth)), total_cells, total_rows, oh, ow, N.ptr(ws), N.ptr(out),
+        N.ptr(flip), n, int(bool(vel_depth)), total_cells, total_rows, oh, ow, N.ptr(ws), N.ptr(out),
         N.stream()), points.numel() * 4 + 8 * words + out.numel() * 4))
     return out if out_size is not None else (out, cell_off)
 
@@ -3827,7 +3942,8 @@ def pil_color_jitter(images, params, want_u8=False):
 # ---------------------------------------------------------------------------------------------------------------- K34
 HINT_MAX_CANDIDATES = 16
 HINT_TABLE_CACHE = 8
-_hint_table_cache = OrderedDict()
+_hint_table_cache = _UploadCache(HINT_TABLE_CACHE, "depth_hint_prepare: the first call with these sizes uploads their index tables; "
+                                                   "make it once before capturing a graph")     # (device, Hs, Ws, H, W) -> (ytab, xtab)
 
 
 def hint_candidate_depths(cand, K):
@@ -3981,19 +4097,9 @@ def depth_hint_prepare_host(hints, flip, out_size):
 
 
 def _hint_tables_device(device, Hs, Ws, H, W):
-    key = (str(device), Hs, Ws, H, W)
-    hit = _hint_table_cache.get(key)
-    if hit is not None:
-        _hint_table_cache.move_to_end(key)
-        return hit[0], hit[1]
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("depth_hint_prepare: the first call with these sizes uploads their index tables; make it once before "
-                           "capturing a graph")
-    host = [torch.from_numpy(cv_nearest_index(a, b).astype(np.int32)).pin_memory() for a, b in ((Hs, H), (Ws, W))]
-    _hint_table_cache[key] = (host[0].to(device, non_blocking=True), host[1].to(device, non_blocking=True), host)   # pinned copies live on
-    while len(_hint_table_cache) > HINT_TABLE_CACHE:
-        _hint_table_cache.popitem(last=False)
-    return _hint_table_cache[key][:2]
+    def make():
+        return [torch.from_numpy(cv_nearest_index(a, b).astype(np.int32)) for a, b in ((Hs, H), (Ws, W))], None
+    return _hint_table_cache.get((str(device), Hs, Ws, H, W), device, make)[0]
 
 
 def depth_hint_prepare(hints, flip, out_size):
@@ -4009,16 +4115,13 @@ def depth_hint_prepare(hints, flip, out_size):
     dev = hints.device
     if dev.type != "cuda":
         return depth_hint_prepare_host(hints, flip, out_size)
-    if flip is not None and not torch.is_tensor(flip):
-        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-    if flip is not None and (flip.dtype != torch.int32 or flip.device != dev):
-        raise RuntimeError("depth_hint_prepare: flip must be an int32 tensor of %d entries on %s" % (B, dev))
+    flip = _flip_operand("depth_hint_prepare", flip, B, dev)
     ytab, xtab = _hint_tables_device(dev, Hs, Ws, H, W)
     hints = _c(hints)
     hint = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
     mask = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
     N.check(_timed("depth_hint_prepare", lambda: N.lib().dmh_depth_hint_prepare(
-        N.ptr(hints), N.ptr(None if flip is None else _c(flip)), N.ptr(ytab), N.ptr(xtab), H, W, B, Hs, Ws, H, W, N.ptr(hint),
+        N.ptr(hints), N.ptr(flip), N.ptr(ytab), N.ptr(xtab), H, W, B, Hs, Ws, H, W, N.ptr(hint),
         N.ptr(mask), N.stream()), B * H * W * 12))
     return hint, mask
 

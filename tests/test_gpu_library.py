@@ -162,3 +162,163 @@ def test_layers_smooth_loss_goes_through_the_kernel(shape):
     ref.backward()
     assert abs(float(out) - float(ref)) <= 2e-6 * abs(float(ref))
     assert float((dd.grad.cpu().double() - d64.grad).abs().max()) <= 1e-5 * float(d64.grad.abs().max())
+
+
+# ---- both surfaces run the launchers of ops.py: what is left to hold is the plumbing around them -- argument order, saved tensors
+# and gradient slots of the autograd.Function and custom_op wrappers -- in the forms the tests above do not reach
+@pytest.mark.parametrize("flip,broadcast", [(True, False), (False, True), (True, True)])
+def test_paste_surfaces_agree_with_flip_and_a_broadcast_scene(flip, broadcast):
+    N, ops, library = _lib()
+    dev = torch.device("cuda")
+    scenes, obj, pmask, coeffs, l_pad, t_pad = _paste_case(dev, 2)
+    scenes = scenes[:1] if broadcast else scenes
+    fl = torch.tensor([1, 0], dtype=torch.int32, device=dev) if flip else None
+    w = torch.rand(2, 3, 40, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    res = []
+    for use_lib in (False, True):
+        patch = obj.clone().requires_grad_(True)
+        if use_lib:
+            adv, m = torch.ops.dmh.eot_paste(scenes, patch, pmask, coeffs, l_pad, t_pad, 40, 128, fl)
+        else:
+            adv, m = ops.eot_paste(scenes, patch, pmask, coeffs, l_pad, t_pad, (40, 128), flip=fl)
+        (g,) = torch.autograd.grad((adv * w).sum(), patch)
+        res.append((adv.detach(), m, g))
+    assert all(torch.equal(a, b) for a, b in zip(*res))
+    assert float(res[0][2].abs().max()) > 0 and float(res[0][1].max()) > 0
+    if flip:        # the flag reaches the kernel on both surfaces: sample 0 differs from its un-flipped paste, sample 1 does not
+        plain, _ = ops.eot_paste(scenes, obj, pmask, coeffs, l_pad, t_pad, (40, 128))
+        assert not torch.equal(plain[0], res[0][0][0]) and torch.equal(plain[1], res[0][0][1])
+
+
+def test_small_operator_surfaces_agree_without_a_mask_and_with_finalize():
+    N, ops, library = _lib()
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(6)
+    d = torch.rand(2, 1, 16, 24, generator=g).to(dev)
+    res = []
+    for fn in (ops.masked_sq_mean, torch.ops.dmh.masked_sq_mean):
+        x = d.clone().requires_grad_(True)
+        cost = fn(x, None)
+        (gx,) = torch.autograd.grad(cost * 3.0, x)
+        res.append((cost.detach(), gx))
+    assert all(torch.equal(a, b) for a, b in zip(*res)) and float(res[0][1].abs().max()) > 0
+    obj = torch.rand(1, 3, 16, 24, generator=g).to(dev)
+    pos0, neg0 = torch.rand(1, 3, 16, 24, generator=g).to(dev) * 1.5 - 0.25, torch.rand(1, 3, 16, 24, generator=g).to(dev) * 1.5 - 0.25
+    w = torch.rand(1, 3, 16, 24, generator=g).to(dev)
+    res = []
+    for use_lib in (False, True):
+        pos, neg = pos0.clone().requires_grad_(True), neg0.clone().requires_grad_(True)
+        adv, count = torch.ops.dmh.l0_compose(obj, pos, neg, 0.3, True) if use_lib else ops.l0_compose(obj, pos, neg, 0.3, finalize=True)
+        res.append((adv.detach(), count) + torch.autograd.grad((adv * w).sum(), [pos, neg]))
+    assert all(torch.equal(a, b) for a, b in zip(*res))
+    plain, _ = ops.l0_compose(obj, pos0, neg0, 0.3, finalize=False)
+    assert not torch.equal(plain, res[0][0])        # ``finalize`` reaches the kernel
+
+
+@pytest.mark.parametrize("variant,philox", [("dh", False), ("md2", True), ("dh", True)])
+def test_fused_loss_surfaces_agree_in_variant_dh_and_with_philox(variant, philox):
+    N, ops, library = _lib()
+    from oracle import synth
+    from tests.util import to_dev
+    B, H, W = 2, 64, 192
+    inputs, disps = synth.make_loss_case(B, H, W, 5)
+    d_in = to_dev(inputs)
+    wfin = torch.rand(N.FIN_SIZE, generator=torch.Generator().manual_seed(8)).cuda()
+    res = []
+    for use_lib in (False, True):
+        dd = [d.cuda().requires_grad_(True) for d in disps]
+        args = (d_in[("color", 0, 0)], [d_in[("color", "s", 0)]], [d_in["stereo_T"]], d_in[("K", 0)], d_in[("inv_K", 0)], dd,
+                [d_in[("color", 0, s)] for s in range(4)])
+        torch.manual_seed(77)
+        gen = torch.cuda.default_generators[torch.cuda.current_device()]
+        gen.set_offset(40)
+        seed, offset = gen.initial_seed() & 0xFFFFFFFFFFFFFFFF, gen.get_offset()       # what ops._philox hands the kernel
+        if use_lib:
+            fin, sel, _ = torch.ops.dmh.photo_smooth_loss(*args, 0.1, 100.0, N.VARIANT_DH if variant == "dh" else N.VARIANT_MD2, True,
+                                                          False, 1e-3, N.NOISE_PHILOX if philox else N.NOISE_NONE, seed, offset)
+        else:
+            out = ops.photometric_smooth_loss(*args, variant=variant, noise="philox" if philox else None)
+            fin, sel = out.fin, out.sel.packed
+        res.append((fin.detach(), sel) + torch.autograd.grad((fin * wfin).sum(), dd))
+    assert all(torch.equal(a, b) for a, b in zip(*res))
+    assert all(float(g.abs().max()) > 0 for g in res[0][2:])
+
+
+# ---- the upload cache of the loader operators (ops._UploadCache): K32's descriptors and K34's index tables follow K31's rules
+def _velo_case(i, dev):
+    """One frame of (4 + i) x 6 cells with a dozen points in front of it: (points, offsets, proj, shapes)."""
+    H, W = 4 + i, 6
+    g = torch.Generator().manual_seed(100 + i)
+    pts = torch.rand(12, 4, generator=g)
+    pts[:, 2] += 1.0                                       # u = rint(W x / z + 1) - 1, v = rint(H y / z + 1) - 1: mostly inside
+    proj = torch.tensor([[[W, 0, 1, 0], [0, H, 1, 0], [0, 0, 1, 0]]], dtype=torch.float64)
+    return pts.to(dev), torch.tensor([0, 12], dtype=torch.int32).to(dev), proj.to(dev), ((H, W),)
+
+
+def _hint_case(i):
+    """(hints [2, 1, Hs, Ws] on the CPU, flip, out_size): a few pixels each, every i another (Hs, Ws) -> (H, W)."""
+    hints = torch.rand(2, 1, 3 + i, 5, generator=torch.Generator().manual_seed(200 + i)) - 0.3
+    return hints, [True, False], (4 + i, 7)
+
+
+def test_upload_caches_stay_bounded_and_right_after_eviction():
+    N, ops, library = _lib()
+    dev, cpu = torch.device("cuda"), torch.device("cpu")
+    for i in list(range(ops.VELO_DESC_CACHE + 3)) + [0]:         # the first key once more, after its eviction
+        got, off = ops.velo_depth_map(*_velo_case(i, dev))
+        want, want_off = ops.velo_depth_map(*_velo_case(i, cpu))
+        assert torch.equal(got.cpu(), want) and off == want_off and float(want.max()) > 0, i
+        assert len(ops._velo_desc_cache) <= ops.VELO_DESC_CACHE + len(ops._velo_desc_cache.held)
+    for i in list(range(ops.HINT_TABLE_CACHE + 3)) + [0]:
+        hints, flip, out_size = _hint_case(i)
+        got, want = ops.depth_hint_prepare(hints.to(dev), flip, out_size), ops.depth_hint_prepare_host(hints, flip, out_size)
+        assert torch.equal(got[0].cpu(), want[0]) and torch.equal(got[1].cpu(), want[1]) and float(want[1].sum()) > 0, i
+        assert len(ops._hint_table_cache) <= ops.HINT_TABLE_CACHE + len(ops._hint_table_cache.held)
+
+
+def test_a_second_stream_waits_for_the_first_upload():
+    N, ops, library = _lib()
+    dev = torch.device("cuda")
+    side = torch.cuda.Stream()
+    velo = _velo_case(40, dev)
+    hints, flip, out_size = _hint_case(40)
+    hints_d, flip_d = hints.to(dev), torch.tensor([1, 0], dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()                                # the inputs are there: what is left to wait for is the tables' upload
+    first_v = ops.velo_depth_map(*velo)[0]
+    with torch.cuda.stream(side):
+        second_v = ops.velo_depth_map(*velo)[0]
+    first_h = ops.depth_hint_prepare(hints_d, flip_d, out_size)
+    with torch.cuda.stream(side):
+        second_h = ops.depth_hint_prepare(hints_d, flip_d, out_size)
+    torch.cuda.synchronize()
+    want_v = ops.velo_depth_map(*_velo_case(40, torch.device("cpu")))[0]
+    want_h = ops.depth_hint_prepare_host(hints, flip, out_size)
+    assert torch.equal(first_v.cpu(), want_v) and torch.equal(second_v.cpu(), want_v)
+    for got in (first_h, second_h):
+        assert torch.equal(got[0].cpu(), want_h[0]) and torch.equal(got[1].cpu(), want_h[1])
+
+
+def test_tables_a_captured_graph_holds_are_not_evicted():
+    N, ops, library = _lib()
+    dev = torch.device("cuda")
+    hints, _, out_size = _hint_case(60)
+    hints_d = hints.to(dev)
+    eager = ops.depth_hint_prepare(hints_d, None, out_size)             # warms the key
+    key = (str(hints_d.device), hints.shape[2], hints.shape[3]) + out_size
+    assert key in ops._hint_table_cache
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(stream):
+        with torch.cuda.graph(graph, stream=stream):                    # one launch: no parallel branches
+            held = ops.depth_hint_prepare(hints_d, None, out_size)
+    torch.cuda.current_stream().wait_stream(stream)
+    for i in range(61, 61 + ops.HINT_TABLE_CACHE + 1):
+        other, flip, size = _hint_case(i)
+        ops.depth_hint_prepare(other.to(dev), flip, size)
+    for t in held:
+        t.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(held[0], eager[0]) and torch.equal(held[1], eager[1]) and float(eager[1].sum()) > 0
+    assert key in ops._hint_table_cache and key in ops._hint_table_cache.held

@@ -430,3 +430,19 @@ def test_environment_switches_are_the_documented_ones():
     documented = set(re.findall(r"^\s*\|\s*`(DMH_[A-Z0-9_]+)`", open(os.path.join(REPO, "INTEGRATION.md")).read(), re.M))
     assert read and read == documented, ("read but not documented", sorted(read - documented),
                                          "documented but not read", sorted(documented - read))
+
+
+def test_one_launch_site_per_kernel_behind_ops_and_library():
+    """torch.ops.dmh.* (library.py) and the autograd Functions (ops.py) launch through the same launchers: library.py makes no call
+    into the C library of its own, and each C entry point of the older kernels (K1-K6, the stand-alone layers) is called at one
+    place in ops.py -- a change of a C signature or of a workspace size is made once."""
+    pkg = os.path.join(REPO, "depthmodelhardening_amd")
+    ops_text, lib_text = open(os.path.join(pkg, "ops.py")).read(), open(os.path.join(pkg, "library.py")).read()
+    assert "N.lib()" not in lib_text and "C.byref" not in lib_text and "import ctypes" not in lib_text
+    assert re.findall(r"\bdmh_\w+\(", lib_text) == []
+    for name in ("dmh_photo_loss_fwd", "dmh_photo_loss_bwd", "dmh_photo_loss_bwd_pose", "dmh_smooth_loss_fwd", "dmh_smooth_loss_bwd",
+                 "dmh_loss_finalize", "dmh_eot_paste_fwd", "dmh_eot_paste_bwd", "dmh_masked_sq_mean_fwd", "dmh_masked_sq_mean_bwd",
+                 "dmh_gt_depth_mse_fwd", "dmh_gt_depth_mse_bwd", "dmh_pgd_linf_step", "dmh_l0_compose_fwd", "dmh_l0_compose_bwd",
+                 "dmh_l0_mask_cost_fwd", "dmh_l0_mask_cost_bwd", "dmh_ssim_map", "dmh_ssim_map_bwd", "dmh_edge_smooth",
+                 "dmh_edge_smooth_bwd"):
+        assert len(re.findall(r"\b%s\(" % name, ops_text)) == 1, name
