@@ -6,6 +6,7 @@ below is one or a few launches of hand-written gfx950 kernels through the C ABI
 """
 import contextlib
 import ctypes as C
+import functools
 import os
 from collections import OrderedDict, namedtuple
 
@@ -1499,22 +1500,26 @@ def frozen_memo(key, fn):
     return _wino_cache[key]
 
 
-def _wino_filter(weight, backward, scale=None):
-    """Winograd-transformed filter of the forward (backward=False) or backward-data pass; `scale` folds a per-channel
-    factor of the forward OUTPUT (an eval-mode BatchNorm) into it."""
+def _wino_filter(weight, backward, scale=None, k17=False):
+    """Winograd-transformed filter of the forward (backward=False) or backward-data pass, in K10's layout or (``k17``) K17's;
+    `scale` (K10) folds a per-channel factor of the forward OUTPUT (an eval-mode BatchNorm) into it."""
     lib = N.lib()
     K, Cc = weight.shape[0], weight.shape[1]
-    key = (weight.data_ptr(), weight._version, bool(backward), None if scale is None else scale.data_ptr())
+    key = (weight.data_ptr(), weight._version, bool(backward), "k17" if k17 else None if scale is None else scale.data_ptr())
     if _wino_frozen and key in _wino_cache:
         return _wino_cache[key]
-    if scale is None and not _wino_frozen:
+    if key[3] is None and not _wino_frozen:
         ready = _wino_ready.get((key[0], key[2]))      # transformed ahead of its use by wino_prefetch()
         if ready is not None and ready[0] == key[1] and ready[1].device == weight.device:
             return ready[1]
     n_out, n_in = (Cc, K) if backward else (K, Cc)
-    U = torch.empty(lib.dmh_wino_weight_size(n_out, n_in), device=weight.device, dtype=torch.float32)
-    N.check(lib.dmh_wino_weight_transform_scaled(N.ptr(_c(weight.detach())), K, Cc, int(backward), N.ptr(scale), N.ptr(U),
-                                                 N.stream()))
+    size = lib.dmh_wino32_weight_size(n_out, n_in) if k17 else lib.dmh_wino_weight_size(n_out, n_in)
+    U = torch.empty(size, device=weight.device, dtype=torch.float32)
+    if k17:
+        N.check(lib.dmh_wino32_weight_transform(N.ptr(_c(weight.detach())), K, Cc, int(backward), N.ptr(U), N.stream()))
+    else:
+        N.check(lib.dmh_wino_weight_transform_scaled(N.ptr(_c(weight.detach())), K, Cc, int(backward), N.ptr(scale), N.ptr(U),
+                                                     N.stream()))
     if _wino_frozen:
         _wino_cache[key] = U
     return U
@@ -1564,7 +1569,7 @@ def wino_prefetch(jobs, fresh=False):
             continue
         K, Cc = weight.shape[0], weight.shape[1]
         n_out, n_in = (Cc, K) if backward else (K, Cc)
-        if n_in % 8 or n_in < 24 or n_out < 64:        # not a K10 shape in this direction (ops._wino_ok)
+        if not _k10_channels(n_in, n_out):             # not a K10 shape in this direction
             continue
         if scale is not None and not _wino_frozen:     # a scale is a temporary: only a frozen scope's cache may key on it
             continue
@@ -1599,40 +1604,54 @@ _WINO_MIN_ITEMS = 64
 _WINO_MIN_FILL = 0.5        # real tiles / tiles of the regions below which MIOpen is ahead
 
 
+def _k10_channels(n_in, n_out):
+    """Channel counts of a pass that K10 (64 output channels per work item, 8 input channels per chunk) takes."""
+    return n_in % 8 == 0 and n_in >= 24 and n_out >= 64
+
+
+def _k17_channels(n_in, n_out):
+    """Channel counts of a pass that K17 takes: 32 or 96 output channels, which K10's 64-channel items would half-fill."""
+    return n_in % 8 == 0 and n_in >= 24 and n_out % 32 == 0 and n_out % 64 != 0 and n_out <= 96
+
+
 def _wino_ok(B, n_in, n_out, Ho, Wo, allow_split=True, allow_sk=False):
     """Shapes the Winograd-MFMA kernel takes: channel counts it tiles without waste and enough 64-channel x 64-tile
-    work items to fill the 256 CUs (measured crossover, tools/wino_bench.py)."""
-    if not WINO_ENABLED or n_in % 8 or n_in < 24 or n_out < 64 or Ho % 2 or Wo % 2 or Ho < 2 or Wo < 2:
+    work items to fill the chip (measured crossover, tools/wino_bench.py).  The thresholds are this rule's; the geometry of the
+    launch they are applied to -- tile form, regions, the two-way channel split, stream-K -- is the library's own answer
+    (dmh_wino_conv3x3_plan: what the launcher would do), not restated here."""
+    if not WINO_ENABLED or not _k10_channels(n_in, n_out) or Ho % 2 or Wo % 2 or Ho < 2 or Wo < 2:
         return False
     if B * n_in * (Ho + 2) * (Wo + 2) >= (1 << 30):     # 32-bit byte offsets of the kernel's buffer loads: ATen beyond
         return False
     if n_in < 64 and n_out % 64:        # few chunks per item and a half-empty channel group: MIOpen is level or ahead
         return False
-    ht, wt = Ho // 2, Wo // 2
-    narrow = wt % 32 != 0 and (wt <= 16 or (-wt) % 16 < (-wt) % 32)
-    if narrow:      # 4x16 regions; rows of tiles flattened over the batch when per-image regions would waste >= 1/5
-        flat = 5 * ht <= 4 * (-(-ht // 4) * 4)
-        rows = -(-(B * ht) // 4) * 4 if flat else B * -(-ht // 4) * 4
-        cols = -(-wt // 16) * 16
-    else:
-        rows, cols = B * -(-ht // 2) * 2, -(-wt // 32) * 32
-    if B * ht * wt < _WINO_MIN_FILL * rows * cols:     # ragged image: too many empty tiles (e.g. 17 tile columns in a 32-wide region)
-        return False
-    regions = (rows // (4 if narrow else 2)) * (cols // (16 if narrow else 32))
-    regions *= -(-n_out // 64)
-    nch = n_in // 8
-    split = 2 if (allow_split and regions < 192 and nch % 2 == 0 and nch >= 6) else 1      # mirrors launch_split()
-    if WINO_SK and (allow_split or allow_sk) and regions * nch >= 8 * _WINO_MIN_ITEMS:
-        # enough (item, chunk) units for the stream-K form -- IF the library takes it for this shape: its own decision is asked
-        # (dmh_wino_conv3x3_plan: cost model, workspace size, the fused epilogue's few-regions rule), not mirrored here
+    ws_floats = 0       # no workspace, no stream-K: the switch is off, or a fused epilogue whose caller does not allow it
+    if WINO_SK and (allow_split or allow_sk):
         try:
             ws_floats = _sk_ws_floats(torch.cuda.current_device()) if torch.cuda.is_available() else 2 * 256 * _SK_SLOT_FLOATS
         except Exception:
             ws_floats = 2 * 256 * _SK_SLOT_FLOATS
-        plan = N.lib().dmh_wino_conv3x3_plan(B, n_in, n_out, Ho, Wo, 1, 0 if allow_split else 1, ws_floats)
-        if plan >= 0 and (plan & 1):
+    return _wino_fills(B, n_in, n_out, Ho, Wo, 0 if allow_split else 1, ws_floats, WINO_SK)
+
+
+@functools.lru_cache(maxsize=4096)
+def _wino_fills(B, n_in, n_out, Ho, Wo, epilogue, ws_floats, sk):
+    """_wino_ok's thresholds on the launch plan of a shape, remembered: a step asks for the same few dozen shapes again and
+    again.  Every input of the decision is an argument (``sk``: WINO_SK, which tests flip at run time, like WINO_ENABLED, which
+    _wino_ok looks at before it comes here)."""
+    plan = N.lib().dmh_wino_conv3x3_plan(B, n_in, n_out, Ho, Wo, 1, epilogue, ws_floats)
+    if plan < 0:
+        return False
+    items = plan >> 8                                   # whole work items: regions x the channel split (bit 1)
+    regions = items // (2 if plan & 2 else 1)
+    # ragged image: too many empty tiles (e.g. 17 tile columns in a 32-wide region); a region has 64 tiles in every form
+    if B * (Ho // 2) * (Wo // 2) < _WINO_MIN_FILL * (regions // -(-n_out // 64)) * 64:
+        return False
+    if plan & 1:        # the library would take the stream-K form: enough (item, chunk) units for it?
+        if regions * (n_in // 8) >= 8 * _WINO_MIN_ITEMS:
             return True
-    return regions * split >= (_WINO_MIN_ITEMS if WINO_SK else max(_WINO_MIN_ITEMS, 200))     # whole items only: round 4's threshold
+        items = N.lib().dmh_wino_conv3x3_plan(B, n_in, n_out, Ho, Wo, 1, epilogue, 0) >> 8      # ... no: as whole items
+    return items >= (_WINO_MIN_ITEMS if sk else max(_WINO_MIN_ITEMS, 200))     # whole items only: round 4's threshold
 
 
 def _wrw_ok(x, g, K, Cc):
@@ -1661,7 +1680,7 @@ def _wrw_ok(x, g, K, Cc):
 def _wino32_ok(B, n_in, n_out, Ho, Wo):
     """Shapes of K17, the 32-output-channel form of K10 (work item 32 channels x 4 x 32 tiles): output channels a multiple
     of 32 that K10's 64-channel items would half-fill, enough items to cover the chip and few empty tiles."""
-    if (not WINO_ENABLED or n_in % 8 or n_in < 32 or n_out % 32 or n_out % 64 == 0 or n_out > 96 or Ho % 2 or Wo % 2
+    if (not WINO_ENABLED or not _k17_channels(n_in, n_out) or n_in < 32 or Ho % 2 or Wo % 2
             or B * n_in * (Ho + 2) * (Wo + 2) >= (1 << 30)):
         return False        # (32 -> 96, the backward-data pass of upconv(1,1): 509 us against MIOpen's 566, tools/wino32_bench.py)
     ht, wt = Ho // 2, Wo // 2
@@ -1669,20 +1688,6 @@ def _wino32_ok(B, n_in, n_out, Ho, Wo):
     if ht * wt < 0.8 * rows * cols:
         return False
     return B * (rows // 4) * (cols // 32) * (n_out // 32) >= 400
-
-
-def _wino32_filter(weight, backward):
-    lib = N.lib()
-    K, Cc = weight.shape[0], weight.shape[1]
-    key = (weight.data_ptr(), weight._version, bool(backward), "k17")
-    if _wino_frozen and key in _wino_cache:
-        return _wino_cache[key]
-    n_out, n_in = (Cc, K) if backward else (K, Cc)
-    U = torch.empty(lib.dmh_wino32_weight_size(n_out, n_in), device=weight.device, dtype=torch.float32)
-    N.check(lib.dmh_wino32_weight_transform(N.ptr(_c(weight.detach())), K, Cc, int(backward), N.ptr(U), N.stream()))
-    if _wino_frozen:
-        _wino_cache[key] = U
-    return U
 
 
 _sk_ws = {}         # (device, stream) -> workspace of the stream-K launches (caller-owned: the library keeps nothing)
@@ -1744,13 +1749,15 @@ def _relu_mask_bwd(y, g):
 def _wino_conv(x, U, bias, K, pad, k17=False):
     """The plain K10 launch, or (``k17``) K17's, on a transformed filter U."""
     lib = N.lib()
-    launch, name = (lib.dmh_wino32_conv3x3_ws, "wino32_conv3x3") if k17 else (lib.dmh_wino_conv3x3_ws, "wino_conv3x3")
     B, Cc, H, W = x.shape
     y = torch.empty((B, K, H + 2 * pad - 2, W + 2 * pad - 2), device=x.device, dtype=torch.float32)
     nb = 4 * (x.numel() + y.numel()) + 4 * U.numel()
     ws = _sk_workspace(x.device) if WINO_SK else None
-    N.check(_timed(name, lambda: launch(N.ptr(x), N.ptr(U), N.ptr(bias), B, Cc, K, H, W, pad, N.ptr(y), N.ptr(ws),
-                                        0 if ws is None else ws.numel(), N.stream()), nb, 18 * Cc * y.numel()))
+    args = (N.ptr(x), N.ptr(U), N.ptr(bias), B, Cc, K, H, W, pad, N.ptr(y), N.ptr(ws), 0 if ws is None else ws.numel(), N.stream())
+    if k17:
+        N.check(_timed("wino32_conv3x3", lambda: lib.dmh_wino32_conv3x3_ws(*args), nb, 18 * Cc * y.numel()))
+    else:
+        N.check(_timed("wino_conv3x3", lambda: lib.dmh_wino_conv3x3_ws(*args), nb, 18 * Cc * y.numel()))
     return y
 
 
@@ -1794,80 +1801,124 @@ def _head_conv_bwd(g, weight):
     return g_x
 
 
+def _direct_wrw(x, g, weight, pad, need_b):
+    """(g_w, g_b or None) of a convolution to ONE output channel (K13: a strip reduction, the disparity heads) or to 16 (K16:
+    pixel axis on the MFMA, persistent workgroups, the last decoder stage) in place of MIOpen's implicit GEMMs."""
+    lib = N.lib()
+    B, Cc, H, W = x.shape
+    K, nb = weight.shape[0], 4 * (x.numel() + g.numel())
+    n_part = lib.dmh_conv3x3_head_wrw_partials_size(B, Cc, H, W, pad) if K == 1 else lib.dmh_conv3x3_small_wrw_partials_size(Cc)
+    part = torch.empty(n_part, device=g.device, dtype=torch.float32)
+    g_w = torch.empty_like(weight)
+    g_b = torch.empty(K, device=g.device, dtype=torch.float32) if need_b else None
+    args = (N.ptr(x), N.ptr(g), B, Cc, H, W, pad, N.ptr(part), N.ptr(g_w), N.ptr(g_b), N.stream())
+    if K == 1:
+        N.check(_timed("conv3x3_head_wrw", lambda: lib.dmh_conv3x3_head_wrw(*args), nb))
+    else:
+        N.check(_timed("conv3x3_small_wrw", lambda: lib.dmh_conv3x3_small_wrw(*args), nb, 18 * Cc * g.numel()))
+    return g_w, g_b
+
+
+def _wino_wrw(x, g, K, pad):
+    """K18, the [K, C, 3, 3] weight gradient in the Winograd domain on the fp32 MFMA (MIOpen: NHWC implicit GEMMs between layout
+    transposes, with atomics).  The bias gradient is a plain reduction of g and the caller's."""
+    lib = N.lib()
+    B, Cc, H, W = x.shape
+    ws = torch.empty(lib.dmh_wino_wrw_workspace_size(B, Cc, K, H, W, pad), device=g.device, dtype=torch.float32)
+    g_w = torch.empty((K, Cc, 3, 3), device=g.device, dtype=torch.float32)
+    N.check(_timed("wino_wrw", lambda: lib.dmh_wino_wrw(N.ptr(x), N.ptr(g), B, Cc, K, H, W, pad, N.ptr(ws), N.ptr(g_w), N.stream()),
+                   4 * (x.numel() + g.numel()), 18 * Cc * g.numel()))
+    return g_w
+
+
+def _wrw_route(x, g, K, Cc):
+    """Which kernel takes the weight gradient of a [K, C, 3, 3] convolution of x with output gradient g: "k13" (one output
+    channel), "k16" (16 output channels from 16 or 32), "k18" (_wrw_ok) or None (ATen)."""
+    if WINO_ENABLED and K == 1 and Cc * x.shape[2] * x.shape[3] < (1 << 29):
+        return "k13"
+    if WINO_ENABLED and K == 16 and Cc in (16, 32) and Cc * x.shape[2] * x.shape[3] < (1 << 28):
+        return "k16"
+    return "k18" if _wrw_ok(x, g, K, Cc) else None
+
+
+def _conv3x3_route(B, n_in, n_out, H, W, pad, backward, capable_only=False):
+    """THE rule of which kernel takes a 3x3 convolution pass: "k10", "k17", "k13", "k11" or None (the caller's fall-back).  Host
+    logic only, in the terms of the pass: n_in -> n_out channels on a [B, n_in, H, W] input with zero padding ``pad``;
+    ``backward``: it is a backward-data pass -- the same convolution on the output gradient with pad = 2 - the forward padding.
+    A kernel is named where it WINS (the thresholds of _wino_ok / _wino32_ok, K13's tile count); with ``capable_only`` wherever
+    it CAN run (channel and size limits): the attack's window launches, smaller than the shapes the thresholds were measured on."""
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    if capable_only:
+        if not WINO_ENABLED or B * n_in * H * W >= (1 << 30):
+            return None
+        if Ho % 2 == 0 and Wo % 2 == 0 and Ho >= 2 and Wo >= 2:
+            if _k17_channels(n_in, n_out):          # (96 output channels: K17's here, K10's by throughput where it fills the chip)
+                return "k17"
+            if _k10_channels(n_in, n_out):
+                return "k10"
+    elif _wino_ok(B, n_in, n_out, Ho, Wo):
+        return "k10"
+    elif _wino32_ok(B, n_in, n_out, Ho, Wo):
+        return "k17"
+    if backward:        # disparity head, backward-data at forward padding 0: one gradient plane in, <= 64 planes out
+        head = n_in == 1 and pad == 2 and n_out % 4 == 0 and n_out <= 64 and Ho >= 3 and Wo >= 3
+    else:               # disparity head: the strip kernel at padding 0, the tiled one where its 8 x 64 tiles fill the chip
+        head = n_out == 1 and ((pad == 0 and n_in % 4 == 0) or (
+            not capable_only and n_in % 16 == 0 and n_in >= 32 and B * -(-Ho // 8) * -(-Wo // 64) >= 512))
+    if WINO_ENABLED and head:
+        return "k13"
+    return "k11" if _small_ok(n_in, n_out) else None
+
+
+def _conv3x3_routed(x, weight, bias, pad, backward=False, scale=None, k10_only=False, capable_only=False):
+    """conv2d(x, weight, bias, padding=pad) -- with ``backward`` the backward-data pass of ``weight`` on a gradient x, pad = 2 -
+    the forward padding -- on the kernel _conv3x3_route() names, or None: the fall-back is the caller's.  ``k10_only``: the
+    sites around K10's fused epilogue, which take K10 or their library path; their ``scale`` is folded into K10's filter."""
+    B, n_in, H, W = x.shape
+    n_out = weight.shape[1] if backward else weight.shape[0]
+    route = _conv3x3_route(B, n_in, n_out, H, W, pad, backward, capable_only)
+    if route == "k10":
+        return _wino_conv(x, _wino_filter(weight, backward, scale), bias, n_out, pad)
+    if route is None or k10_only:
+        return None
+    if route == "k17":
+        return _wino_conv(x, _wino_filter(weight, backward, k17=True), bias, n_out, pad, k17=True)
+    if route == "k13":
+        return _head_conv_bwd(x, weight) if backward else _head_conv(x, weight, bias, pad)
+    return _small_conv(x, weight, bias, pad, backward)
+
+
 class _Conv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, pad):
-        B, Cc, H, W = x.shape
-        K = weight.shape[0]
         ctx.pad = pad
         ctx.has_bias = bias is not None
         ctx.params_const = _wino_frozen > 0
         ctx.save_for_backward(x, weight)
-        if _wino_ok(B, Cc, K, H + 2 * pad - 2, W + 2 * pad - 2):
-            return _wino_conv(x, _wino_filter(weight, False), None if bias is None else _c(bias.detach()), K, pad)
-        if _wino32_ok(B, Cc, K, H + 2 * pad - 2, W + 2 * pad - 2):
-            return _wino_conv(x, _wino32_filter(weight, False), None if bias is None else _c(bias.detach()), K, pad, k17=True)
-        if WINO_ENABLED and K == 1 and ((pad == 0 and Cc % 4 == 0) or (      # disparity head: K13 (strip kernel at pad 0)
-                Cc % 16 == 0 and Cc >= 32 and B * -(-(H + 2 * pad - 2) // 8) * -(-(W + 2 * pad - 2) // 64) >= 512)):
-            return _head_conv(x, weight, None if bias is None else _c(bias.detach()), pad)
-        if _small_ok(Cc, K):
-            return _small_conv(x, weight, None if bias is None else _c(bias.detach()), pad, False)
-        return torch.conv2d(x, weight, bias, 1, pad)
+        y = _conv3x3_routed(x, weight, None if bias is None else _c(bias.detach()), pad)
+        return torch.conv2d(x, weight, bias, 1, pad) if y is None else y
 
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        B, Cc, H, W = x.shape
-        K = weight.shape[0]
+        K, Cc = weight.shape[0], weight.shape[1]
         pad = ctx.pad
         g = _c(g)
         need_x = ctx.needs_input_grad[0]
         need_w = ctx.needs_input_grad[1] and not ctx.params_const
         need_b = ctx.has_bias and ctx.needs_input_grad[2] and not ctx.params_const
         g_x = g_w = g_b = None
-        if need_x and _wino_ok(B, K, Cc, H, W):
-            # backward-data = the same convolution on g with the flipped/transposed filter and pad' = 2 - pad
-            g_x = _wino_conv(g, _wino_filter(weight, True), None, Cc, 2 - pad)
-            need_x = False
-        elif need_x and _wino32_ok(B, K, Cc, H, W):
-            g_x = _wino_conv(g, _wino32_filter(weight, True), None, Cc, 2 - pad, k17=True)
-            need_x = False
-        elif need_x and K == 1 and pad == 0 and Cc % 4 == 0 and Cc <= 64 and H >= 3 and W >= 3 and WINO_ENABLED:
-            g_x = _head_conv_bwd(g, weight)         # disparity head
-            need_x = False
-        elif need_x and _small_ok(K, Cc):
-            g_x = _small_conv(g, weight, None, 2 - pad, True)
-            need_x = False
-        if need_w and K == 1 and WINO_ENABLED and Cc * H * W < (1 << 29):
-            # disparity head (one output channel): K13's strip reduction instead of MIOpen's 1-row implicit GEMM
-            lib = N.lib()
-            part = torch.empty(lib.dmh_conv3x3_head_wrw_partials_size(B, Cc, H, W, pad), device=g.device, dtype=torch.float32)
-            g_w = torch.empty_like(weight)
-            g_b = torch.empty(1, device=g.device, dtype=torch.float32) if need_b else None
-            N.check(_timed("conv3x3_head_wrw", lambda: lib.dmh_conv3x3_head_wrw(
-                N.ptr(x), N.ptr(g), B, Cc, H, W, pad, N.ptr(part), N.ptr(g_w), N.ptr(g_b), N.stream()),
-                4 * (x.numel() + g.numel())))
-            need_w = need_b = False
-        if need_w and K == 16 and Cc in (16, 32) and WINO_ENABLED and Cc * H * W < (1 << 28):
-            # last decoder stage: K16 (pixel axis on the MFMA, persistent workgroups) instead of MIOpen's implicit GEMM
-            lib = N.lib()
-            part = torch.empty(lib.dmh_conv3x3_small_wrw_partials_size(Cc), device=g.device, dtype=torch.float32)
-            g_w = torch.empty_like(weight)
-            g_b = torch.empty(16, device=g.device, dtype=torch.float32) if need_b else None
-            N.check(_timed("conv3x3_small_wrw", lambda: lib.dmh_conv3x3_small_wrw(
-                N.ptr(x), N.ptr(g), B, Cc, H, W, pad, N.ptr(part), N.ptr(g_w), N.ptr(g_b), N.stream()),
-                4 * (x.numel() + g.numel()), 2 * 9 * 16 * Cc * g.numel() // 16))
-            need_w = need_b = False
-        if need_w and _wrw_ok(x, g, K, Cc):
-            # >= 64 channels on both sides: K18, the weight gradient in the Winograd domain on the fp32 MFMA (MIOpen: NHWC
-            # implicit GEMMs between layout transposes, with atomics); the bias gradient is a plain reduction of g
-            lib = N.lib()
-            ws = torch.empty(lib.dmh_wino_wrw_workspace_size(B, Cc, K, H, W, pad), device=g.device, dtype=torch.float32)
-            g_w = torch.empty_like(weight)
-            N.check(_timed("wino_wrw", lambda: lib.dmh_wino_wrw(N.ptr(x), N.ptr(g), B, Cc, K, H, W, pad, N.ptr(ws), N.ptr(g_w),
-                                                                N.stream()), 4 * (x.numel() + g.numel()), 18 * Cc * g.numel()))
+        if need_x:
+            g_x = _conv3x3_routed(g, weight, None, 2 - pad, backward=True)
+            need_x = g_x is None
+        route = _wrw_route(x, g, K, Cc) if need_w else None
+        if route in ("k13", "k16"):
+            g_w, g_b = _direct_wrw(x, g, weight, pad, need_b)
+        elif route == "k18":
+            g_w = _wino_wrw(x, g, K, pad)
             if need_b:
                 g_b = channel_sum(g) if K <= 65535 else g.sum((0, 2, 3))
+        if route is not None:
             need_w = need_b = False
         if need_x or need_w or need_b:
             r = torch.ops.aten.convolution_backward(g, x, weight, [K] if ctx.has_bias else None, [1, 1], [pad, pad], [1, 1],
@@ -1896,16 +1947,13 @@ class _ConvBnAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, scale, y = ctx.saved_tensors
-        B, Cc, H, W = x.shape
-        K = weight.shape[0]
         g = _c(g)
         g_pre = _relu_mask_bwd(y, g) if ctx.relu else g         # it is also the residual's gradient
         g_x = g_w = None
         need_w = ctx.needs_input_grad[1] and not ctx.params_const
         if ctx.needs_input_grad[0]:
-            if _wino_ok(B, K, Cc, H, W):
-                g_x = _wino_conv(g_pre, _wino_filter(weight, True, scale), None, Cc, 2 - ctx.pad)
-            else:
+            g_x = _conv3x3_routed(g_pre, weight, None, 2 - ctx.pad, backward=True, scale=scale, k10_only=True)
+            if g_x is None:
                 g_conv = g_pre * scale.view(1, -1, 1, 1)
                 g_x = torch.ops.aten.convolution_backward(g_conv, x, weight, None, [1, 1], [ctx.pad] * 2, [1, 1], False,
                                                           [0, 0], 1, [True, False, False])[0]
@@ -2006,9 +2054,8 @@ def reduce_conv_fwd_launch(x, weight, bias):
     b = _c(bias.detach())
     if _reduce_act_ok(B, Cc, K, H, W):
         return _k10(x, wc, None, backward=False, bias=b, flag=1, workspace=True, count_filter=True)
-    if _wino_ok(B, Cc, K, H, W):
-        z = _wino_conv(x, _wino_filter(wc, False), None, K, 1)
-    else:
+    z = _conv3x3_routed(x, wc, None, 1, k10_only=True)
+    if z is None:
         with _lib_deterministic():
             z = torch.conv2d(x, wc, None, 1, 1)
     N.check(_timed("reduce_bias_relu", lambda: N.lib().dmh_reduce_bias_relu(N.ptr(z), N.ptr(b), B, Cc, K, H * W, N.ptr(z), N.stream()),
@@ -2031,18 +2078,14 @@ def reduce_conv_bwd_launch(g, x, weight, y, need_x=True, need_params=True):
     wc = _reduce_slice(weight, Cc)
     g_x = g_w = g_b = None
     if need_x:
-        if _wino_ok(B, K, Cc, H, W):
-            g_x = _wino_conv(g_pre, _wino_filter(wc, True), None, Cc, 1)
-        else:
+        g_x = _conv3x3_routed(g_pre, wc, None, 1, backward=True, k10_only=True)
+        if g_x is None:
             with _lib_deterministic():
                 g_x = torch.ops.aten.convolution_backward(g_pre, x, wc, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
                                                           [True, False, False])[0]
     if need_params:
-        if _wrw_ok(x, g_pre, K, Cc):
-            ws = torch.empty(lib.dmh_wino_wrw_workspace_size(B, Cc, K, H, W, 1), device=g.device, dtype=torch.float32)
-            dw = torch.empty((K, Cc, 3, 3), device=g.device, dtype=torch.float32)
-            N.check(_timed("wino_wrw", lambda: lib.dmh_wino_wrw(N.ptr(x), N.ptr(g_pre), B, Cc, K, H, W, 1, N.ptr(ws), N.ptr(dw),
-                                                                N.stream()), 4 * (x.numel() + g.numel()), 18 * Cc * g.numel()))
+        if _wrw_ok(x, g_pre, K, Cc):        # the node considers K18 only (not _wrw_route's K13 / K16)
+            dw = _wino_wrw(x, g_pre, K, 1)
         else:
             with _lib_deterministic():
                 dw = _c(torch.ops.aten.convolution_backward(g_pre, x, wc, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
@@ -2517,22 +2560,11 @@ ROI_ENABLED = os.environ.get("DMH_ROI", "1") != "0"      # A/B switch: 0 = the a
 
 def _conv_any(x, weight, bias, pad, backward=False):
     """conv2d(x, weight, padding=pad) -- or, with ``backward``, the same filter's backward-data pass on a gradient x with
-    pad' = 2 - pad_forward -- on whichever hand-written kernel takes the channel counts; ATen otherwise."""
-    _, n_in, H, W = x.shape
-    n_out = weight.shape[1] if backward else weight.shape[0]
-    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-    if WINO_ENABLED and x.numel() < (1 << 30):
-        if not backward and n_out == 1 and pad == 0 and n_in % 4 == 0:
-            return _head_conv(x, weight, bias, 0)
-        if backward and n_in == 1 and pad == 2 and n_out % 4 == 0 and n_out <= 64 and Ho >= 3 and Wo >= 3:
-            return _head_conv_bwd(x, weight)
-        if _small_ok(n_in, n_out):
-            return _small_conv(x, weight, bias, pad, backward)
-        if n_in % 8 == 0 and n_in >= 24 and Ho % 2 == 0 and Wo % 2 == 0 and Ho >= 2 and Wo >= 2:
-            if n_out % 32 == 0 and n_out % 64 and n_out <= 96:
-                return _wino_conv(x, _wino32_filter(weight, backward), bias, n_out, pad, k17=True)
-            if n_out >= 64:
-                return _wino_conv(x, _wino_filter(weight, backward), bias, n_out, pad)
+    pad' = 2 - pad_forward -- on whichever hand-written kernel takes the channel counts (_conv3x3_route's ``capable_only``);
+    ATen otherwise."""
+    y = _conv3x3_routed(x, weight, bias, pad, backward, capable_only=True)
+    if y is not None:
+        return y
     if backward:
         return torch.nn.functional.conv_transpose2d(x, weight, None, 1, 2 - pad)
     return torch.conv2d(x, weight, bias, 1, pad)

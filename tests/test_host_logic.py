@@ -210,6 +210,88 @@ def test_conv_dispatch_rule_mirrors_the_launcher():
     assert not ops._small_ok(32, 32) and not ops._small_ok(64, 16)
 
 
+# ops._conv3x3_route: (B, n_in, n_out, H, W, pad, backward) of the pass -> the kernel by throughput, the same with WINO_SK off,
+# and with capable_only.  One row on each side of every rule; the expected values are what the five dispatch chains that the
+# function replaced answered for the row.
+_ROUTE_TABLE = [
+    # K10: enough work items / (item, chunk) units, few empty tiles, channels it tiles, even output
+    ((2, 64, 64, 64, 128, 1, False), "k10", None, "k10"),           # 64 regions: stream-K's 512 units, not 200 whole items
+    ((1, 64, 64, 32, 128, 1, False), None, None, "k10"),            # 8 regions: below every threshold, but K10 can run it
+    ((12, 512, 256, 10, 32, 1, False), "k10", None, "k10"),         # upconv(4,0): 60 regions, taken through stream-K only
+    ((12, 256, 512, 12, 34, 1, True), "k10", "k10", "k10"),         # 17 tile columns in 32-wide regions: 53 % filled
+    ((12, 256, 512, 10, 34, 1, True), None, None, "k10"),           # ... 44 %
+    ((12, 64, 64, 81, 256, 1, False), None, None, None),            # odd output height
+    ((12, 16, 64, 80, 256, 1, False), None, None, None),            # 16 input channels
+    ((12, 64, 96, 80, 256, 1, False), "k10", "k10", "k17"),         # 96 output channels: K10 where it fills the chip
+    # K17: 32 / 96 output channels, >= 400 items
+    ((12, 96, 32, 160, 512, 1, False), "k17", "k17", "k17"),        # upconv(1,1): not K10's (32 output channels half-fill an item)
+    ((12, 32, 96, 162, 514, 1, True), "k17", "k17", "k17"),         # its backward-data: few chunks, half-empty channel group
+    ((4, 96, 32, 104, 512, 1, False), "k17", "k17", "k17"),         # 4 x 13 x 8 = 416 items
+    ((4, 96, 32, 96, 512, 1, False), None, None, "k17"),            # 4 x 12 x 8 = 384
+    ((4, 32, 96, 104, 512, 1, True), "k17", "k17", "k17"),
+    ((4, 64, 32, 104, 512, 1, False), "k17", "k17", "k17"),
+    ((4, 24, 32, 104, 512, 1, False), None, None, "k17"),           # 24 input channels: it can, MIOpen is ahead
+    # K13: one output channel.  Forward: the strip kernel at padding 0, the tiled one from 512 tiles of 8 x 64
+    ((2, 16, 1, 34, 66, 0, False), "k13", "k13", "k13"),
+    ((2, 18, 1, 34, 66, 0, False), None, None, None),               # channels not a multiple of 4
+    ((1, 64, 1, 256, 1024, 1, False), "k13", "k13", None),          # 32 x 16 = 512 tiles
+    ((1, 64, 1, 248, 1024, 1, False), None, None, None),            # 31 x 16
+    ((12, 40, 1, 320, 1024, 1, False), None, None, None),           # channels not a multiple of 16
+    ((12, 16, 1, 320, 1024, 1, False), "k11", "k11", "k11"),        # ... below 32: K11's
+    # K13 backward-data: forward padding 0 (pad 2 in the terms of the pass), <= 64 channels out
+    ((2, 1, 64, 32, 64, 2, True), "k13", "k13", "k13"),
+    ((2, 1, 68, 32, 64, 2, True), None, None, None),
+    ((2, 1, 64, 32, 64, 1, True), None, None, None),                # forward padding 1
+    ((2, 1, 16, 32, 64, 2, True), "k13", "k13", "k13"),             # K13 before K11 where both take it
+    ((2, 1, 16, 32, 64, 1, True), "k11", "k11", "k11"),
+    # K11: few channels
+    ((2, 16, 16, 32, 64, 1, False), "k11", "k11", "k11"),
+    ((2, 32, 16, 32, 64, 1, False), "k11", "k11", "k11"),
+    ((2, 16, 1, 32, 64, 1, False), "k11", "k11", "k11"),
+    ((2, 16, 32, 32, 64, 1, True), "k11", "k11", "k11"),
+    ((2, 48, 48, 16, 32, 1, False), None, None, None),
+    ((2, 32, 32, 32, 64, 1, False), None, None, "k17"),
+    ((2, 64, 16, 32, 64, 1, False), None, None, None),
+]
+
+
+def test_conv3x3_route_table():
+    """ops._conv3x3_route, the one rule behind conv3x3, conv3x3_bn_act, the reduce node and the window path (pure host logic)."""
+    from depthmodelhardening_amd import ops
+    assert ops.WINO_SK and ops.WINO_ENABLED
+    for args, by_speed, by_speed_whole_items, capable in _ROUTE_TABLE:
+        assert ops._conv3x3_route(*args) == by_speed, args
+        assert ops._conv3x3_route(*args, capable_only=True) == capable, args
+        ops.WINO_SK = False
+        try:
+            assert ops._conv3x3_route(*args) == by_speed_whole_items, args
+            assert ops._conv3x3_route(*args, capable_only=True) == capable, args
+        finally:
+            ops.WINO_SK = True
+    ops.WINO_ENABLED = False
+    try:
+        for args, _, _, _ in _ROUTE_TABLE:
+            assert ops._conv3x3_route(*args) is None and ops._conv3x3_route(*args, capable_only=True) is None, args
+    finally:
+        ops.WINO_ENABLED = True
+    assert ops._small_ok(16, 16) and ops._small_ok(32, 16) and ops._small_ok(16, 1)
+    assert not ops._small_ok(48, 48) and not ops._small_ok(32, 32) and not ops._small_ok(64, 16)
+    assert ops._k10_channels(24, 64) and not ops._k10_channels(16, 64) and not ops._k10_channels(28, 64) and not ops._k10_channels(64, 32)
+    assert ops._k17_channels(24, 32) and ops._k17_channels(64, 96) and not ops._k17_channels(64, 64) and not ops._k17_channels(64, 160)
+
+    class Shape:
+        def __init__(self, *shape):
+            self.shape = shape
+
+        def numel(self):
+            return self.shape[0] * self.shape[1] * self.shape[2] * self.shape[3]
+    # the weight gradient of a [K, C, 3, 3] convolution with padding 1: K13 / K16 by channel counts, K18 from 1024 chunk blocks
+    for B, Cc, K, H, W, want in ((4, 64, 64, 64, 128, "k18"), (2, 64, 64, 64, 128, None), (4, 96, 32, 104, 512, "k18"),
+                                 (2, 16, 1, 32, 64, "k13"), (2, 16, 16, 32, 64, "k16"), (2, 32, 16, 32, 64, "k16"),
+                                 (2, 48, 16, 32, 64, None), (2, 48, 48, 16, 32, None), (4, 64, 64, 63, 128, None)):
+        assert ops._wrw_route(Shape(B, Cc, H, W), Shape(B, K, H, W), K, Cc) == want, (B, Cc, K, H, W)
+
+
 def test_frozen_weights_scope_and_coefficient_memo():
     import numpy as np
     import torch
@@ -434,8 +516,9 @@ def test_environment_switches_are_the_documented_ones():
 
 def test_one_launch_site_per_kernel_behind_ops_and_library():
     """torch.ops.dmh.* (library.py) and the autograd Functions (ops.py) launch through the same launchers: library.py makes no call
-    into the C library of its own, and each C entry point of the older kernels (K1-K6, the stand-alone layers) is called at one
-    place in ops.py -- a change of a C signature or of a workspace size is made once."""
+    into the C library of its own, and each C entry point of the older kernels (K1-K6, the stand-alone layers) and of the 3x3
+    convolution family (K10, K11, K13, K16, K17, K18) is called at one place in ops.py -- a change of a C signature or of a
+    workspace size is made once."""
     pkg = os.path.join(REPO, "depthmodelhardening_amd")
     ops_text, lib_text = open(os.path.join(pkg, "ops.py")).read(), open(os.path.join(pkg, "library.py")).read()
     assert "N.lib()" not in lib_text and "C.byref" not in lib_text and "import ctypes" not in lib_text
@@ -444,5 +527,7 @@ def test_one_launch_site_per_kernel_behind_ops_and_library():
                  "dmh_loss_finalize", "dmh_eot_paste_fwd", "dmh_eot_paste_bwd", "dmh_masked_sq_mean_fwd", "dmh_masked_sq_mean_bwd",
                  "dmh_gt_depth_mse_fwd", "dmh_gt_depth_mse_bwd", "dmh_pgd_linf_step", "dmh_l0_compose_fwd", "dmh_l0_compose_bwd",
                  "dmh_l0_mask_cost_fwd", "dmh_l0_mask_cost_bwd", "dmh_ssim_map", "dmh_ssim_map_bwd", "dmh_edge_smooth",
-                 "dmh_edge_smooth_bwd"):
+                 "dmh_edge_smooth_bwd",
+                 "dmh_wino_conv3x3_ws", "dmh_wino32_conv3x3_ws", "dmh_wino_conv3x3_act", "dmh_wino_conv3x3_act_ws", "dmh_conv3x3_small",
+                 "dmh_conv3x3_head", "dmh_conv3x3_head_bwd_data", "dmh_conv3x3_head_wrw", "dmh_conv3x3_small_wrw", "dmh_wino_wrw"):
         assert len(re.findall(r"\b%s\(" % name, ops_text)) == 1, name
