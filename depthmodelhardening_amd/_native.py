@@ -15,6 +15,7 @@ VARIANT_MD2, VARIANT_DH = 0, 1
 NOISE_NONE, NOISE_TENSOR, NOISE_PHILOX = 0, 1, 2
 PASTE_COMPOSITE, PASTE_WARP_ONLY = 0, 1
 SGM_COST, SGM_PATHS, SGM_SELECT, SGM_SPECKLE, SGM_ALL = 1, 2, 4, 8, 15       # DMH_SGM_*: the phases of K35
+COLORIZE_MIN_P95, COLORIZE_ZERO_REF, COLORIZE_MIN_MAX, COLORIZE_MAX_PANELS, COLORIZE_STATS = 0, 1, 2, 32, 5    # DMH_COLORIZE_* (K37)
 PIL_LANCZOS, PIL_BILINEAR, PIL_TILE_ROWS = 1, 2, 8      # PIL.Image.LANCZOS / BILINEAR; DMH_PIL_TILE_ROWS
 FIN_LOSS, FIN_LOSS_S, FIN_REPROJ_S, FIN_COUNT_S, FIN_SMOOTH_S, FIN_HINT_S, FIN_HINTCOUNT_S, FIN_SIZE = 0, 1, 5, 9, 13, 20, 24, 28
 
@@ -59,6 +60,10 @@ class WinoWtJob(C.Structure):
 class SgmParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("num_disparities", "block_size", "P1", "P2", "pre_filter_cap", "uniqueness_ratio",
                                          "disp12_max_diff", "speckle_window_size", "speckle_range", "min_disparity")]
+
+
+class ColorizePanel(C.Structure):
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("mode", C.c_int32), ("ref", C.c_int32), ("origin", C.c_int64)]
 
 
 _PtrArr = _fp * MAX_SCALES
@@ -209,6 +214,9 @@ _SIGNATURES = {
     "dmh_reduce_bwd_mask": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [_fp, _fp, _fp]),
     "dmh_reduce_bwd_finish": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp, _fp, _fp]),
     "dmh_sgm_disparity": (C.c_int, [_fp] * 3 + [C.c_int] * 3 + [C.POINTER(SgmParams), C.c_int, _fp, _fp, C.c_int64, C.c_int, _fp]),
+    "dmh_disp_colorize_ws_size": (C.c_int64, [C.c_int]),
+    "dmh_disp_colorize": (C.c_int, [_fp] + [C.c_int] * 3 + [C.POINTER(ColorizePanel)] + [C.c_int] * 5 + [C.c_float] + [_fp] * 5
+                          + [C.c_int64, C.c_int64, _fp]),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -143,14 +143,15 @@ class _Prefetcher(object):
     and uploads it on a side stream from a loader thread; ``take(k)`` returns (device buffer, sizes) once the current stream has
     been told to wait for the upload's event."""
 
-    def __init__(self, slots, device, workers):
+    def __init__(self, slots, device, workers, slot_hw=(SLOT_H, SLOT_W)):
         self.device = torch.device(device)
         self.cuda = self.device.type == "cuda"
         self.workers = ThreadPoolExecutor(max_workers=workers)
         self.loader = ThreadPoolExecutor(max_workers=1)
-        self.host = [torch.empty((slots, SLOT_H, SLOT_W, 3), dtype=torch.uint8, pin_memory=self.cuda) for _ in range(2)]
+        slot_h, slot_w = int(slot_hw[0]), int(slot_hw[1])       # the KITTI raw slot; test_simple sizes it by its folder's files
+        self.host = [torch.empty((slots, slot_h, slot_w, 3), dtype=torch.uint8, pin_memory=self.cuda) for _ in range(2)]
         self.host_np = [t.numpy() for t in self.host]          # the workers write through numpy views of the pinned buffers
-        self.dev = [torch.empty((slots, SLOT_H, SLOT_W, 3), dtype=torch.uint8, device=self.device) for _ in range(2)] if self.cuda else self.host
+        self.dev = [torch.empty((slots, slot_h, slot_w, 3), dtype=torch.uint8, device=self.device) for _ in range(2)] if self.cuda else self.host
         self.side = torch.cuda.Stream(self.device) if self.cuda else None
         self.uploaded = [None, None]     # event: the upload of the buffer has finished
         self.consumed = [None, None]     # event: the kernels that read the device buffer have been queued before it

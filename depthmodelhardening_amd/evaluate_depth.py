@@ -15,7 +15,7 @@ import torch
 from . import ops
 from .datasets import make_object
 from .layers import disp_to_depth
-from .my_utils import to_device_async
+from .my_utils import eval_depth_diff_jcl, to_device_async
 from .torchattacks import (PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_arbi, Phy_obj_atk_guassian, Phy_obj_atk_l0,
                            Phy_obj_atk_l2, Phy_obj_atk_light, Phy_obj_atk_Square, Phy_obj_atk_vanila)
 
@@ -37,7 +37,7 @@ def compute_errors(gt, pred, mask=None):
             np.sqrt((d ** 2 * w).sum() / total), np.sqrt(((np.log(gt) - np.log(pred)) ** 2 * w).sum() / total), a1, a2, a3)
 
 
-def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
+def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None, figure_path=None):
     """Attack the model on ``eval_count`` scene batches and report the mean of the eight metrics between the
     benign and the attacked depth (object-masked for the object attacks).  ``scene_source(n)`` yields n scenes
     [n,3,375,1242]; the KITTI-object loader of the reference (:157-170, starting at index 42) is replaced by it.
@@ -45,7 +45,10 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
     they are refused like every unserved ``norm_type``, as they were before the rows existed.  In the same way the "Square" row
     is served when ``args['square_attack']`` is true (``query_patch``: "candidate", or "best" for the reference's line
     phy_obj_atk_square.py:295; ``graph_attack``: replay the query from a HIP graph), and the "l_2" row when ``args['l2_attack']``
-    is true (``epsilon``, ``alpha`` -- which the attack ignores -- and ``step`` as at :134-137; ``graph_attack`` as above)."""
+    is true (``epsilon``, ``alpha`` -- which the attack ignores -- and ``step`` as at :134-137; ``graph_attack`` as above).
+    ``figure_path``: the first batch's first scene is saved there as ``my_utils.eval_depth_diff_jcl``'s figure of the attacked image, its
+    disparity and the difference to the benign one, from the disparities evaluated here (the reference's ``result_img_atk.save`` at evaluate_depth_physical.py:160-163,
+    without its ``raise NameError()``); None changes nothing."""
     device = next(model2atk.parameters()).device
     obj_tensor, mask_tensor = make_object(device)
     if args['norm_type'] == "l_inf":
@@ -99,6 +102,8 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None):
             disp_atk = model2atk(adv_images)
         errors.append(ops.masked_depth_errors(disp_gt, disp_atk, obj_masks_out, 0.1, 100, STEREO_SCALE_FACTOR,
                                               MIN_DEPTH, MAX_DEPTH))
+        if figure_path is not None and i == 0:
+            eval_depth_diff_jcl(adv_images[[0]], ben_images[[0]], model2atk, disp1=disp_atk[[0]], disp2=disp_gt[[0]]).save(figure_path)
     errors = torch.stack(errors)
     mean_errors, max_errors = errors.mean(0).cpu().numpy(), errors.max(0)[0].cpu().numpy()
     names = ("abs_err", "abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")

@@ -43,6 +43,8 @@ the same bits.  There is no CPU kernel behind any of them: CPU tensors are rejec
                                                                                        + dmh::reduce_conv_degenerate_bwd
     dmh::sgm_disparity        the stereo matchers of depth-hints/precompute_depth_hints.py:42-63,128-147 as this package's own integer
                               semi-global matcher (not OpenCV's output)   (K35, no autograd)
+    dmh::disp_colorize        MD2/test_simple.py:136-156, my_utils.py:54-67 (bilinear resize, np.percentile, Normalize + magma, uint8)
+                              (K37, no autograd)
 """
 from typing import List, Optional, Tuple
 
@@ -719,6 +721,25 @@ def _(base, lookup, params, reverse=None, workspace_cap=ops.SGM_WORKSPACE_CAP):
     return base.new_empty((B, len(params) // len(ops._SGM_KEYS), H, W), dtype=torch.int16)
 
 
+# ---------------------------------------------------------------------------------------------------------------- K37
+@custom_op("dmh::disp_colorize", mutates_args=())
+def disp_colorize(maps: torch.Tensor, panels: List[int], out_h: int, out_w: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(uint8 [P, out_h, out_w, 3], the coloured float maps [P, out_h, out_w], float32 [P, 5] statistics).  ``panels``: a, b, mode
+    number, ref of every panel, flattened (``ops.COLORIZE_MODES``).  Figures carry no gradient: there is no autograd formula."""
+    ops._need_cuda(maps)
+    if len(panels) == 0 or len(panels) % 4 != 0:
+        raise RuntimeError("disp_colorize: panels must hold four integers per panel; got %d" % len(panels))
+    out = ops.disp_colorize(maps, [tuple(panels[i:i + 4]) for i in range(0, len(panels), 4)], (out_h, out_w), return_map=True)
+    return out.rgb, out.map, out.stats
+
+
+@disp_colorize.register_fake
+def _(maps, panels, out_h, out_w):
+    P = len(panels) // 4
+    return (maps.new_empty((P, out_h, out_w, 3), dtype=torch.uint8), maps.new_empty((P, out_h, out_w)),
+            maps.new_empty((P, ops.N.COLORIZE_STATS)))
+
+
 def sgm_params_flat(params):
     """A list of parameter dicts as the flat integer list ``torch.ops.dmh.sgm_disparity`` takes."""
     return [int(v) for t in ops._sgm_params(params) for v in t]
@@ -736,4 +757,4 @@ OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
        "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity",
-       "reduce_conv_degenerate", "reduce_conv_degenerate_bwd")
+       "reduce_conv_degenerate", "reduce_conv_degenerate_bwd", "disp_colorize")

@@ -4421,3 +4421,180 @@ def sgm_disparity(base, lookup, params, reverse=None, workspace_cap=SGM_WORKSPAC
         N.ptr(base), N.ptr(lookup), N.ptr(None if reverse is None else _c(reverse)), B, H, W, native, len(plist),
         C.c_void_p(out.data_ptr()), N.ptr(ws), int(nbytes), int(phases), N.stream()), B * H * W * (6 + 2 * len(plist))))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- K37
+COLORIZE_MODES = {"min_p95": N.COLORIZE_MIN_P95, "zero_ref": N.COLORIZE_ZERO_REF, "min_max": N.COLORIZE_MIN_MAX}
+COLORIZE_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "magma_256.txt")
+ColorizeOut = namedtuple("ColorizeOut", ["rgb", "map", "stats"])
+_colorize_table_host = None
+_colorize_table_cache = _UploadCache(8, "disp_colorize: the first call on a device uploads the colour table; make it once before "
+                                        "capturing a graph")
+
+
+def magma_table():
+    """(matplotlib's magma at 256 entries * 255).astype(uint8) as uint8 [256, 3]: data/magma_256.txt (256 lines "r g b"), written once by
+    tools/make_goldens_colorize.py.  matplotlib is not imported."""
+    global _colorize_table_host
+    if _colorize_table_host is None:
+        with open(COLORIZE_TABLE_PATH) as f:
+            rows = [[int(v) for v in line.split()] for line in f if line.strip() and not line.startswith("#")]
+        if len(rows) != 256 or any(len(r) != 3 or min(r) < 0 or max(r) > 255 for r in rows):
+            raise RuntimeError("%s must hold 256 lines of three bytes" % COLORIZE_TABLE_PATH)
+        _colorize_table_host = np.array(rows, dtype=np.uint8)
+    return _colorize_table_host
+
+
+def percentile_plan(n, q=95):
+    """(lo, hi, g) of ``np.percentile(a, q)`` for a float32 ``a`` of n elements (numpy 2: float32 throughout): the result is
+    ``lerp(sorted[lo], sorted[hi], g)``.  numpy's own expressions (the "linear" method's virtual index ``(n - 1) * quantiles`` and
+    the bounds of ``_get_indexes``), evaluated in float32 as numpy evaluates them -- they depend on n and q only."""
+    n = int(n)
+    if n < 1:
+        raise RuntimeError("percentile_plan: n must be positive; got %d" % n)
+    quant = np.asanyarray(np.true_divide(q, np.float32(100)), dtype=np.float32)
+    if not 0 <= float(quant) <= 1:
+        raise RuntimeError("percentile_plan: q must lie in [0, 100]; got %r" % (q,))
+    vi = np.asanyarray((n - 1) * quant)
+    if vi.dtype != np.float32:
+        raise RuntimeError("percentile_plan: the virtual index left float32 (%s)" % vi.dtype)
+    if vi >= n - 1:
+        return n - 1, n - 1, 0.0
+    if vi < 0:
+        return 0, 0, 0.0
+    lo = np.floor(vi)
+    return int(lo), int(lo) + 1, float(np.float32(vi - lo))
+
+
+def _colorize_panels(panels, n_src):
+    """Panels as (a, b, mode number, ref) tuples; the default is one ``min_p95`` panel per map."""
+    if panels is None:
+        panels = [(i, -1, "min_p95", i) for i in range(n_src)]
+    out = []
+    for i, pn in enumerate(panels):
+        if len(pn) != 4:
+            raise RuntimeError("disp_colorize: a panel is (a, b, mode, ref); got %r" % (pn,))
+        a, b, mode, ref = pn
+        mode = COLORIZE_MODES.get(mode, mode)
+        if mode not in COLORIZE_MODES.values():
+            raise RuntimeError("disp_colorize: mode must be one of %s; got %r" % (sorted(COLORIZE_MODES), pn[2]))
+        a, b, ref = int(a), int(b), int(ref)
+        if not (0 <= a < n_src and -1 <= b < n_src):
+            raise RuntimeError("disp_colorize: panel %d names a map outside the batch of %d: a = %d, b = %d" % (i, n_src, a, b))
+        out.append((a, b, int(mode), ref))
+    if not 1 <= len(out) <= N.COLORIZE_MAX_PANELS:
+        raise RuntimeError("disp_colorize: 1 <= panels <= %d; got %d" % (N.COLORIZE_MAX_PANELS, len(out)))
+    for i, (a, b, mode, ref) in enumerate(out):
+        if mode == N.COLORIZE_ZERO_REF and not 0 <= ref < len(out):
+            raise RuntimeError("disp_colorize: panel %d takes its limit from panel %d, outside the %d panels" % (i, ref, len(out)))
+    return out
+
+
+def _colorize_check(maps, panels, out_size, out, origins):
+    if not (torch.is_tensor(maps) and maps.dtype == torch.float32 and maps.dim() == 3 and maps.numel() > 0):
+        raise RuntimeError("disp_colorize: maps must be a non-empty float32 tensor [B, h, w]; got %s %s"
+                           % (getattr(maps, "dtype", type(maps)), tuple(getattr(maps, "shape", ()))))
+    B, h, w = (int(v) for v in maps.shape)
+    H, W = (h, w) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if H < 1 or W < 1:
+        raise RuntimeError("disp_colorize: out_size must be a positive (H, W); got %s" % (out_size,))
+    panels = _colorize_panels(panels, B)
+    if (out is None) != (origins is None):
+        raise RuntimeError("disp_colorize: out (a uint8 mosaic [Hm, Wm, 3]) and origins (one (y, x) per panel) go together")
+    offsets, pitch = [i * H * W * 3 for i in range(len(panels))], W * 3
+    if out is not None:
+        if not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.dim() == 3 and out.shape[2] == 3 and out.is_contiguous()
+                and out.device == maps.device):
+            raise RuntimeError("disp_colorize: out must be a contiguous uint8 tensor [Hm, Wm, 3] on the maps' device")
+        Hm, Wm = int(out.shape[0]), int(out.shape[1])
+        if len(origins) != len(panels):
+            raise RuntimeError("disp_colorize: one origin per panel (%d); got %d" % (len(panels), len(origins)))
+        offsets, pitch = [], Wm * 3
+        for y, x in origins:
+            y, x = int(y), int(x)
+            if not (0 <= y and y + H <= Hm and 0 <= x and x + W <= Wm):
+                raise RuntimeError("disp_colorize: a %d x %d panel at (%d, %d) leaves the %d x %d mosaic" % (H, W, y, x, Hm, Wm))
+            offsets.append((y * Wm + x) * 3)
+    return B, h, w, H, W, panels, offsets, pitch
+
+
+def colorize_bytes_host(a, vmin, vmax):
+    """The bytes of ``(ScalarMappable(Normalize(vmin, vmax), 'magma').to_rgba(a)[..., :3] * 255).astype(uint8)`` for a float32
+    array: float32 throughout, the index 0 where 256 x < 0, 255 where 256 x >= 256, trunc(256 x) otherwise."""
+    a, vmin, vmax = np.asarray(a, dtype=np.float32), np.float32(vmin), np.float32(vmax)
+    with np.errstate(all="ignore"):
+        x = np.zeros_like(a) if vmin == vmax else (a - vmin) / (vmax - vmin)
+        xa = x * np.float32(256)
+        idx = np.where(xa < 0, 0, np.where(xa >= 256, 255, np.trunc(xa))).astype(np.int64)
+    return magma_table()[idx]
+
+
+def disp_colorize_host(maps, panels=None, out_size=None, out=None, origins=None, return_map=False, q=95):
+    """K37's numpy twin, the arithmetic stated in csrc/disp_colorize.hip: sort instead of the radix select, numpy's float32 lerp,
+    float32 limits and index, the packaged table.  With ``out_size`` the map is resized by torch's own float32 CPU
+    ``F.interpolate(bilinear, align_corners=False)``, which is NOT bit-equal to the kernel's resize (torch's back ends differ among
+    themselves): colour the kernel's returned map (no ``out_size``) to compare bytes."""
+    B, h, w, H, W, panels, offsets, pitch = _colorize_check(maps, panels, out_size, out, origins)
+    src = maps.detach().cpu().numpy()
+    lo, hi, g = percentile_plan(H * W, q)
+    g = np.float32(g)
+    made, stats = [], np.zeros((len(panels), N.COLORIZE_STATS), dtype=np.float32)
+    for i, (a, b, mode, ref) in enumerate(panels):
+        m = src[a] if b < 0 else np.abs(src[a] - src[b])
+        if (H, W) != (h, w):
+            m = torch.nn.functional.interpolate(torch.from_numpy(np.ascontiguousarray(m))[None, None], (H, W), mode="bilinear",
+                                                align_corners=False)[0, 0].numpy()
+        s = np.sort(m, axis=None)
+        a_lo, a_hi = s[lo], s[hi]
+        d = a_hi - a_lo
+        p = a_hi - d * (1 - g) if g >= 0.5 else a_lo + d * g
+        stats[i] = (s[0], s[-1], a_lo, a_hi, p)
+        made.append(m)
+    rgb = np.empty((len(panels), H, W, 3), dtype=np.uint8)
+    for i, (a, b, mode, ref) in enumerate(panels):
+        vmin, vmax = ((stats[i, 0], stats[i, 4]) if mode == N.COLORIZE_MIN_P95 else
+                      (np.float32(0), stats[ref, 4]) if mode == N.COLORIZE_ZERO_REF else (stats[i, 0], stats[i, 1]))
+        rgb[i] = colorize_bytes_host(made[i], vmin, vmax)
+    if out is not None:
+        view = out.numpy()
+        for i, (y, x) in enumerate(origins):
+            view[int(y):int(y) + H, int(x):int(x) + W] = rgb[i]
+    return ColorizeOut(out if out is not None else torch.from_numpy(rgb), torch.from_numpy(np.stack(made)) if return_map else None,
+                       torch.from_numpy(stats))
+
+
+def disp_colorize(maps, panels=None, out_size=None, out=None, origins=None, return_map=False, q=95):
+    """K37: float maps to magma-coloured bytes, as MD2/test_simple.py:136-156 and the figures of my_utils.py:43-105 make them on
+    the host, in one fixed chain of launches with no host read.
+
+    maps      float32 [B, h, w], finite (disparities).
+    panels    what is coloured: a sequence of (a, b, mode, ref) -- maps[a], or |maps[a] - maps[b]| when b >= 0, with the limits
+              "min_p95" (the panel's own minimum and q-th percentile), "zero_ref" (0 and the percentile of panel ``ref``) or
+              "min_max" (the panel's minimum and maximum).  Default: every map, "min_p95".
+    out_size  (H, W): the source is resized first (bilinear, align_corners=False semantics); default (h, w), the input bits.
+    out, origins  a uint8 mosaic [Hm, Wm, 3] and one (y, x) per panel: the panels are written into their places, nothing else
+              is touched.  Without them a new uint8 [P, H, W, 3].
+    Returns   ColorizeOut(rgb, map, stats): the bytes (``out`` when given), the coloured float maps [P, H, W] with ``return_map``
+              (None otherwise), and float32 [P, 5] = min, max, sorted[lo], sorted[hi], the percentile as ``np.percentile`` gives it.
+
+    CPU tensors run ``disp_colorize_host``."""
+    B, h, w, H, W, panels, offsets, pitch = _colorize_check(maps, panels, out_size, out, origins)
+    dev = maps.device
+    if dev.type != "cuda":
+        return disp_colorize_host(maps, panels, out_size, out, origins, return_map, q)
+    P = len(panels)
+    if P * H * W >= 2 ** 31 or B * h * w >= 2 ** 31:
+        raise RuntimeError("disp_colorize: B h w and panels H W must stay below 2^31; got %d x %d x %d -> %d x %d x %d"
+                           % (B, h, w, P, H, W))
+    lo, hi, g = percentile_plan(H * W, q)
+    table = _colorize_table_cache.get(str(dev), dev, lambda: ([torch.from_numpy(magma_table().copy())], None))[0][0]
+    maps = _c(maps)
+    native = (N.ColorizePanel * P)(*[N.ColorizePanel(a, b, mode, ref, off) for (a, b, mode, ref), off in zip(panels, offsets)])
+    rgb = out if out is not None else torch.empty((P, H, W, 3), device=dev, dtype=torch.uint8)
+    fmap = torch.empty((P, H, W), device=dev, dtype=torch.float32)
+    stats = torch.empty((P, N.COLORIZE_STATS), device=dev, dtype=torch.float32)
+    ws = torch.empty(N.lib().dmh_disp_colorize_ws_size(P), device=dev, dtype=torch.int32)
+    N.check(_timed("disp_colorize", lambda: N.lib().dmh_disp_colorize(
+        N.ptr(maps), B, h, w, native, P, H, W, lo, hi, g, N.ptr(table), N.ptr(fmap), N.ptr(ws), N.ptr(stats), N.ptr(rgb),
+        rgb.numel(), pitch, N.stream()), 4 * P * (4 * H * W + h * w) + 3 * P * H * W))
+    return ColorizeOut(rgb, fmap if return_map else None, stats)

@@ -998,6 +998,40 @@ int dmh_reduce_bwd_mask(const float* g, const float* y, int B, int C, int K, int
 int dmh_reduce_bwd_finish(const float* partials, const float* dw, int B, int C, int K, int D, int HW, float* g_bias,
                           float* g_weight, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K37 Float maps to magma-coloured bytes (MD2/test_simple.py:136-156, my_utils.py:43-105): source, percentile, limits, colour.
+ *   src      float [n_src][h][w]: the maps (finite values).
+ *   panels   HOST array [n_panels] (copied into the launches' arguments; n_panels <= DMH_COLORIZE_MAX_PANELS).  Per panel:
+ *            a, b    the panel shows src[a] (b = -1) or |src[a] - src[b]|, resized to H x W with the arithmetic of
+ *                    F.interpolate(mode="bilinear", align_corners=False) when (H, W) != (h, w) -- the input bits otherwise;
+ *            mode    DMH_COLORIZE_MIN_P95: vmin = the panel's minimum, vmax = its percentile;
+ *                    DMH_COLORIZE_ZERO_REF: vmin = 0, vmax = the percentile of panel ``ref``;
+ *                    DMH_COLORIZE_MIN_MAX: the panel's minimum and maximum;
+ *            origin  byte offset of the panel's first pixel in out; pixel (y, x) goes to out + origin + y pitch + 3 x.
+ *   lo, hi, g  numpy's virtual index of H W elements: the percentile is lerp(sorted[lo], sorted[hi], g) in float32 as
+ *            np.percentile computes it (hi = lo or lo + 1; 0 <= g < 1).
+ *   table    uint8 [256][3]: the colour table (device).
+ *   map      float [n_panels][H][W]: written with the maps that are coloured.
+ *   ws       uint32 [dmh_disp_colorize_ws_size(n_panels)]: histograms and selection state, zeroed by the call.
+ *   stats    float [n_panels][DMH_COLORIZE_STATS]: min, max, sorted[lo], sorted[hi], the percentile.
+ *   out      uint8 [out_len]: only the panels' bytes are written.  index = 0 where 256 x < 0, 255 where 256 x >= 256, trunc(256 x)
+ *            otherwise, x = (a - vmin) / (vmax - vmin), 0 when vmin == vmax.
+ * A fixed number of launches, no host read between them, integer atomics only: two runs give the same bits.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_COLORIZE_MAX_PANELS 32
+#define DMH_COLORIZE_STATS 5
+#define DMH_COLORIZE_MIN_P95 0
+#define DMH_COLORIZE_ZERO_REF 1
+#define DMH_COLORIZE_MIN_MAX 2
+typedef struct {
+    int32_t a, b, mode, ref;
+    int64_t origin;
+} dmh_colorize_panel;
+int64_t dmh_disp_colorize_ws_size(int n_panels);
+int dmh_disp_colorize(const float* src, int n_src, int h, int w, const dmh_colorize_panel* panels, int n_panels, int H, int W,
+                      int lo, int hi, float g, const uint8_t* table, float* map, uint32_t* ws, float* stats, uint8_t* out,
+                      int64_t out_len, int64_t pitch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
