@@ -197,6 +197,7 @@ _SIGNATURES = {
     "dmh_pose_head_fwd": (C.c_int, [_fp] + [C.c_int] * 4 + [C.c_float, C.c_uint32] + [_fp] * 4),
     "dmh_pose_head_bwd": (C.c_int, [_fp] * 5 + [C.c_int] * 4 + [C.c_float, C.c_uint32, _fp, _fp]),
     "dmh_cost_volume_fwd": (C.c_int, [_fp] * 6 + [C.c_int] * 9 + [_fp] * 7),
+    "dmh_cost_volume_bwd": (C.c_int, [_fp] * 6 + [C.c_int] * 7 + [_fp, C.c_int64] + [_fp] * 6),
     "dmh_pil_resample_tables_size": (C.c_int64, [C.c_int] * 3),
     "dmh_pil_resample": (C.c_int, [_fp, C.c_int] + [C.c_int64] * 4 + [C.c_int, C.c_int, _fp, C.c_int64, _fp, _fp] + [C.c_int] * 5
                          + [_fp] * 3),

@@ -18,7 +18,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdmh_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 
-SOURCES = ["runtime.hip", "photo_loss.hip", "warp_view.hip", "smooth_loss.hip", "eot_paste.hip", "attack_ops.hip", "apgd_ops.hip", "l0_fused.hip", "tube_light.hip", "gauss_blur.hip", "square_search.hip", "l2_step.hip", "eigen_eval.hip", "decoder_glue.hip", "roi_glue.hip", "roi_encoder.hip", "encoder_glue.hip", "wino_conv.hip", "wino32_conv.hip", "wino_wrw.hip", "small_conv.hip", "small_wrw.hip", "stem_conv_bwd.hip", "stem_conv_fwd.hip", "down_conv.hip", "down_wrw.hip", "stem_wrw.hip", "head_conv.hip", "layers_ops.hip", "pose_head.hip", "cost_volume.hip", "pil_resample.hip", "velo_depth.hip", "color_jitter.hip", "depth_hints.hip", "sgm_stereo.hip", "reduce_node.hip", "disp_colorize.hip"]
+SOURCES = ["runtime.hip", "photo_loss.hip", "warp_view.hip", "smooth_loss.hip", "eot_paste.hip", "attack_ops.hip", "apgd_ops.hip", "l0_fused.hip", "tube_light.hip", "gauss_blur.hip", "square_search.hip", "l2_step.hip", "eigen_eval.hip", "decoder_glue.hip", "roi_glue.hip", "roi_encoder.hip", "encoder_glue.hip", "wino_conv.hip", "wino32_conv.hip", "wino_wrw.hip", "small_conv.hip", "small_wrw.hip", "stem_conv_bwd.hip", "stem_conv_fwd.hip", "down_conv.hip", "down_wrw.hip", "stem_wrw.hip", "head_conv.hip", "layers_ops.hip", "pose_head.hip", "cost_volume.hip", "cost_volume_bwd.hip", "pil_resample.hip", "velo_depth.hip", "color_jitter.hip", "depth_hints.hip", "sgm_stereo.hip", "reduce_node.hip", "disp_colorize.hip"]
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent fp32 ops into v_pk_*_f32 and pays for it with register-pair
 # shuffles (v_mov): on the fused loss kernel that was +30 % VALU instructions and +50 VGPRs (2 -> 4 waves/SIMD without it)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-slp-vectorize",
@@ -55,7 +55,7 @@ def build(force=False, verbose=True):
 
 def _build_locked(force, verbose):
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.hpp"), os.path.join(INCLUDE, "dmh_hip.h")]
+    headers = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "cost_volume_pos.hpp"), os.path.join(INCLUDE, "dmh_hip.h")]
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
@@ -106,7 +106,7 @@ def build_asan(verbose=False, driver_name="host_checks"):
     flags = ["--offload-arch=gfx950", "--offload-host-only", "--offload-new-driver", "-O1", "-g", "-fsanitize=address",
              "-fno-omit-frame-pointer",
              "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I" + INCLUDE]
-    headers = [os.path.join(CSRC, "common.hpp"), os.path.join(INCLUDE, "dmh_hip.h")]
+    headers = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "cost_volume_pos.hpp"), os.path.join(INCLUDE, "dmh_hip.h")]
 
     def run(cmd):
         if verbose:

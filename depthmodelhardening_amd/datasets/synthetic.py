@@ -137,6 +137,13 @@ class SyntheticKITTIDataset(object):
         idx = to_device_async([self.rng.randrange(self.pool_size) for _ in range(n)], self.device, torch.int64)
         return self.raw_left.index_select(0, idx)
 
+    def next_scene_pairs(self, n, shift=12, gain=0.95):
+        """(n attack scenes, their lookup frames), both [n,3,375,1242]: the scenes of ``next_scenes(n)`` (the same draws) and,
+        as the previous frame of each, the scene rolled ``shift`` columns to the right and dimmed by ``gain`` -- a deterministic
+        stand-in with matching features, as the 48 x 96 fixture of the cost-volume tests makes its lookup frame."""
+        scenes = self.next_scenes(n)
+        return scenes, torch.roll(scenes, int(shift), dims=3) * gain
+
     def begin_epoch(self):
         """Epoch boundary.  With ``reference_stale_patch`` the synthesis keeps pasting the patch as it stood here until
         the next epoch: the reference's DataLoader workers are forked when ``enumerate(self.train_loader)`` creates the

@@ -84,20 +84,25 @@ class ManyDepthModelWrapper(DepthModelWrapper):
         self.register_buffer("invK", invK, persistent=False)
         self.register_buffer("zero_pose", torch.zeros([1, 1, 4, 4]), persistent=False)
 
-    def forward(self, input_image):
+    def forward(self, input_image, lookup_images=None, poses=None):
+        """One argument: the single-frame call above.  With ``lookup_images`` [B,L,3,H,W] and ``poses`` [Bp,L,4,4] (current camera
+        -> lookup camera, translation in the network's units) the encoder's multi-frame form runs; whether a gradient flows through
+        the matching volume is the encoder's ``matching_grad``."""
         bs = input_image.shape[0]
-        feats, _, _ = self.encoder(input_image, None, self.zero_pose, self.K.expand(bs, 4, 4), self.invK.expand(bs, 4, 4),
-                                   self.min_depth_bin, self.max_depth_bin)
+        if lookup_images is not None and poses is None:
+            raise RuntimeError("ManyDepthModelWrapper: lookup_images need poses [Bp,L,4,4]")
+        feats, _, _ = self.encoder(input_image, lookup_images, self.zero_pose if lookup_images is None else poses,
+                                   self.K.expand(bs, 4, 4), self.invK.expand(bs, 4, 4), self.min_depth_bin, self.max_depth_bin)
         if feats[-1].is_cuda and hasattr(self.decoder, "_forward_fused"):
             disp = self.decoder(feats, only_scales=(0,))[("disp", 0)]
         else:
             disp = self.decoder(feats)[("disp", 0)]
         return disp / MANYDEPTH_DISP_SCALE
 
-    def masked_sq_mean(self, input_image, mask, plan=None, tab=None, clean=None, negate=False):
+    def masked_sq_mean(self, input_image, mask, plan=None, tab=None, clean=None, negate=False, lookup_images=None, poses=None):
         """mean((disp_0 / 8.6437 * mask)^2) on the whole frame: the windowed path (K19) is not extended to the cost-volume
-        encoder, so ``plan`` / ``tab`` / ``clean`` are accepted and ignored."""
-        disp = self.forward(input_image)
+        encoder, so ``plan`` / ``tab`` / ``clean`` are accepted and ignored.  ``lookup_images`` / ``poses``: as forward."""
+        disp = self.forward(input_image) if lookup_images is None else self.forward(input_image, lookup_images, poses)
         if disp.is_cuda:
             from . import ops
             cost = ops.masked_sq_mean(disp, mask)

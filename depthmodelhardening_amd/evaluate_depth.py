@@ -17,7 +17,7 @@ from .datasets import make_object
 from .layers import disp_to_depth
 from .my_utils import eval_depth_diff_jcl, to_device_async
 from .torchattacks import (PGD_depth, Phy_obj_atk, Phy_obj_atk_APGD, Phy_obj_atk_arbi, Phy_obj_atk_guassian, Phy_obj_atk_l0,
-                           Phy_obj_atk_l2, Phy_obj_atk_light, Phy_obj_atk_Square, Phy_obj_atk_vanila)
+                           Phy_obj_atk_l2, Phy_obj_atk_light, Phy_obj_atk_mf, Phy_obj_atk_Square, Phy_obj_atk_vanila)
 
 STEREO_SCALE_FACTOR = 5.4
 MIN_DEPTH = 1e-3
@@ -46,12 +46,23 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None, figure_p
     is served when ``args['square_attack']`` is true (``query_patch``: "candidate", or "best" for the reference's line
     phy_obj_atk_square.py:295; ``graph_attack``: replay the query from a HIP graph), and the "l_2" row when ``args['l2_attack']``
     is true (``epsilon``, ``alpha`` -- which the attack ignores -- and ``step`` as at :134-137; ``graph_attack`` as above).
+    ``args['lookup'] = {"tz": metres, "matching_grad": "none" | "current" | "full", "pose_translation_scale": 1.0}`` with ``norm_type``
+    "l_inf" runs ``Phy_obj_atk_mf`` on a multi-frame model: the lookup camera stands ``tz`` behind the current one, ``scene_source(n)``
+    then yields (scenes, their previous frames) -- the synthetic source's ``next_scene_pairs`` -- and both depths are evaluated
+    with the lookup frames (``figure_path`` shows those disparities).  Without the key nothing changes.
     ``figure_path``: the first batch's first scene is saved there as ``my_utils.eval_depth_diff_jcl``'s figure of the attacked image, its
     disparity and the difference to the benign one, from the disparities evaluated here (the reference's ``result_img_atk.save`` at evaluate_depth_physical.py:160-163,
     without its ``raise NameError()``); None changes nothing."""
     device = next(model2atk.parameters()).device
     obj_tensor, mask_tensor = make_object(device)
-    if args['norm_type'] == "l_inf":
+    lookup = args.get('lookup') if args['norm_type'] == "l_inf" else None
+    if lookup is not None:          # the multi-frame attack (this project's addition): the object in the current and the lookup frame
+        depth_atk = Phy_obj_atk_mf(model2atk, obj_tensor, mask_tensor, eps=args['epsilon'], alpha=args['alpha'], steps=args['step'],
+                                   matching_grad=lookup.get('matching_grad', 'full'),
+                                   pose_translation_scale=lookup.get('pose_translation_scale', 1.0))
+        T_lookup = np.eye(4)
+        T_lookup[2, 3] = float(lookup['tz'])
+    elif args['norm_type'] == "l_inf":
         depth_atk = Phy_obj_atk(model2atk, obj_tensor, mask_tensor, eps=args['epsilon'], alpha=args['alpha'],
                                 steps=args['step'])
     elif args['norm_type'] == "l_0":
@@ -83,11 +94,19 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None, figure_p
     if scene_source is None:
         from .datasets import SyntheticKITTIDataset
         data = SyntheticKITTIDataset(320, 1024, [0, "s"], 4, 1 << 30, device, seed=17, pool=max(8, args['batch_size']))
-        scene_source = data.next_scenes
+        scene_source = data.next_scene_pairs if lookup is not None else data.next_scenes
     errors = []
     for i in range(eval_count):
         scene_img = scene_source(args['batch_size'])
-        if args['norm_type'] == "image":
+        if lookup is not None:      # the source yields (scenes, their previous frames); both depths are the multi-frame model's
+            scene_img, lookup_img = scene_img
+            adv_images, ben_images, obj_masks_out, _ = depth_atk(scene_img, args['batch_size'], lookup_images=lookup_img,
+                                                                 T_lookup=T_lookup, eval=True)
+            poses = depth_atk.network_pose(T_lookup, args['batch_size'])
+            with torch.no_grad():
+                disp_gt = model2atk(ben_images, lookup_images=depth_atk.last_lookup_scenes_ben.unsqueeze(1), poses=poses)
+                disp_atk = model2atk(adv_images, lookup_images=depth_atk.last_lookup_scenes.unsqueeze(1), poses=poses)
+        elif args['norm_type'] == "image":
             adv_images, ben_images = depth_atk(scene_img)
             obj_masks_out = None
         elif args['norm_type'] == "light":      # :178-182: the first batch runs the search, the others paste what it found
@@ -97,9 +116,10 @@ def evaluate_attacks(model2atk, args, eval_count=25, scene_source=None, figure_p
                 adv_images, ben_images, obj_masks_out, _ = vanila_atk(scene_img, obj_img_adv, args['batch_size'], eval=True)
         else:
             adv_images, ben_images, obj_masks_out, _ = depth_atk(scene_img, args['batch_size'], eval=True)
-        with torch.no_grad():
-            disp_gt = model2atk(ben_images)
-            disp_atk = model2atk(adv_images)
+        if lookup is None:
+            with torch.no_grad():
+                disp_gt = model2atk(ben_images)
+                disp_atk = model2atk(adv_images)
         errors.append(ops.masked_depth_errors(disp_gt, disp_atk, obj_masks_out, 0.1, 100, STEREO_SCALE_FACTOR,
                                               MIN_DEPTH, MAX_DEPTH))
         if figure_path is not None and i == 0:

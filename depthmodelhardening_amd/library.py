@@ -34,6 +34,7 @@ the same bits.  There is no CPU kernel behind any of them: CPU tensors are rejec
     dmh::pose_head            MD2/networks/pose_decoder.py:47-52 + MD2/layers.py:28-103   (K29) + dmh::pose_head_bwd
     dmh::cost_volume          manydepth2/networks/resnet_encoder.py:157-236,258-265,294-296   (K30, forward only)
     dmh::cost_volume_into     the same, cost_volume * confidence written into channels 64 .. of ``buffer``   (K30, in place)
+    dmh::cost_volume_stack    cat([features, cost_volume * confidence], 1) with gradient; no counterpart in the reference   (K30 + K38)
     dmh::pil_resample         MD2/datasets/mono_dataset.py:100-104,119-144 (PIL.Image.resize, 8-bit, bit for bit)   (K31, no autograd)
     dmh::velo_depth_map       MD2/kitti_utils.py:46-98 + datasets/kitti_dataset.py:70-85 (generate_depth_map, float32-equal) (K32, no autograd)
     dmh::color_jitter         MD2/datasets/mono_dataset.py:344-348,133,144 (torchvision 0.8.2 ColorJitter on 8-bit PIL images, Pillow's bytes) (K33, no autograd)
@@ -593,6 +594,59 @@ def _(current_feats, lookup_feats, poses, K, invK, depth_bins, buffer, set_missi
     return current_feats.new_empty((B, H, W)), current_feats.new_empty((B, H, W), dtype=torch.int32)
 
 
+# ---------------------------------------------------------------------------------------------------------------- K38
+@custom_op("dmh::cost_volume_stack", mutates_args=())
+def cost_volume_stack(current_feats: torch.Tensor, lookup_feats: torch.Tensor, poses: torch.Tensor, K: torch.Tensor, invK: torch.Tensor,
+                      depth_bins: torch.Tensor, set_missing_to_max: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(stacked [B, 64 + D, H, W], confidence, argmin); differentiable w.r.t. the two feature tensors through ``stacked`` (K38)."""
+    for t in (current_feats, lookup_feats, poses, K, invK, depth_bins):
+        ops._need_cuda(t)
+    return ops.cost_volume_stack_fwd_launch(_cu(current_feats), _cu(lookup_feats), poses, K, invK, depth_bins, set_missing_to_max)
+
+
+@cost_volume_stack.register_fake
+def _(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True):
+    B, Cc, H, W = current_feats.shape
+    return (current_feats.new_empty((B, Cc + depth_bins.shape[0], H, W)), current_feats.new_empty((B, H, W)),
+            current_feats.new_empty((B, H, W), dtype=torch.int32))
+
+
+@custom_op("dmh::cost_volume_stack_bwd", mutates_args=())
+def cost_volume_stack_bwd(g: torch.Tensor, current_feats: torch.Tensor, lookup_feats: torch.Tensor, poses: torch.Tensor,
+                          K: torch.Tensor, invK: torch.Tensor, depth_bins: torch.Tensor, need_current: bool,
+                          need_lookup: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d current_feats, d lookup_feats) for the gradient ``g`` of ``stacked``; the one that is not needed is an empty tensor (and
+    is not computed)."""
+    Cc = current_feats.shape[1]
+    g = _cu(g)
+    d_cur, d_look = ops.cost_volume_bwd_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, g[:, Cc:], need_current,
+                                               need_lookup)
+    if d_cur is not None:
+        d_cur += g[:, :Cc]
+    return (d_cur if need_current else g.new_empty(0)), (d_look if need_lookup else g.new_empty(0))
+
+
+@cost_volume_stack_bwd.register_fake
+def _(g, current_feats, lookup_feats, poses, K, invK, depth_bins, need_current, need_lookup):
+    return (torch.empty_like(current_feats) if need_current else g.new_empty(0),
+            torch.empty_like(lookup_feats) if need_lookup else g.new_empty(0))
+
+
+def _cvs_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:6])
+
+
+def _cvs_backward(ctx, g, _g_conf, _g_idx):
+    need_cur, need_look = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if not (need_cur or need_look):
+        return (None,) * 7
+    d_cur, d_look = torch.ops.dmh.cost_volume_stack_bwd(g, *ctx.saved_tensors, need_cur, need_look)
+    return (d_cur if need_cur else None), (d_look if need_look else None), None, None, None, None, None
+
+
+cost_volume_stack.register_autograd(_cvs_backward, setup_context=_cvs_setup)
+
+
 # ---------------------------------------------------------------------------------------------------------------- K36
 @custom_op("dmh::reduce_conv_degenerate", mutates_args=())
 def reduce_conv_degenerate(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
@@ -756,5 +810,5 @@ OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt
        "l0_mask_cost", "l0_mask_cost_bwd", "photo_smooth_loss", "photo_smooth_loss_bwd", "ssim_map", "ssim_map_bwd", "smooth_loss", "smooth_loss_bwd",
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
-       "cost_volume", "cost_volume_into", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity",
+       "cost_volume", "cost_volume_into", "cost_volume_stack", "cost_volume_stack_bwd", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity",
        "reduce_conv_degenerate", "reduce_conv_degenerate_bwd", "disp_colorize")

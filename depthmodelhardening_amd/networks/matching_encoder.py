@@ -65,6 +65,10 @@ class ResnetEncoderMatching(nn.Module):
         self.matching_height, self.matching_width = input_height // 4, input_width // 4     # the volume is built at 1/4 resolution
         self.roi_backward = False       # the windowed attack path (K19) is not extended to this encoder
         self.fuse_train = True          # train(): the fused stem / reduce_conv path of the degenerate call (False: module path)
+        # True: with lookup frames, the lookup features and the volume are built WITH gradient (K38; this project's addition --
+        # the reference computes both under no_grad, which False keeps: the volume is then a constant of every gradient).
+        # "current": the volume with gradient, the lookup features without -- the gradient reaches the current frame only
+        self.matching_grad = False
 
         block, layers = _CONFIGS[num_layers]
         trunk = ResNet(block, layers)
@@ -147,48 +151,13 @@ class ResnetEncoderMatching(nn.Module):
         return self._match_features_module(current_feats, lookup_feats, relative_poses, K, invK)
 
     def _match_features_module(self, current_feats, lookup_feats, relative_poses, K, invK):
-        B, C, H, W = current_feats.shape
-        D = self.num_depth_bins
-        dev, dt = current_feats.device, current_feats.dtype
-        depths = self.depth_bins.to(device=dev, dtype=dt).view(D, 1, 1)
+        """The reference's arithmetic as plain PyTorch expressions, any device and dtype (``ops.cost_volume_module``: the one copy,
+        which ``ops.cost_volume_stack`` differentiates for CPU tensors)."""
+        H, W = current_feats.shape[2:]
         if (H, W) != (self.matching_height, self.matching_width):
             raise RuntimeError("ResnetEncoderMatching: features of %d x %d, the matching grid is %d x %d" % (
                 H, W, self.matching_height, self.matching_width))
-        pix = self.backprojector.pix_coords[:1].to(device=dev, dtype=dt)                                        # [1,3,HW]
-        ones = torch.ones(D, 1, H * W, device=dev, dtype=dt)
-        current_mask = torch.zeros(D, H, W, device=dev, dtype=dt)
-        current_mask[:, 2:-2, 2:-2] = 1.0
-        volumes, masks = [], []
-        for b in range(B):
-            cost = torch.zeros(D, H, W, device=dev, dtype=dt)
-            counts = torch.zeros(D, H, W, device=dev, dtype=dt)
-            points = torch.cat([depths * torch.matmul(invK[b:b + 1, :3, :3], pix), ones], 1)            # [D,4,HW]
-            for l in range(lookup_feats.shape[1]):
-                pose = relative_poses[b:b + 1, l]           # an empty slice for b >= Bp: its sum is 0
-                if pose.sum() == 0:
-                    continue
-                P = torch.matmul(K[b:b + 1], pose)[:, :3, :]
-                cam = torch.matmul(P, points)
-                grid = cam[:, :2, :] / (cam[:, 2, :].unsqueeze(1) + 1e-7)
-                grid = grid.view(D, 2, H, W).permute(0, 2, 3, 1).clone()
-                grid[..., 0] /= W - 1
-                grid[..., 1] /= H - 1
-                grid = (grid - 0.5) * 2
-                warped = F.grid_sample(lookup_feats[b:b + 1, l].expand(D, C, H, W), grid, padding_mode='zeros', mode='bilinear',
-                                       align_corners=True)
-                x_vals = (grid[..., 0] / 2 + 0.5) * (W - 1)
-                y_vals = (grid[..., 1] / 2 + 0.5) * (H - 1)
-                edge = ((x_vals >= 2.0) * (x_vals <= W - 2) * (y_vals >= 2.0) * (y_vals <= H - 2)).to(dt) * current_mask
-                diffs = torch.abs(warped - current_feats[b:b + 1]).mean(1) * edge
-                cost = cost + diffs
-                counts = counts + (diffs > 0).to(dt)
-            cost = cost / (counts + 1e-7)
-            miss = (cost == 0).to(dt)
-            if self.set_missing_to_max:
-                cost = cost * (1 - miss) + cost.max(0)[0].unsqueeze(0) * miss
-            volumes.append(cost)
-            masks.append(miss)
-        return torch.stack(volumes, 0), torch.stack(masks, 0)
+        return ops.cost_volume_module(current_feats, lookup_feats, relative_poses, K, invK, self.depth_bins, self.set_missing_to_max)
 
     # ------------------------------------------------------------------------------------------------------------ stages
     def _fused_ok(self, image):
@@ -281,6 +250,32 @@ class ResnetEncoderMatching(nn.Module):
             feats.append(y)
         return feats
 
+    def _forward_matching_grad(self, current_feats, lookup_images, poses, K, invK, bins, weight, fused):
+        """The multi-frame tail of forward with the matching path differentiable.  CUDA fp32 features take ``ops.cost_volume_stack``
+        (K30 + K38, one node) whether or not the stages around it run fused -- ``match_features`` would hand them to K30, which is
+        forward only and would make the volume a constant again; everything else takes the module expression, the lines of forward
+        without no_grad / detach.  The same values as forward's."""
+        B, C, H, W = current_feats.shape
+        L = lookup_images.shape[1]
+        with torch.set_grad_enabled(self.matching_grad != "current" and torch.is_grad_enabled()):
+            lookup_feats = self.feature_extraction(lookup_images.reshape(B * L, *lookup_images.shape[2:]))
+        lookup_feats = lookup_feats.reshape(B, L, C, H, W)
+        if current_feats.is_cuda and current_feats.dtype == torch.float32:
+            stacked, confidence_mask, argmin = ops.cost_volume_stack(current_feats, lookup_feats, poses, K, invK, bins,
+                                                                     self.set_missing_to_max)
+        else:
+            cost_volume, missing_mask = self._match_features_module(current_feats, lookup_feats, poses, K, invK)
+            with torch.no_grad():
+                confidence_mask = self.compute_confidence_mask(cost_volume * (1 - missing_mask))
+                viz = torch.where(cost_volume == 0, torch.full_like(cost_volume, 100.0), cost_volume)
+                argmin = torch.min(viz, 1)[1]
+            cost_volume = cost_volume * confidence_mask.unsqueeze(1)
+            stacked = torch.cat([current_feats, cost_volume], 1)
+        with torch.no_grad():
+            lowest_cost = self.indices_to_disparity(argmin)
+        post = self._reduce(stacked, weight)
+        return self._tail(post, fused), lowest_cost, confidence_mask
+
     def forward(self, current_image, lookup_images, poses, K, invK, min_depth_bin=None, max_depth_bin=None):
         """(features, lowest_cost, confidence_mask).  ``lookup_images`` [B,L,3,H,W], or None: the caller states that there are no
         lookup frames (the degenerate call; ``poses`` is then not read)."""
@@ -313,6 +308,8 @@ class ResnetEncoderMatching(nn.Module):
                                % (tuple(lookup_images.shape), tuple(current_image.shape)))
         L = lookup_images.shape[1]
         self._check_lookups(B, L, poses)
+        if self.matching_grad:
+            return self._forward_matching_grad(current_feats, lookup_images, poses, K, invK, bins, weight, fused)
         with torch.no_grad():
             lookup_feats = self.feature_extraction(lookup_images.reshape(B * L, *lookup_images.shape[2:]))
             lookup_feats = lookup_feats.reshape(B, L, C, H, W)

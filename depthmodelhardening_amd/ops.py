@@ -3372,6 +3372,221 @@ def cost_volume(current_feats, lookup_feats, poses, K, invK, depth_bins, set_mis
     return cost_volume_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max, into, volume=into is None)
 
 
+# ----------------------------------------------------------------------------------------------------------------- K38
+def cost_volume_bwd_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, g, need_current=True, need_lookup=True):
+    """K38: (d_current [B,64,H,W] or None, d_lookup [B,L,64,H,W] or None) of V = cost_volume * confidence for the upstream gradient
+    ``g`` [B,D,H,W].  ``g`` may be a channel slice of a contiguous [B,64+D,H,W] tensor: it is read in place through its batch
+    stride.  The gradient that is not needed is not computed.  No host read."""
+    B, L, Bp, Cc, H, W, D = _cost_volume_shapes(current_feats, lookup_feats, poses, K, invK, depth_bins)
+    if not (need_current or need_lookup):
+        return None, None
+    dev = current_feats.device
+    if tuple(g.shape) != (B, D, H, W) or g.dtype != torch.float32 or not g.is_cuda:
+        raise RuntimeError("cost_volume_bwd: g must be a CUDA fp32 [%d,%d,%d,%d]; got %s %s on %s" % (
+            B, D, H, W, g.dtype, tuple(g.shape), g.device))
+    if B > 1 and g.stride(0) < D * H * W or g.stride()[1:] != (H * W, W, 1):
+        g = g.contiguous()
+    cur, look, poses, K, invK, bins = (_c(t.detach().to(torch.float32)) for t in (current_feats, lookup_feats, poses, K, invK,
+                                                                                   depth_bins))
+    nhwc = torch.empty((B, L, H, W, Cc), device=dev, dtype=torch.float32)
+    dtotal = torch.empty((B, D, H, W), device=dev, dtype=torch.float32)
+    acc = torch.empty((B * L * H * W * Cc + 1,), device=dev, dtype=torch.int64) if need_lookup else None
+    d_cur = torch.empty((B, Cc, H, W), device=dev, dtype=torch.float32) if need_current else None
+    d_look = torch.empty((B, L, Cc, H, W), device=dev, dtype=torch.float32) if need_lookup else None
+    nbytes = 4 * (2 * cur.numel() + 3 * look.numel() + 3 * B * D * H * W) + (20 * look.numel() if need_lookup else 0)
+    N.check(_timed("cost_volume_bwd", lambda: N.lib().dmh_cost_volume_bwd(
+        N.ptr(cur), N.ptr(look), N.ptr(poses), N.ptr(K), N.ptr(invK), N.ptr(bins), B, L, Bp, Cc, H, W, D, C.c_void_p(g.data_ptr()),
+        g.stride(0) if B > 1 else D * H * W, N.ptr(nhwc), N.ptr(dtotal), None if acc is None else C.c_void_p(acc.data_ptr()),
+        N.ptr(d_cur), N.ptr(d_look), N.stream()), nbytes))
+    return d_cur, d_look
+
+
+def cost_volume_stack_fwd_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True):
+    """(stacked [B,64+D,H,W], confidence, argmin): K30 into the buffer plus the copy of the current features."""
+    B, _, _, C, H, W, D = _cost_volume_shapes(current_feats, lookup_feats, poses, K, invK, depth_bins)
+    stacked = torch.empty((B, C + D, H, W), device=current_feats.device, dtype=torch.float32)
+    _, _, conf, idx = cost_volume_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max, stacked,
+                                         volume=False)
+    stacked[:, :C] = current_feats.detach()
+    return stacked, conf, idx
+
+
+class _CostVolumeStack(torch.autograd.Function):
+    """cat([current_feats, cost_volume * confidence], 1) as one node: K30 forward, K38 backward."""
+
+    @staticmethod
+    def forward(ctx, current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max):
+        stacked, conf, idx = cost_volume_stack_fwd_launch(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max)
+        ctx.save_for_backward(current_feats, lookup_feats, poses, K, invK, depth_bins)
+        ctx.mark_non_differentiable(conf, idx)
+        return stacked, conf, idx
+
+    @staticmethod
+    def backward(ctx, g, _g_conf, _g_idx):
+        cur, look, poses, K, invK, bins = ctx.saved_tensors
+        Cc = cur.shape[1]
+        g = _c(g)
+        d_cur, d_look = cost_volume_bwd_launch(cur, look, poses, K, invK, bins, g[:, Cc:], ctx.needs_input_grad[0],
+                                               ctx.needs_input_grad[1])
+        if d_cur is not None:
+            d_cur += g[:, :Cc]
+        return d_cur, d_look, None, None, None, None, None
+
+
+def cost_volume_module(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True):
+    """(cost_volume, missing_mask), both [B,D,H,W], in torch, any device and dtype, differentiable: match_features
+    (manydepth2/networks/resnet_encoder.py:157-236) as plain expressions of the reference's arithmetic -- the module path of
+    ``ResnetEncoderMatching`` and the CPU restatement the GPU tests compare with."""
+    F = torch.nn.functional
+    B, Cc, H, W = current_feats.shape
+    D = depth_bins.numel()
+    dev, dt = current_feats.device, current_feats.dtype
+    depths = depth_bins.to(device=dev, dtype=dt).view(D, 1, 1)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W)], 0).unsqueeze(0).to(device=dev, dtype=dt)
+    ones = torch.ones(D, 1, H * W, device=dev, dtype=dt)
+    current_mask = torch.zeros(D, H, W, device=dev, dtype=dt)
+    current_mask[:, 2:-2, 2:-2] = 1.0
+    volumes, masks = [], []
+    for b in range(B):
+        cost = torch.zeros(D, H, W, device=dev, dtype=dt)
+        counts = torch.zeros(D, H, W, device=dev, dtype=dt)
+        points = torch.cat([depths * torch.matmul(invK[b:b + 1, :3, :3], pix), ones], 1)
+        for l in range(lookup_feats.shape[1]):
+            pose = poses[b:b + 1, l]
+            if pose.sum() == 0:
+                continue
+            P = torch.matmul(K[b:b + 1], pose)[:, :3, :]
+            cam = torch.matmul(P, points)
+            grid = cam[:, :2, :] / (cam[:, 2, :].unsqueeze(1) + 1e-7)
+            grid = grid.view(D, 2, H, W).permute(0, 2, 3, 1).clone()
+            grid[..., 0] /= W - 1
+            grid[..., 1] /= H - 1
+            grid = (grid - 0.5) * 2
+            warped = F.grid_sample(lookup_feats[b:b + 1, l].expand(D, Cc, H, W), grid, padding_mode='zeros', mode='bilinear',
+                                   align_corners=True)
+            x_vals = (grid[..., 0] / 2 + 0.5) * (W - 1)
+            y_vals = (grid[..., 1] / 2 + 0.5) * (H - 1)
+            edge = ((x_vals >= 2.0) * (x_vals <= W - 2) * (y_vals >= 2.0) * (y_vals <= H - 2)).to(dt) * current_mask
+            diffs = torch.abs(warped - current_feats[b:b + 1]).mean(1) * edge
+            cost = cost + diffs
+            counts = counts + (diffs > 0).to(dt)
+        cost = cost / (counts + 1e-7)
+        miss = (cost == 0).to(dt)
+        if set_missing_to_max:
+            cost = cost * (1 - miss) + cost.max(0)[0].unsqueeze(0) * miss
+        volumes.append(cost)
+        masks.append(miss)
+    return torch.stack(volumes, 0), torch.stack(masks, 0)
+
+
+def cost_volume_stack_host(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True):
+    """The definition in torch (any device and dtype; autograd differentiates it): the path of CPU tensors."""
+    cost, miss = cost_volume_module(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max)
+    conf = ((cost * (1 - miss) > 0).sum(1) == depth_bins.numel()).to(cost.dtype).detach()
+    viz = torch.where(cost == 0, torch.full_like(cost, 100.0), cost)
+    argmin = torch.min(viz.detach(), 1)[1].to(torch.int32)
+    return torch.cat([current_feats, cost * conf.unsqueeze(1)], 1), conf, argmin
+
+
+def cost_volume_stack(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max=True):
+    """reduce_conv's input of the multi-frame call WITH gradient: (stacked [B,64+D,H,W], confidence [B,H,W], argmin [B,H,W] int32),
+    ``stacked[:, :64] = current_feats`` and ``stacked[:, 64:] = cost_volume * confidence``.  One autograd node on CUDA fp32 tensors
+    (K30 forward, K38 backward): d current = g[:, :64] + K38's d_current, d lookup = K38's d_lookup, and the one that is not
+    required is not computed.  The sample positions, masks, counts and the confidence are constants, as torch autograd treats them
+    in the module expression; the reference itself computes the volume under no_grad -- this gradient is this project's addition.
+    CPU tensors take ``cost_volume_stack_host``."""
+    if not current_feats.is_cuda:
+        return cost_volume_stack_host(current_feats, lookup_feats, poses, K, invK, depth_bins, set_missing_to_max)
+    for t in (current_feats, lookup_feats, poses, K, invK, depth_bins):
+        _need_cuda(t)
+    if current_feats.dtype != torch.float32 or lookup_feats.dtype != torch.float32:
+        raise RuntimeError("libdmh_hip ops compute in fp32; got %s, %s" % (current_feats.dtype, lookup_feats.dtype))
+    _cost_volume_shapes(current_feats, lookup_feats, poses, K, invK, depth_bins)
+    return _CostVolumeStack.apply(_c(current_feats), _c(lookup_feats), poses, K, invK, depth_bins, bool(set_missing_to_max))
+
+
+def cost_volume_bwd_host(current_feats, lookup_feats, poses, K, invK, depth_bins, g):
+    """K38's formulas in numpy, in the dtype of ``current_feats`` (float32 or float64): (d_current [B,C,H,W], d_lookup
+    [B,L,C,H,W]) of V = cost_volume * confidence for the upstream gradient ``g`` [B,D,H,W].  Positions, masks, counts and the
+    confidence are constants; sgn(0) = 0; taps outside the map and non-finite positions get nothing; a lookup whose pose sums to
+    exactly 0, or of a sample b >= Bp, is skipped."""
+    cur = np.asarray(current_feats)
+    dtype = cur.dtype.type
+    if dtype not in (np.float32, np.float64):
+        raise RuntimeError("cost_volume_bwd_host: float32 or float64 arrays; got %s" % cur.dtype)
+    look, poses, K, invK, bins, g = (np.asarray(t).astype(dtype) for t in (lookup_feats, poses, K, invK, depth_bins, g))
+    B, Cc, H, W = cur.shape
+    L, D, Bp = look.shape[1], bins.shape[0], poses.shape[0]
+    one, half, two, eps = dtype(1), dtype(0.5), dtype(2), dtype(1e-7)
+    wm1, hm1 = dtype(W - 1), dtype(H - 1)
+    ys, xs = np.meshgrid(np.arange(H).astype(dtype), np.arange(W).astype(dtype), indexing="ij")
+    cur_mask = np.zeros((H, W), dtype=dtype)
+    cur_mask[2:-2, 2:-2] = 1
+    d_cur, d_look = np.zeros_like(cur), np.zeros_like(look)
+    for b in range(B):
+        iK = invK[b]
+        cam = [iK[r, 0] * xs + iK[r, 1] * ys + iK[r, 2] for r in range(3)]
+        pts = [bins[:, None, None] * cam[r][None] for r in range(3)]
+        total, counts = np.zeros((D, H, W), dtype), np.zeros((D, H, W), dtype)
+        kept = []           # per lookup that counts: (l, sign * edge [C,D,H,W], taps [(flat index, weight)])
+        for l in range(L):
+            if b >= Bp:
+                continue
+            T = poses[b, l]
+            s = dtype(0)
+            for v in T.reshape(-1):
+                s = s + v
+            if s == 0:
+                continue
+            P = np.zeros((3, 4), dtype)
+            for r in range(3):
+                for cc in range(4):
+                    a = K[b, r, 0] * T[0, cc]
+                    for k in (1, 2, 3):
+                        a = a + K[b, r, k] * T[k, cc]
+                    P[r, cc] = a
+            proj = [((P[r, 0] * pts[0] + P[r, 1] * pts[1]) + P[r, 2] * pts[2]) + P[r, 3] for r in range(3)]
+            den = proj[2] + eps
+            with np.errstate(divide="ignore", invalid="ignore"):
+                gx = ((proj[0] / den) / wm1 - half) * two
+                gy = ((proj[1] / den) / hm1 - half) * two
+                xv, yv = (gx / two + half) * wm1, (gy / two + half) * hm1
+                edge = ((xv >= 2) & (xv <= W - 2) & (yv >= 2) & (yv <= H - 2)).astype(dtype) * cur_mask[None]
+                ix, iy = ((gx + one) / two) * wm1, ((gy + one) / two) * hm1
+            ix = np.nan_to_num(ix, nan=-5.0, posinf=-5.0, neginf=-5.0)
+            iy = np.nan_to_num(iy, nan=-5.0, posinf=-5.0, neginf=-5.0)
+            x0, y0 = np.floor(ix), np.floor(iy)
+            wx1, wy1, wx0, wy0 = ix - x0, iy - y0, (x0 + 1) - ix, (y0 + 1) - iy
+            feat = look[b, l].reshape(Cc, H * W)
+            warped = np.zeros((Cc, D, H, W), dtype)
+            taps = []
+            for dy, dx, wgt in ((0, 0, wx0 * wy0), (0, 1, wx1 * wy0), (1, 0, wx0 * wy1), (1, 1, wx1 * wy1)):
+                xt, yt = x0 + dx, y0 + dy
+                ok = (xt >= 0) & (xt <= W - 1) & (yt >= 0) & (yt <= H - 1)
+                flat = (np.where(ok, yt, 0) * W + np.where(ok, xt, 0)).astype(np.int64)
+                wgt = np.where(ok, wgt, 0).astype(dtype)
+                warped = warped + feat[:, flat] * wgt[None]
+                taps.append((flat, wgt))
+            delta = warped - cur[b][:, None]
+            diffs = (np.abs(delta).sum(0, dtype=dtype) / dtype(Cc)) * edge
+            total = total + diffs
+            counts = counts + (diffs > 0).astype(dtype)
+            kept.append((l, np.sign(delta) * edge[None], taps))
+        cost = total / (counts + eps)
+        conf = ((cost > 0).sum(0) == D).astype(dtype)
+        dtotal = (g[b] / (counts + eps)) * conf[None]
+        for l, sg, taps in kept:
+            dw = sg * (dtotal[None] / dtype(Cc))                      # d warped_l [C,D,H,W]
+            d_cur[b] -= dw.sum(1, dtype=dtype)
+            out = np.zeros((H * W, Cc), dtype)
+            dwt = np.ascontiguousarray(dw.reshape(Cc, -1).T)
+            for flat, wgt in taps:
+                np.add.at(out, flat.reshape(-1), dwt * wgt.reshape(-1, 1))
+            d_look[b, l] = out.T.reshape(Cc, H, W)
+    return d_cur, d_look
+
+
 # ------------------------------------------------------------------------------------ the loader operators (K31, K32, K34)
 class _UploadCache(object):
     """The last ``cap`` sets of small tables a loader operator has uploaded, by key, so that a repeated batch shape launches with

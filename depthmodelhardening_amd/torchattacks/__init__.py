@@ -12,8 +12,9 @@ from .attacks.phy_obj_atk_arbi import Phy_obj_atk_arbi
 from .attacks.phy_obj_atk_guassian import Phy_obj_atk_guassian
 from .attacks.phy_obj_atk_l0 import Phy_obj_atk_l0
 from .attacks.phy_obj_atk_l2 import Phy_obj_atk_l2
+from .attacks.phy_obj_atk_multiframe import Phy_obj_atk_mf
 from .attacks.phy_obj_atk_light import Phy_obj_atk_light
 from .attacks.phy_obj_atk_square import Phy_obj_atk_Square
 from .attacks.phy_obj_atk_vanila import Phy_obj_atk_vanila
 
-__all__ = ["Attack", "PGD_depth", "Phy_obj_atk", "Phy_obj_atk_APGD", "Phy_obj_atk_arbi", "Phy_obj_atk_guassian", "Phy_obj_atk_l0", "Phy_obj_atk_l2", "Phy_obj_atk_light", "Phy_obj_atk_Square", "Phy_obj_atk_vanila"]
+__all__ = ["Attack", "PGD_depth", "Phy_obj_atk", "Phy_obj_atk_APGD", "Phy_obj_atk_arbi", "Phy_obj_atk_guassian", "Phy_obj_atk_l0", "Phy_obj_atk_l2", "Phy_obj_atk_mf", "Phy_obj_atk_light", "Phy_obj_atk_Square", "Phy_obj_atk_vanila"]

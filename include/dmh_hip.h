@@ -811,7 +811,7 @@ int dmh_pose_head_bwd(const float* g_T, const float* g_axisangle, const float* g
 
 /* ------------------------------------------------------------------------------------
  * K30 ManyDepth's matching cost volume, forward only (manydepth2/networks/resnet_encoder.py:157-236 match_features, :258-265
- *     compute_confidence_mask, :294-296 the argmin of forward).  No backward: the reference computes it under no_grad.
+ *     compute_confidence_mask, :294-296 the argmin of forward).  The reference computes it under no_grad; the backward is K38.
  *     current[B][C][H][W], lookup[B][L][C][H][W] (layer-1 features), poses[Bp][L][4][4], K / invK[B][4][4], bins[D] (depths).
  *     Per (b, d, h, w, l): the reference's fp32 position arithmetic without contraction, bilinear sample (zero padding,
  *     align_corners), mean over channels of |warped - current| times the edge mask and the current frame's border mask; summed
@@ -828,6 +828,26 @@ int dmh_cost_volume_fwd(const float* current, const float* lookup, const float* 
                         const float* bins, int B, int L, int Bp, int C, int H, int W, int D, int set_missing_to_max, int banded,
                         float* nhwc, float* cost_volume, float* missing, float* confidence, int32_t* argmin, float* buffer,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * K38 backward of the matching cost volume (this project's addition: the reference has none).  Differentiates
+ *     V[b][d][h][w] = cost_volume[b][d][h][w] * confidence[b][h][w] (what K30 writes into `buffer`) with respect to current and
+ *     lookup as torch autograd differentiates the module expression: sample positions, edge / border masks, counts, missing and
+ *     confidence are constants, so only confident columns carry gradient and set_missing_to_max plays no part.  With
+ *     dtotal[d] = g[d] / (counts[d] + 1e-7) in a confident column:
+ *       d_current[b][c][h][w] = -(1/C) sum_{d,l} dtotal[d] edge_l[d] sgn(warped_l[c][d] - current[c]),   sgn(0) = 0;
+ *       d_lookup[b][l][c] receives (1/C) dtotal[d] edge_l[d] sgn(...) through the four bilinear weights of the sample.
+ *     Inputs and limits as K30 (the positions are K30's own arithmetic; skipped lookups are decided on the device and get exact
+ *     zeros).  g: element (b, d, h, w) at g[b * g_batch_stride + (d * H + h) * W + w], so channels C .. C + D - 1 of a
+ *     [B][C + D][H][W] gradient are read in place (g + C H W, stride (C + D) H W).  g must be finite.
+ *     d_current[B][C][H][W], d_lookup[B][L][C][H][W]: either may be NULL, not both; both are overwritten (no need to zero them).
+ *     Workspaces: nhwc (B L C H W floats), dtotal (B D H W floats), acc (B L C H W + 1 int64 words; may be NULL when d_lookup is).
+ *     d_current is a gather; d_lookup is accumulated in 64-bit fixed point with integer atomics, the scale taken on the device
+ *     from max|dtotal| (csrc/cost_volume_bwd.hip states the bound): no float atomics, bitwise reproducible, no host read.
+ * ---------------------------------------------------------------------------------- */
+int dmh_cost_volume_bwd(const float* current, const float* lookup, const float* poses, const float* K, const float* invK,
+                        const float* bins, int B, int L, int Bp, int C, int H, int W, int D, const float* g, int64_t g_batch_stride,
+                        float* nhwc, float* dtotal, int64_t* acc, float* d_current, float* d_lookup, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * K31 Pillow's 8-bit separable resample, Image.resize(size, filter) of mode RGB / L with reducing_gap=None, bit for bit
