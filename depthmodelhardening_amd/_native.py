@@ -17,6 +17,7 @@ PASTE_COMPOSITE, PASTE_WARP_ONLY = 0, 1
 SGM_COST, SGM_PATHS, SGM_SELECT, SGM_SPECKLE, SGM_ALL = 1, 2, 4, 8, 15       # DMH_SGM_*: the phases of K35
 COLORIZE_MIN_P95, COLORIZE_ZERO_REF, COLORIZE_MIN_MAX, COLORIZE_MAX_PANELS, COLORIZE_STATS = 0, 1, 2, 32, 5    # DMH_COLORIZE_* (K37)
 PIL_LANCZOS, PIL_BILINEAR, PIL_TILE_ROWS = 1, 2, 8      # PIL.Image.LANCZOS / BILINEAR; DMH_PIL_TILE_ROWS
+LIDAR_DEPTH, LIDAR_DISP, LIDAR_NET, LIDAR_TILE, LIDAR_CALIB = 0, 1, 2, 1024, 27     # DMH_LIDAR_* (K39)
 FIN_LOSS, FIN_LOSS_S, FIN_REPROJ_S, FIN_COUNT_S, FIN_SMOOTH_S, FIN_HINT_S, FIN_HINTCOUNT_S, FIN_SIZE = 0, 1, 5, 9, 13, 20, 24, 28
 
 LIB_PATH = os.environ.get("DMH_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
@@ -218,6 +219,7 @@ _SIGNATURES = {
     "dmh_disp_colorize_ws_size": (C.c_int64, [C.c_int]),
     "dmh_disp_colorize": (C.c_int, [_fp] + [C.c_int] * 3 + [C.POINTER(ColorizePanel)] + [C.c_int] * 5 + [C.c_float] + [_fp] * 5
                           + [C.c_int64, C.c_int64, _fp]),
+    "dmh_pseudo_lidar": (C.c_int, [_fp, C.c_int64] + [C.c_int] * 4 + [_fp] * 3 + [C.c_int, C.c_int, C.c_double, _fp, _fp, C.c_int64, _fp, _fp]),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

@@ -46,6 +46,8 @@ the same bits.  There is no CPU kernel behind any of them: CPU tensors are rejec
                               semi-global matcher (not OpenCV's output)   (K35, no autograd)
     dmh::disp_colorize        MD2/test_simple.py:136-156, my_utils.py:54-67 (bilinear resize, np.percentile, Normalize + magma, uint8)
                               (K37, no autograd)
+    dmh::pseudo_lidar         preprocessing/generate_lidar.py:10-33 + kitti_util.py:159-175 (maps to velodyne-frame clouds, float32-equal)
+                              (K39, no autograd)
 """
 from typing import List, Optional, Tuple
 
@@ -794,6 +796,23 @@ def _(maps, panels, out_h, out_w):
             maps.new_empty((P, ops.N.COLORIZE_STATS)))
 
 
+# ---------------------------------------------------------------------------------------------------------------- K39
+@custom_op("dmh::pseudo_lidar", mutates_args=())
+def pseudo_lidar(src: torch.Tensor, form: str, shapes: List[int], calib: torch.Tensor, max_high: float = 1.0, quantise: bool = False,
+                 offsets: Optional[List[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(points float32 [sum H W, 4], offsets int64 [n + 1]).  ``shapes``: H0, W0, H1, W1, ... of the frames; ``form``: "depth", "disp"
+    or "net" (``ops.pseudo_lidar``).  Clouds carry no gradient: there is no autograd formula."""
+    ops._need_cuda(src)
+    out = ops.pseudo_lidar(src, form, list(zip(shapes[0::2], shapes[1::2])), calib, max_high, quantise, offsets)
+    return out.points, out.offsets
+
+
+@pseudo_lidar.register_fake
+def _(src, form, shapes, calib, max_high=1.0, quantise=False, offsets=None):
+    return (src.new_empty((sum(h * w for h, w in zip(shapes[0::2], shapes[1::2])), 4)),
+            src.new_empty((len(shapes) // 2 + 1,), dtype=torch.int64))
+
+
 def sgm_params_flat(params):
     """A list of parameter dicts as the flat integer list ``torch.ops.dmh.sgm_disparity`` takes."""
     return [int(v) for t in ops._sgm_params(params) for v in t]
@@ -811,4 +830,4 @@ OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
        "cost_volume", "cost_volume_into", "cost_volume_stack", "cost_volume_stack_bwd", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity",
-       "reduce_conv_degenerate", "reduce_conv_degenerate_bwd", "disp_colorize")
+       "reduce_conv_degenerate", "reduce_conv_degenerate_bwd", "disp_colorize", "pseudo_lidar")

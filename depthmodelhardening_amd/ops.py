@@ -4813,3 +4813,220 @@ def disp_colorize(maps, panels=None, out_size=None, out=None, origins=None, retu
         N.ptr(maps), B, h, w, native, P, H, W, lo, hi, g, N.ptr(table), N.ptr(fmap), N.ptr(ws), N.ptr(stats), N.ptr(rgb),
         rgb.numel(), pitch, N.stream()), 4 * P * (4 * H * W + h * w) + 3 * P * H * W))
     return ColorizeOut(rgb, fmap if return_map else None, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------- K39
+PseudoLidarOut = namedtuple("PseudoLidarOut", ["points", "offsets"])
+LIDAR_FORMS = {"depth": N.LIDAR_DEPTH, "disp": N.LIDAR_DISP, "net": N.LIDAR_NET}
+LIDAR_BASELINE = 0.54                   # generate_lidar.py:12
+LIDAR_DESC_CACHE = 16
+_lidar_desc_cache = _UploadCache(LIDAR_DESC_CACHE, "pseudo_lidar: the first call with these shapes uploads their descriptors; make it "
+                                                   "once before capturing a graph")      # (device, form, shapes, offsets) -> tables
+
+
+def lidar_calib(path_or_text, crop=None):
+    """The 27 float64 values K39 takes for one frame -- f_u f_v c_u c_v b_x b_y, inv(R0), C2V -- from a KITTI-object calibration
+    file (or its text), made as the reference's ``Calibration.__init__`` makes them (datasets/kitti_object.py).
+    ``crop=(left, top)``: the scene was cropped by that many pixels; c_u and c_v move with it, nothing else does."""
+    from .datasets.kitti_object import Calibration
+    return Calibration(path_or_text, crop).packed()
+
+
+def _lidar_shapes(shapes, n):
+    shapes = tuple((int(h), int(w)) for h, w in (shapes.tolist() if hasattr(shapes, "tolist") else shapes))
+    if n < 1 or len(shapes) != n or not all(h >= 0 and w >= 0 and h * w < 2 ** 31 for h, w in shapes):
+        raise RuntimeError("pseudo_lidar: shapes must be n >= 1 pairs (H, W) with H, W >= 0, one per frame (%d); got %s" % (n, shapes))
+    return shapes
+
+
+def _lidar_offsets(form, shapes, offsets, src_len):
+    """The first element of every frame of a packed depth / disp input (K32's cell offsets); default: one map after the other."""
+    if form == "net":
+        if offsets is not None:
+            raise RuntimeError("pseudo_lidar: offsets belong to the packed depth / disp forms")
+        return None
+    if offsets is None:
+        offsets = np.cumsum([0] + [h * w for h, w in shapes])
+    offsets = tuple(int(v) for v in (offsets.tolist() if hasattr(offsets, "tolist") else offsets))
+    if len(offsets) not in (len(shapes), len(shapes) + 1) or any(o < 0 or o + h * w > src_len for o, (h, w) in zip(offsets, shapes)):
+        raise RuntimeError("pseudo_lidar: offsets must place every frame's H W values inside the %d values given; got %s for %s"
+                           % (src_len, offsets, shapes))
+    return offsets[:len(shapes)]
+
+
+def _lidar_lin_axis(dst, src):
+    """K25's lin_axis for every destination index of one axis: (s0, s1, f), f float32 (OpenCV's INTER_LINEAR coordinates)."""
+    scale = float(src) / float(dst)
+    f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    f = f - s.astype(np.float32)
+    lo, hi = s < 0, s >= src - 1
+    s = np.where(lo, 0, np.where(hi, src - 1, s))
+    f = np.where(lo | hi, np.float32(0), f).astype(np.float32)
+    return s, np.minimum(s + 1, src - 1), f
+
+
+def lidar_net_depth_host(disp, H, W, quantise=False):
+    """The net form's depth of one frame, float32 [H, W], from the sigmoid output [h, w]: disp_to_depth's scaling in fp32, the
+    bilinear resize, 5.4 / disp, evaluate's clamp and with ``quantise`` the 16-bit PNG round trip -- every operation a rounded
+    float32 one, in the kernel's order."""
+    disp = np.asarray(disp, dtype=np.float32)
+    h, w = disp.shape
+    with np.errstate(all="ignore"):
+        taps = np.float32(1.0 / 100.0) + np.float32(1.0 / 0.1 - 1.0 / 100.0) * disp
+        sx, sx1, fx = _lidar_lin_axis(W, w)
+        sy, sy1, fy = _lidar_lin_axis(H, h)
+        a0, a1 = np.float32(1) - fx, fx
+        b0, b1 = (np.float32(1) - fy)[:, None], fy[:, None]
+        rows = a0 * taps[:, sx] + a1 * taps[:, sx1]
+        small = b0 * rows[sy] + b1 * rows[sy1]
+        depth = (np.float32(1) / small) * np.float32(5.4)
+        depth = np.where(depth < np.float32(1e-3), np.float32(1e-3), depth)
+        depth = np.where(depth > np.float32(80), np.float32(80), depth)
+        if quantise:
+            q = depth * np.float32(256)
+            k = np.where(np.isnan(q), np.float32(0), q).astype(np.uint16)
+            depth = k.astype(np.float32) / np.float32(256)
+    return depth.astype(np.float32)
+
+
+def _lidar_frame_host(cal, H, W, d, keep, max_high):
+    """project_image_to_velo and the validity test on the candidates of one frame: ``d`` float64 [H W] in pixel order, ``keep`` the
+    candidate mask (None: all).  Element-wise float64 in the kernel's association; never ``np.dot``."""
+    p = np.arange(H * W, dtype=np.int64) if keep is None else np.nonzero(keep)[0]
+    v, u = (p // max(W, 1)).astype(np.float64), (p % max(W, 1)).astype(np.float64)
+    d = d[p]
+    f_u, f_v, c_u, c_v, b_x, b_y = (float(c) for c in cal[:6])
+    Ri, Cm = cal[6:15].reshape(3, 3), cal[15:27].reshape(3, 4)
+    with np.errstate(all="ignore"):
+        x = ((u - c_u) * d) / f_u + b_x
+        y = ((v - c_v) * d) / f_v + b_y
+        z = d
+        r = [(Ri[i, 0] * x + Ri[i, 1] * y) + Ri[i, 2] * z for i in range(3)]
+        o = [((Cm[i, 0] * r[0] + Cm[i, 1] * r[1]) + Cm[i, 2] * r[2]) + Cm[i, 3] for i in range(3)]
+        valid = (o[0] >= 0) & (o[2] < max_high)                 # a NaN fails either comparison
+        rows = np.stack([o[0][valid], o[1][valid], o[2][valid], np.ones(int(valid.sum()))], axis=1).astype(np.float32)
+    return rows
+
+
+def pseudo_lidar_host(src, form, shapes, calib, max_high=1, quantise=False, offsets=None):
+    """K39 in numpy, the definition the kernel is held to (and the path CPU tensors take).  ``src``: float32, the packed maps of
+    the depth / disp forms (frame f at ``offsets[f]``) or the network's output [n, h, w] of the net form.  ``calib``: float64
+    [n, 27].  Returns (float32 [M, 4], int64 [n + 1]): the kept rows of all frames in batch order and pixel order, and where each
+    frame's rows start."""
+    if form not in LIDAR_FORMS:
+        raise RuntimeError("pseudo_lidar: form must be one of %s; got %r" % (sorted(LIDAR_FORMS), form))
+    src = np.asarray(src, dtype=np.float32)
+    n = src.shape[0] if form == "net" else len(shapes)
+    if form == "net" and src.ndim != 3:
+        raise RuntimeError("pseudo_lidar: the net form takes [n, h, w]; got %s" % (src.shape,))
+    if quantise and form != "net":
+        raise RuntimeError("pseudo_lidar: quantise belongs to the net form")
+    shapes = _lidar_shapes(shapes, n)
+    calib = np.asarray(calib, dtype=np.float64).reshape(n, N.LIDAR_CALIB)
+    starts = _lidar_offsets(form, shapes, offsets, src.size)
+    flat = src.reshape(-1)
+    max_high = float(max_high)
+    clouds = []
+    for f, (H, W) in enumerate(shapes):
+        cal, keep = calib[f], None
+        if H * W == 0:
+            clouds.append(np.zeros((0, 4), dtype=np.float32))
+            continue
+        if form == "net":
+            d = lidar_net_depth_host(src[f], H, W, quantise).reshape(-1).astype(np.float64)
+        else:
+            m = flat[starts[f]:starts[f] + H * W]
+            if form == "depth":
+                d = m.astype(np.float64)
+            else:
+                with np.errstate(all="ignore"):
+                    s = np.where(m < 0, np.float32(0), m)       # a NaN stays and fails the mask
+                    keep = s > 0
+                    d = (cal[0] * LIDAR_BASELINE) / ((s.astype(np.float64) + 1.) - keep.astype(np.float64))
+        clouds.append(_lidar_frame_host(cal, H, W, d, keep, max_high))
+    counts = np.array([0] + [c.shape[0] for c in clouds], dtype=np.int64)
+    return np.concatenate(clouds).reshape(-1, 4), np.cumsum(counts)
+
+
+def _lidar_tables_device(device, form, shapes, starts):
+    def make():
+        tiles = [(h * w + N.LIDAR_TILE - 1) // N.LIDAR_TILE for h, w in shapes]
+        first = np.cumsum([0] + tiles)
+        desc = [[h, w, 0 if starts is None else starts[i], int(first[i])] for i, (h, w) in enumerate(shapes)]
+        tile_frame = np.repeat(np.arange(len(shapes)), tiles)
+        if tile_frame.size == 0:
+            tile_frame = np.array([-1])                         # never read: a launch has n_tiles = 0
+        return [torch.tensor(desc, dtype=torch.int32), torch.from_numpy(tile_frame.astype(np.int32))], int(first[-1])
+    (desc, tile_frame), n_tiles = _lidar_desc_cache.get((str(device), form, shapes, starts), device, make)
+    return desc, tile_frame, n_tiles
+
+
+def pseudo_lidar(src, form, shapes, calib, max_high=1, quantise=False, offsets=None):
+    """K39: maps of a batch of frames to velodyne-frame point clouds, as the reference's preprocessing/generate_lidar.py makes them
+    on the host (``project_depth_to_points`` / ``project_disp_to_points`` over ``Calibration.project_image_to_velo``), float32-equal,
+    in three launches with no host read.
+
+    src      float32.  ``form`` "depth": metric depth maps packed flat, frame f's H W values at ``offsets[f]`` (K32's layout; default
+             one map after the other); every pixel is a candidate.  "disp": the same layout of disparities in pixels; negatives
+             count as 0 and only pixels with a positive disparity are candidates.  "net": the network's sigmoid output [n, h, w]
+             (or [n, 1, h, w]); per frame it is scaled (disp_to_depth(., 0.1, 100)), resized to (H, W) as evaluate resizes it,
+             turned into 5.4 / disp, clamped to [1e-3, 80], and with ``quantise`` rounded down to 1 / 256 as a 16-bit PNG stores it.
+    shapes   n pairs (H, W): each frame's own size.  Host values: they size the launch.
+    calib    float64 [n, 27] on src's device: ``lidar_calib`` of every frame.
+    max_high a point is kept if its velodyne x >= 0 and z < max_high.
+    Returns  PseudoLidarOut(points, offsets): float32 [sum H W, 4], the kept rows (x, y, z, 1) of all frames in batch order, each
+             frame's in row-major pixel order, and int64 [n + 1] on the device: frame f is points[offsets[f]:offsets[f + 1]].
+             Rows from offsets[n] on are unspecified.
+
+    CPU tensors run ``pseudo_lidar_host``, the numpy restatement the kernel is bit-equal to."""
+    if form not in LIDAR_FORMS:
+        raise RuntimeError("pseudo_lidar: form must be one of %s; got %r" % (sorted(LIDAR_FORMS), form))
+    if not torch.is_tensor(src) or src.dtype != torch.float32:
+        raise RuntimeError("pseudo_lidar: src must be a float32 tensor; got %s" % (getattr(src, "dtype", type(src)),))
+    if form == "net":
+        if src.dim() == 4 and src.shape[1] == 1:
+            src = src[:, 0]
+        if src.dim() != 3 or src.shape[1] < 1 or src.shape[2] < 1:
+            raise RuntimeError("pseudo_lidar: the net form takes [n, h, w] or [n, 1, h, w]; got %s" % (tuple(src.shape),))
+        n, h, w = (int(v) for v in src.shape)
+    else:
+        if quantise:
+            raise RuntimeError("pseudo_lidar: quantise belongs to the net form")
+        if src.dim() != 1:
+            raise RuntimeError("pseudo_lidar: the %s form takes the maps packed flat; got %s" % (form, tuple(src.shape)))
+        n, h, w = len(shapes), 0, 0
+    shapes = _lidar_shapes(shapes, n)
+    if not torch.is_tensor(calib) or calib.dtype != torch.float64 or calib.numel() != N.LIDAR_CALIB * n:
+        raise RuntimeError("pseudo_lidar: calib must be a float64 tensor of %d x %d entries; got %s %s"
+                           % (n, N.LIDAR_CALIB, getattr(calib, "dtype", type(calib)), tuple(getattr(calib, "shape", ()))))
+    dev = src.device
+    if calib.device != dev:
+        raise RuntimeError("pseudo_lidar: src and calib must share a device; got %s and %s" % (dev, calib.device))
+    starts = _lidar_offsets(form, shapes, offsets, src.numel())
+    cap = sum(hh * ww for hh, ww in shapes)
+    if cap >= 2 ** 31 or src.numel() >= 2 ** 31:
+        raise RuntimeError("pseudo_lidar: the batch must hold fewer than 2^31 pixels; got %d" % cap)
+    if dev.type != "cuda":
+        pts, off = pseudo_lidar_host(src.numpy(), form, shapes, calib.numpy(), max_high, quantise, starts)
+        points = torch.zeros((cap, 4), dtype=torch.float32)
+        points[:pts.shape[0]] = torch.from_numpy(pts)
+        return PseudoLidarOut(points, torch.from_numpy(off))
+    desc, tile_frame, n_tiles = _lidar_tables_device(dev, form, shapes, starts)
+    src, calib = _c(src), _c(calib)
+    ws = torch.empty(2 * max(n_tiles, 1), device=dev, dtype=torch.int32)
+    points = torch.empty((cap, 4), device=dev, dtype=torch.float32)
+    off = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    N.check(_timed("pseudo_lidar", lambda: N.lib().dmh_pseudo_lidar(
+        N.ptr(src) if src.numel() else None, src.numel(), LIDAR_FORMS[form], h, w, int(bool(quantise)), N.ptr_f64(calib), N.ptr(desc),
+        N.ptr(tile_frame), n, n_tiles, float(max_high), N.ptr(ws), N.ptr(points) if cap else None, cap, C.c_void_p(off.data_ptr()),
+        N.stream()), 2 * 4 * src.numel() + 16 * cap))
+    return PseudoLidarOut(points, off)
+
+
+def lidar_clouds(out):
+    """The clouds of a ``PseudoLidarOut`` on the host, one float32 [M_f, 4] array per frame: the n + 1 offsets are read first (they
+    say how many rows are in use), then only those rows are copied."""
+    off = out.offsets.cpu().numpy()
+    used = out.points[:int(off[-1])].cpu().numpy()
+    return [used[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]

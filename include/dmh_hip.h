@@ -1052,6 +1052,38 @@ int dmh_disp_colorize(const float* src, int n_src, int h, int w, const dmh_color
                       int lo, int hi, float g, const uint8_t* table, float* map, uint32_t* ws, float* stats, uint8_t* out,
                       int64_t out_len, int64_t pitch, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K39 Pseudo-LiDAR: maps of a batch of n frames, each with its own size (H, W) and KITTI-object calibration, to velodyne-frame
+ *     clouds: preprocessing/generate_lidar.py:10-33 over kitti_util.Calibration.project_image_to_velo, float32-equal.
+ *   form     DMH_LIDAR_DEPTH: src float [src_len], frame f's H W depths at desc[f][2]; every pixel is a candidate, d = (double)src.
+ *            DMH_LIDAR_DISP:  the same layout of disparities in pixels; s = src < 0 ? 0 : src, only pixels with s > 0 are
+ *                             candidates, d = (f_u * 0.54) / (((double)s + 1.) - 1.).
+ *            DMH_LIDAR_NET:   src float [n][h][w], the network's sigmoid output (src_len = n h w); per pixel of (H, W) the taps
+ *                             0.01f + 9.99f * src, the bilinear resize with K25's coordinates (OpenCV's INTER_LINEAR), fp32
+ *                             unfused, depth = (1.f / disp) * 5.4f clamped to [1e-3, 80], with quantise != 0 then
+ *                             (float)(uint16)(depth * 256.f) / 256.f; d = (double)depth.  h = w = quantise = 0 in the other forms.
+ *   calib    double [n][DMH_LIDAR_CALIB]: f_u f_v c_u c_v b_x b_y, Ri[9] = inv(R0) row-major, C[12] = C2V row-major.
+ *            With u the column and v the row, in float64 without contraction and with IEEE division:
+ *            x = ((u - c_u) d) / f_u + b_x, y = ((v - c_v) d) / f_v + b_y, z = d; r_i = (Ri[i][0] x + Ri[i][1] y) + Ri[i][2] z;
+ *            o_i = ((C[i][0] r_0 + C[i][1] r_1) + C[i][2] r_2) + C[i][3]; kept if o_0 >= 0 && o_2 < max_high (a NaN is dropped).
+ *   desc     int32 [n][4]: H, W (either may be 0: a frame without pixels), the frame's offset in src (ignored by the net form),
+ *            its first tile.  A tile is DMH_LIDAR_TILE consecutive pixels of one frame in row-major order; tile_frame int32
+ *            [n_tiles] names each tile's frame; the tiles of the frames are consecutive in batch order.  A record that points
+ *            outside src yields no point.
+ *   ws       int32 [2 n_tiles], contents ignored.
+ *   out      float [cap][4], cap = sum H W <= n_tiles DMH_LIDAR_TILE: the kept rows (o_0, o_1, o_2, 1) as float32, frames in batch
+ *            order, rows in pixel order; rows from offsets[n] on are not written.  offsets: int64 [n + 1] in device memory.
+ *     Three launches (count, one-workgroup scan, write); no atomics, no host read: bitwise reproducible, capturable.
+ * ---------------------------------------------------------------------------------- */
+#define DMH_LIDAR_DEPTH 0
+#define DMH_LIDAR_DISP 1
+#define DMH_LIDAR_NET 2
+#define DMH_LIDAR_TILE 1024
+#define DMH_LIDAR_CALIB 27
+int dmh_pseudo_lidar(const float* src, int64_t src_len, int form, int h, int w, int quantise, const double* calib,
+                     const int32_t* desc, const int32_t* tile_frame, int n, int n_tiles, double max_high, int32_t* ws,
+                     float* out, int64_t cap, int64_t* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
