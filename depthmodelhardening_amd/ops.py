@@ -1,94 +1,31 @@
-"""Autograd-aware Python faces of the HIP kernels in libdmh_hip.so.
+"""Autograd-aware Python faces of the HIP kernels in libdmh_hip.so, and the one namespace everything else reaches them through.
 
-PyTorch is plumbing here: it owns device memory, streams and the autograd graph; every op
-below is one or a few launches of hand-written gfx950 kernels through the C ABI
-(include/dmh_hip.h).  There is no eager/CPU fallback: CPU tensors raise RuntimeError.
+PyTorch is plumbing here: it owns device memory, streams and the autograd graph; every op below is one or a few launches of
+hand-written gfx950 kernels through the C ABI (include/dmh_hip.h).
+
+This file holds the hot path -- the losses, the EOT paste, the decoder and encoder glue, BatchNorm, the 3x3 convolutions and
+their routing rule, the block nodes, the ROI window chain, the pose head and the cost volume -- and every module-level name that
+is rebound or assigned at run time.  The hot path has no CPU path: CPU tensors raise RuntimeError.  The attack, evaluation and
+loader operators live in attack_ops.py, eval_ops.py and data_ops.py, which state their own rule for CPU tensors, and the launch
+plumbing in _launch.py; all of their names are re-exported below, so ``ops.<name>`` is the same object wherever it is defined.
 """
 import contextlib
 import ctypes as C
 import functools
 import os
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import _native as N
+from . import _launch, _native as N, attack_ops, data_ops, eval_ops
+
+# The profile state stays behind: enable_profile() rebinds it in _launch, and a copy here would go stale.
+for _m in (_launch, attack_ops, eval_ops, data_ops):
+    globals().update((k, v) for k, v in vars(_m).items() if not k.startswith("__") and k not in ("_profile", "_profile_only"))
+del _m
 
 LossOut = namedtuple("LossOut", ["fin", "sel", "to_opt"])
-
-# Optional per-launch HIP-event timing of the K1 kernels (bench.py's roofline figure): a dict
-# name -> list of (start, end) torch.cuda.Event pairs recorded on the launch stream, or None (off).
-_profile = None
-_profile_only = None
-
-
-def enable_profile(on=True, only=None):
-    """HIP-event timing of the instrumented launches.  ``only``: tuple of name prefixes to time (the others launch
-    untouched) -- an event pair adds ~10 us of dispatch latency around a launch, so a timed region should carry events
-    on the kernels it reports and nothing else."""
-    global _profile, _profile_only
-    _profile = {} if on else None
-    _profile_only = tuple(only) if (on and only) else None
-
-
-def profile_ms():
-    """Average launch duration in ms per instrumented kernel (synchronises)."""
-    if not _profile:
-        return {}
-    torch.cuda.synchronize()
-    return {k: sum(e[0].elapsed_time(e[1]) for e in v) / len(v) for k, v in _profile.items() if v}
-
-
-def profile_bytes():
-    """Per instrumented kernel: (launches, total ms, total algorithmic bytes, total direct-convolution flops) -- for
-    kernels whose shape varies from launch to launch."""
-    if not _profile:
-        return {}
-    torch.cuda.synchronize()
-    return {k: (len(v), sum(e[0].elapsed_time(e[1]) for e in v), sum(e[2] for e in v), sum(e[3] for e in v))
-            for k, v in _profile.items() if v}
-
-
-def profiling_every_launch():
-    """True while enable_profile(True) without ``only`` is in force: every instrumented launch carries an event pair (bench.py's
-    one fully instrumented step).  Events cannot be read back from a captured HIP graph, so the attack runs that step eagerly."""
-    return _profile is not None and _profile_only is None
-
-
-def _timed(name, launch, nbytes=0, flops=0):
-    if _profile is None or (_profile_only is not None and not name.startswith(_profile_only)):
-        return launch()
-    if torch.cuda.is_current_stream_capturing():      # an event recorded into a graph has no time stamp to read
-        return launch()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    rc = launch()
-    e1.record()
-    _profile.setdefault(name, []).append((e0, e1, nbytes, flops))
-    return rc
-
-
-def _philox(device, count):
-    """(seed, offset) for the in-kernel tie-break noise, drawn from torch's CUDA generator state so
-    that torch.manual_seed() makes runs reproducible; the generator offset is advanced past the
-    ``count`` counters this call consumes."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    gen = torch.cuda.default_generators[idx]
-    seed, off = gen.initial_seed(), gen.get_offset()
-    gen.set_offset(off + ((count + 3) // 4) * 4)
-    return seed & 0xFFFFFFFFFFFFFFFF, off
-
-
-def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _need_cuda(t):
-    """A CPU operand (``t``: a tensor or a torch.device) is an error, never another code path."""
-    device = t if isinstance(t, torch.device) else t.device
-    if device.type != "cuda":
-        raise RuntimeError("libdmh_hip ops need CUDA (ROCm) tensors; got device %s -- there is no CPU path" % device)
 
 
 def _photo_args(cfg, target, sources, Ts, K, inv_K, disps, noises, hint=None):
@@ -592,546 +529,6 @@ def avg_pyramid(x):
     N.check(_timed("avg_pyramid", lambda: N.lib().dmh_avg_pyramid(N.ptr(x), B * Cc, H, W, N.ptr(outs[0]), N.ptr(outs[1]),
                                                                   N.ptr(outs[2]), N.stream()), 4 * (x.numel() * 85 // 64)))
     return outs
-
-
-def pgd_linf_step(x, x0, grad, alpha, eps, out=None):
-    """x <- clamp(x0 + clamp(x + alpha*sign(grad) - x0, -eps, eps), 0, 1) (phy_obj_atk.py:98-101)."""
-    x, x0, grad = _c(x.detach()), _c(x0), _c(grad)
-    if x.shape != x0.shape or x.shape != grad.shape:
-        raise RuntimeError("pgd_linf_step: shape mismatch")
-    if out is None:
-        out = torch.empty_like(x)
-    N.check(N.lib().dmh_pgd_linf_step(N.ptr(x), N.ptr(x0), N.ptr(grad), float(alpha), float(eps), N.ptr(out),
-                                      x.numel(), N.stream()))
-    return out
-
-
-def pgd_l2_workspace(n, device):
-    """The float64 workspace of pgd_l2_step for tensors of ``n`` elements: K28's per-workgroup partial sums."""
-    return torch.empty(int(N.lib().dmh_pgd_l2_workspace_size(int(n))) // 8, device=device, dtype=torch.float64)
-
-
-def pgd_l2_step(x, x0, grad, alpha, eps, out=None, workspace=None):
-    """K28: y = x + alpha grad / (||grad||_2 + 1e-10); out = clamp(x0 + (y - x0) min(eps / ||y - x0||_2, 1), 0, 1), with ONE norm
-    over the whole tensor (phy_obj_atk_l2.py:110-120, shared-patch form).  Two launches, no host read.  ``workspace``:
-    pgd_l2_workspace(x.numel(), x.device), written by every call (one is allocated when none is given: not inside a graph capture
-    that is to be replayed).  ``out`` must be a tensor of its own."""
-    x, x0, grad = _c(x.detach()), _c(x0), _c(grad)
-    if x.shape != x0.shape or x.shape != grad.shape:
-        raise RuntimeError("pgd_l2_step: shape mismatch")
-    if not float(eps) >= 0.0:
-        raise RuntimeError("pgd_l2_step: eps must not be negative")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape:
-        raise RuntimeError("pgd_l2_step: shape mismatch")
-    if workspace is None:
-        workspace = pgd_l2_workspace(x.numel(), x.device)
-    N.check(N.lib().dmh_pgd_l2_step(N.ptr(x), N.ptr(x0), N.ptr(grad), float(alpha), float(eps), N.ptr(out), x.numel(),
-                                    N.ptr_f64(workspace), workspace.numel() * 8, N.stream()))
-    return out
-
-
-APGD_REC = 16       # floats per controller record (DMH_APGD_REC)
-
-
-def apgd_controller(steps, eps, loss0, rho=0.75):
-    """Device state of the Auto-PGD controller (K22) for one attack of ``steps`` iterations: (ctl [steps + 1, 16] with record 0
-    filled from phy_obj_atk_apgd.py:137,190-200, hist [steps] zeros, cursor int32 [2] zeros, size_decr, steps_min).  ``loss0``:
-    the device scalar holding the loss at the start point (loss_best and loss_best_last_check start there); nothing is read back."""
-    steps = int(steps)
-    if steps < 1 or steps >= 1 << 24:
-        raise RuntimeError("apgd_controller: steps must lie in [1, 2^24)")
-    _need_cuda(loss0)
-    k0, steps_min, size_decr = max(int(0.22 * steps), 1), max(int(0.06 * steps), 1), max(int(0.03 * steps), 1)
-    host = torch.zeros((steps + 1, APGD_REC), dtype=torch.float32)
-    host[0, 0], host[0, 1], host[0, 4], host[0, 7] = 2.0 * float(torch.tensor(eps, dtype=torch.float32)), 1.0, k0, 1.0
-    ctl = host.to(loss0.device, non_blocking=True)
-    ctl[0, 2:4] = loss0.detach().reshape(1).to(torch.float32)
-    hist = torch.zeros(steps, device=loss0.device, dtype=torch.float32)
-    cursor = torch.zeros(2, device=loss0.device, dtype=torch.int32)
-    return ctl, hist, cursor, size_decr, steps_min
-
-
-def _apgd_check(name, steps, ctl, hist, cursor, tensors):
-    n = tensors[0].numel()
-    for t in tensors:
-        if t.numel() != n or t.dtype != torch.float32:
-            raise RuntimeError("%s: the patch-sized tensors must be fp32 and of one size" % name)
-    if int(steps) < 1 or ctl.dtype != torch.float32 or ctl.numel() < (int(steps) + 1) * APGD_REC:
-        raise RuntimeError("%s: ctl must hold steps + 1 records of %d floats" % (name, APGD_REC))
-    if hist is not None and (hist.dtype != torch.float32 or hist.numel() < int(steps)):
-        raise RuntimeError("%s: hist must hold steps floats" % name)
-    if cursor.dtype != torch.int32 or cursor.numel() < 2:
-        raise RuntimeError("%s: cursor must be int32[2]" % name)
-    return n
-
-
-def apgd_step(x_adv, x_old, x0, grad, ctl, cursor, steps, eps):
-    """In place: x_old <- x_adv, x_adv <- Auto-PGD's momentum step (phy_obj_atk_apgd.py:207-215) with the step size and the
-    momentum weight of the controller record the device cursor points at.  No host value of the iteration enters."""
-    n = _apgd_check("apgd_step", steps, ctl, None, cursor, (x_adv, x_old, x0, grad))
-    N.check(N.lib().dmh_apgd_step(N.ptr(x_adv), N.ptr(x_old), N.ptr(x0), N.ptr(grad), N.ptr(ctl), N.ptr(cursor), int(steps),
-                                  float(eps), n, N.stream()))
-    return x_adv
-
-
-def apgd_commit(x_adv, g_new, grad, x_best, grad_best, x_ret, loss, ctl, hist, cursor, steps, size_decr, steps_min, rho=0.75):
-    """In place, decided on the device from ``loss`` (device scalar: the cost at the new x_adv, ``g_new`` its gradient) and the
-    controller record: best point, loss history, checkpoint, step halving, restart (phy_obj_atk_apgd.py:255-290); writes the
-    next record and advances the cursor."""
-    n = _apgd_check("apgd_commit", steps, ctl, hist, cursor, (x_adv, g_new, grad, x_best, grad_best, x_ret))
-    if loss.numel() != 1 or loss.dtype != torch.float32:
-        raise RuntimeError("apgd_commit: loss must be one fp32 value")
-    N.check(N.lib().dmh_apgd_commit(N.ptr(x_adv), N.ptr(g_new), N.ptr(grad), N.ptr(x_best), N.ptr(grad_best), N.ptr(x_ret),
-                                    N.ptr(loss), N.ptr(ctl), N.ptr(hist), N.ptr(cursor), int(steps), int(size_decr),
-                                    int(steps_min), float(rho), n, N.stream()))
-    return x_adv
-
-
-LIGHT_REC = 10      # doubles per query record (DMH_LIGHT_REC)
-
-
-def tube_light_table(params, alpha=1.0):
-    """Host: the record array [n, 10] float64 of K24 for ``params`` [n, 4] = (wavelength, angle, b, beta) per query.  Every scalar
-    is made in float64 the way the reference's Python makes it: k = round(tan(radians(angle)), 2) (phy_obj_atk_light.py:130-131),
-    full_end = int(sqrt(beta) + 0.5), light_end = int(sqrt(beta * 20) + 0.5), the divisor sqrt(1 + k k) and the colour of
-    wavelength_to_rgb with its ``** 0.8`` times alpha (light_simulation.py:40-84,143-146,150)."""
-    import math
-    params = np.asarray(params).reshape(-1, 4)
-    out = np.zeros((len(params), LIGHT_REC), dtype=np.float64)
-    for row, (wl, angle, b, beta) in zip(out, params.tolist()):
-        k = round(math.tan(math.radians(angle)), 2)
-        w, g = float(wl), 0.8
-        if 380 <= w <= 440:         # the first matching band wins at a shared boundary
-            att = 0.3 + 0.7 * (w - 380) / (440 - 380)
-            c = (((-(w - 440) / (440 - 380)) * att) ** g, 0.0, (1.0 * att) ** g)
-        elif 440 <= w <= 490:
-            c = (0.0, ((w - 440) / (490 - 440)) ** g, 1.0)
-        elif 490 <= w <= 510:
-            c = (0.0, 1.0, (-(w - 510) / (510 - 490)) ** g)
-        elif 510 <= w <= 580:
-            c = (((w - 510) / (580 - 510)) ** g, 1.0, 0.0)
-        elif 580 <= w <= 645:
-            c = (1.0, (-(w - 645) / (645 - 580)) ** g, 0.0)
-        elif 645 <= w <= 750:
-            c = ((1.0 * (0.3 + 0.7 * (750 - w) / (750 - 645))) ** g, 0.0, 0.0)
-        else:
-            c = (0.0, 0.0, 0.0)
-        row[:9] = (k, b, beta, int(math.sqrt(beta) + 0.5), int(math.sqrt(beta * 20) + 0.5), math.sqrt(1 + k * k),
-                   c[0] * alpha, c[1] * alpha, c[2] * alpha)
-    return out
-
-
-def tube_light_host(base_hwc, rec):
-    """Host twin of K24's compose in numpy (``Phy_obj_atk_light(host_chain=True)``): uint8 [H, W, 3] base and one record ->
-    the lit uint8 [H, W, 3], float64 / fp32 with the roundings of the reference's chain."""
-    h, w, _ = base_hwc.shape
-    k, b, beta, full, end, s = (rec[i] for i in range(6))
-    d = np.abs(k * np.arange(w, dtype=np.float64)[None, :] - np.arange(h, dtype=np.float64)[:, None] + b) / s
-    with np.errstate(divide="ignore", invalid="ignore"):
-        att = np.where(d <= full, 1.0, np.where(d <= end, beta / (d * d), 0.0))
-    lit = (np.stack([rec[6 + i] * att for i in range(3)], -1) * 255.0).astype(np.float32)
-    return np.clip(base_hwc.astype(np.float32) + lit, 0.0, 255.0).astype(np.uint8)
-
-
-def tube_light_state(n_queries, device):
-    """Device state of one tube-light search (K24): (state int32 [2] = (cursor 0, best query -1), best float [1] = 1e10,
-    cost float [n_queries] zeros)."""
-    if int(n_queries) < 1:
-        raise RuntimeError("tube_light_state: need at least one query")
-    state = torch.tensor([0, -1], dtype=torch.int32).to(device, non_blocking=True)
-    best = torch.full((1,), 1e10, device=device, dtype=torch.float32)
-    return state, best, torch.zeros(int(n_queries), device=device, dtype=torch.float32)
-
-
-def tube_light_compose(table, index, base_u8, out=None):
-    """The object lit by the tube light of record ``index[0]`` (a device int32: nothing of the query comes from the host) of
-    ``table`` [n, 10] float64: ``base_u8`` [1 or no batch, 3, H, W] uint8 -> fp32 [1, 3, H, W], bit-equal to the reference's
-    numpy / OpenCV / PIL chain.  An index outside [0, n) leaves ``out`` as it is."""
-    if table.dim() != 2 or table.shape[1] != LIGHT_REC:
-        raise RuntimeError("tube_light_compose: table must be [n, %d] float64" % LIGHT_REC)
-    if index.dtype != torch.int32 or index.numel() < 1:
-        raise RuntimeError("tube_light_compose: index must be int32")
-    if base_u8.dtype != torch.uint8 or base_u8.numel() % 3 or base_u8.dim() < 3 or base_u8.shape[-3] != 3 \
-            or base_u8.numel() != 3 * base_u8.shape[-2] * base_u8.shape[-1]:
-        raise RuntimeError("tube_light_compose: base must be uint8 [3, H, W]")
-    H, W = int(base_u8.shape[-2]), int(base_u8.shape[-1])
-    if out is None:
-        out = torch.zeros((1, 3, H, W), device=base_u8.device, dtype=torch.float32)
-    elif out.dtype != torch.float32 or out.numel() != base_u8.numel():
-        raise RuntimeError("tube_light_compose: out must be fp32 of the base's size")
-    N.check(N.lib().dmh_tube_light_compose(N.ptr_f64(table), N.ptr(index), N.ptr(base_u8), N.ptr(out), int(table.shape[0]), H, W,
-                                           N.stream()))
-    return out
-
-
-def tube_light_commit(cost_in, cost, best, state):
-    """In place, on the device (phy_obj_atk_light.py:165-167): the query the cursor state[0] points at gets ``cost_in`` (device
-    scalar) into ``cost``; a strictly smaller cost than ``best`` becomes the best and its query state[1]; the cursor advances."""
-    if cost_in.numel() != 1 or cost_in.dtype != torch.float32 or best.numel() != 1 or best.dtype != torch.float32 \
-            or cost.dtype != torch.float32:
-        raise RuntimeError("tube_light_commit: cost_in and best must be one fp32 value each, cost fp32")
-    if state.dtype != torch.int32 or state.numel() < 2:
-        raise RuntimeError("tube_light_commit: state must be int32[2]")
-    N.check(N.lib().dmh_tube_light_commit(N.ptr(cost_in), N.ptr(cost), N.ptr(best), N.ptr(state), int(cost.numel()), N.stream()))
-    return state
-
-
-GAUSS_REGION = (90, 170, 100, 200)      # rows 90:170, columns 100:200 of the object (phy_obj_atk_guassian.py:88)
-
-
-def gauss_sigmas(steps, h, w):
-    """Host: the sigmas of a ``steps``-step Gaussian-blur attack on an h x w object, in Python floats as the reference
-    accumulates them (phy_obj_atk_guassian.py:76-95): ``epsilon += 1.0 / steps``, ``sigma = epsilon * (max(h, w) // 2)``."""
-    if int(steps) < 1:
-        raise RuntimeError("gauss_sigmas: need at least one step")
-    epsilon, stepsize, max_sigma, out = 0.0, 1.0 / int(steps), max(int(h), int(w)) // 2, []
-    for _ in range(int(steps)):
-        epsilon += stepsize
-        out.append(epsilon * max_sigma)
-    return out
-
-
-def gauss_blur_table(sigmas):
-    """Host: (weights float64 [n, max lw + 1], radii int32 [n]) of K26.  Row s holds p[0 .. lw] -- the left half and the centre
-    of the symmetric kernel -- of scipy's ``_gaussian_kernel1d`` for sigma s with truncate 4.0, in float64 and in its order:
-    lw = int(4.0 * s + 0.5), p = exp(-0.5 / (s * s) * x ** 2) for x = -lw .. lw, p / p.sum(); zero padded."""
-    sigmas = [float(s) for s in sigmas]
-    if not sigmas:
-        raise RuntimeError("gauss_blur_table: need at least one sigma")
-    if not all(s > 0.0 and np.isfinite(s) for s in sigmas):
-        raise RuntimeError("gauss_blur_table: every sigma must be positive and finite")
-    radii = np.asarray([int(4.0 * s + 0.5) for s in sigmas], dtype=np.int32)
-    weights = np.zeros((len(sigmas), int(radii.max()) + 1), dtype=np.float64)
-    for row, s, lw in zip(weights, sigmas, radii.tolist()):
-        x = np.arange(-lw, lw + 1)
-        p = np.exp(-0.5 / (s * s) * x ** 2)
-        row[:lw + 1] = (p / p.sum())[:lw + 1]
-    return weights, radii
-
-
-def _gauss_region(region, H, W, name):
-    """``region`` = (r0, r1, c0, c1) clipped to an H x W patch the way the slices [r0:r1, c0:c1] clip."""
-    if len(region) != 4:
-        raise RuntimeError("%s: region must be (r0, r1, c0, c1)" % name)
-    r0, r1, _ = slice(int(region[0]), int(region[1])).indices(H)
-    c0, c1, _ = slice(int(region[2]), int(region[3])).indices(W)
-    if r1 <= r0 or c1 <= c0:
-        raise RuntimeError("%s: the rectangle %s clips to empty on a %d x %d patch" % (name, tuple(region), H, W))
-    return r0, r1, c0, c1
-
-
-def _gauss_axis_host(a, idx, p, lw):
-    """correlate1d of scipy (symmetric branch, mode 'reflect') along the last axis of ``a`` at the positions ``idx``: float64,
-    the taps in scipy's order, every operation rounded on its own; the result rounded to fp32."""
-    n = a.shape[-1]
-    a = a.astype(np.float64)
-
-    def r(j):
-        m = np.mod(j, 2 * n)
-        return np.where(m >= n, 2 * n - 1 - m, m)
-    tmp = a[..., idx] * p[lw]
-    for ll in range(-lw, 0):
-        tmp = tmp + (a[..., r(idx + ll)] + a[..., r(idx - ll)]) * p[lw + ll]
-    return tmp.astype(np.float32)
-
-
-def gauss_blur_host(x, sigma, region=None):
-    """Host twin of K26 in numpy (``Phy_obj_atk_guassian(host_chain=True)``): np.clip(gaussian_filter(x, [0, .., 0, s, s]), 0, 1) of
-    fp32 ``x`` [..., H, W] on the rectangle ``region`` (the whole patch by default), bit-equal to scipy's."""
-    x = np.asarray(x, dtype=np.float32)
-    H, W = x.shape[-2:]
-    r0, r1, c0, c1 = _gauss_region((0, H, 0, W) if region is None else region, H, W, "gauss_blur_host")
-    weights, radii = gauss_blur_table([sigma])
-    p, lw = weights[0], int(radii[0])
-    rows = _gauss_axis_host(np.swapaxes(x, -1, -2), np.arange(r0, r1), p, lw)        # axis H first: [..., W, rh]
-    out = _gauss_axis_host(np.swapaxes(rows, -1, -2), np.arange(c0, c1), p, lw)      # then axis W: [..., rh, rw]
-    return np.clip(out, 0, 1)
-
-
-def _gauss_obj(obj, name):
-    if obj.dtype != torch.float32 or obj.dim() not in (3, 4) or (obj.dim() == 4 and obj.shape[0] != 1):
-        raise RuntimeError("%s: obj must be fp32 [1, C, H, W] or [C, H, W]" % name)
-    return tuple(int(v) for v in obj.shape[-3:])
-
-
-def gauss_blur_windows(obj, weights, radii, region=GAUSS_REGION):
-    """K26: np.clip(scipy.ndimage.gaussian_filter(obj, [0, 0, s, s]), 0, 1) on the rectangle ``region`` = (r0, r1, c0, c1) of
-    fp32 ``obj`` [1, C, H, W] for every row of ``(weights, radii) = gauss_blur_table(sigmas)`` (device float64 [n, k] / int32
-    [n]) -> fp32 [n, C, r1 - r0, c1 - c0], bit-equal to scipy's; two launches for all n."""
-    C_, H, W = _gauss_obj(obj, "gauss_blur_windows")
-    if weights.dim() != 2 or weights.dtype != torch.float64:
-        raise RuntimeError("gauss_blur_windows: weights must be float64 [steps, k]")
-    n = int(weights.shape[0])
-    if n < 1 or int(weights.shape[1]) < 1:
-        raise RuntimeError("gauss_blur_windows: need at least one step")
-    if radii.dtype != torch.int32 or radii.dim() != 1 or int(radii.shape[0]) != n:
-        raise RuntimeError("gauss_blur_windows: radii must be int32 [steps]")
-    r0, r1, c0, c1 = _gauss_region(region, H, W, "gauss_blur_windows")
-    tmp = torch.empty((n, C_, r1 - r0, W), device=obj.device, dtype=torch.float32)
-    windows = torch.empty((n, C_, r1 - r0, c1 - c0), device=obj.device, dtype=torch.float32)
-    N.check(N.lib().dmh_gauss_blur_windows(N.ptr(obj), N.ptr_f64(weights), N.ptr(radii), N.ptr(tmp), N.ptr(windows), n,
-                                           int(weights.shape[1]), C_, H, W, r0, r1, c0, c1, N.stream()))
-    return windows
-
-
-def gauss_blur_compose(windows, index, obj, region=GAUSS_REGION, out=None):
-    """The object with window ``index[0]`` (a device int32: nothing of the step comes from the host) of ``windows``
-    [n, C, rh, rw] in the rectangle ``region`` and ``obj`` elsewhere -> fp32 [1, C, H, W].  An index outside [0, n) leaves
-    ``out`` as it is."""
-    C_, H, W = _gauss_obj(obj, "gauss_blur_compose")
-    r0, r1, c0, c1 = _gauss_region(region, H, W, "gauss_blur_compose")
-    if windows.dtype != torch.float32 or windows.dim() != 4 or int(windows.shape[0]) < 1 \
-            or tuple(windows.shape[1:]) != (C_, r1 - r0, c1 - c0):
-        raise RuntimeError("gauss_blur_compose: windows must be fp32 [steps, %d, %d, %d] for this rectangle" % (C_, r1 - r0, c1 - c0))
-    if index.dtype != torch.int32 or index.numel() < 1:
-        raise RuntimeError("gauss_blur_compose: index must be int32")
-    if out is None:
-        out = torch.zeros((1, C_, H, W), device=obj.device, dtype=torch.float32)
-    elif out.dtype != torch.float32 or out.numel() != obj.numel():
-        raise RuntimeError("gauss_blur_compose: out must be fp32 of the object's size")
-    N.check(N.lib().dmh_gauss_blur_compose(N.ptr(windows), N.ptr(index), N.ptr(obj), N.ptr(out), int(windows.shape[0]), C_, H, W,
-                                           r0, r1, c0, c1, N.stream()))
-    return out
-
-
-def square_sides(n_queries, c, h, w, p_init=0.8, resc_schedule=True):
-    """Host: the side of the square of every iteration of a Square attack of ``n_queries`` iterations on a c x h x w object, in
-    Python floats as the reference makes it: ``p_selection`` (phy_obj_atk_square.py:222-249, with ``int(it / n_queries *
-    10000)`` under ``resc_schedule``) and ``s = max(int(round(sqrt(p * n_features / c))), 1)`` (:281)."""
-    import math
-    n_queries = int(n_queries)
-    if n_queries < 1:
-        raise RuntimeError("square_sides: need at least one query")
-    n_features, out = c * h * w, []
-    for it in range(n_queries):
-        if resc_schedule:
-            it = int(it / n_queries * 10000)
-        p = p_init
-        for above, div in ((10, 2), (50, 4), (200, 8), (500, 16), (1000, 32), (2000, 64), (4000, 128), (6000, 256), (8000, 512)):
-            if it > above:
-                p = p_init / div
-        out.append(max(int(round(math.sqrt(p * n_features / c))), 1))
-    return out
-
-
-def square_table(n_queries, c, h, w, p_init=0.8, resc_schedule=True):
-    """Host: every draw of a Square attack, from the CPU torch global generator with the reference's expressions in its call
-    order -- the start stripes ``sign(2 rand([1, c, 1, w]) - 1)`` (:259-260, :173-175), then per iteration ``vh``, ``vw`` =
-    ``(0 + (h - s - 0) rand([1])).long()`` (:177-179, :282-283) and the signs ``sign(2 rand([c, 1, 1]) - 1)`` (:286).
-    Returns (table int32 [n_queries + 1, 3 + c] = (vh, vw, s, signs) with row q the square of iteration q - 1 and row 0 zero:
-    query 0 is the stripes; stripes fp32 [c, w]).  A side larger than min(h, w) -- where the reference would slice with a negative
-    bound -- is refused before any draw."""
-    sides = square_sides(n_queries, c, h, w, p_init, resc_schedule)
-    if max(sides) > min(h, w):
-        raise RuntimeError("square_table: the schedule's largest square (%d) exceeds the %d x %d object; lower p_init"
-                           % (max(sides), h, w))
-    stripes = torch.sign(2 * torch.rand([1, c, 1, w]) - 1).reshape(c, w).contiguous()
-    table = np.zeros((len(sides) + 1, 3 + c), dtype=np.int32)
-    for row, s in zip(table[1:], sides):
-        vh = (0 + (h - s - 0) * torch.rand([1])).long()
-        vw = (0 + (w - s - 0) * torch.rand([1])).long()
-        sign = torch.sign(2 * torch.rand([c, 1, 1]) - 1)
-        row[0], row[1], row[2] = int(vh), int(vw), s
-        row[3:] = sign.reshape(c).numpy()
-    return table, stripes
-
-
-def _square_operands(name, x0, x_best, x_new, table, stripes):
-    if x0.dtype != torch.float32 or x0.dim() not in (3, 4) or (x0.dim() == 4 and x0.shape[0] != 1):
-        raise RuntimeError("%s: x0 must be fp32 [1, C, H, W] or [C, H, W]" % name)
-    C_, H, W = (int(v) for v in x0.shape[-3:])
-    for t in (x_best, x_new):
-        if t.dtype != torch.float32 or t.numel() != x0.numel() or tuple(t.shape[-3:]) != (C_, H, W):
-            raise RuntimeError("%s: x_best and x_new must be fp32 of x0's size" % name)
-    ptrs = {x0.data_ptr(), x_best.data_ptr(), x_new.data_ptr()}
-    if len(ptrs) != 3:
-        raise RuntimeError("%s: x0, x_best and x_new must be three different buffers" % name)
-    if table.dtype != torch.int32 or table.dim() != 2 or int(table.shape[0]) < 1 or int(table.shape[1]) != 3 + C_:
-        raise RuntimeError("%s: table must be int32 [n, %d]" % (name, 3 + C_))
-    if stripes.dtype != torch.float32 or tuple(stripes.shape) != (C_, W):
-        raise RuntimeError("%s: stripes must be fp32 [%d, %d]" % (name, C_, W))
-    return C_, H, W
-
-
-def square_propose(x0, x_best, x_new, table, stripes, state, eps):
-    """K27, in place, driven by K24's ``state`` = (cursor q, best query) on the device: if query q - 1 became the best,
-    ``x_best`` <- ``x_new``; then ``x_new`` <- the candidate of query q -- the stripes for q = 0, else ``x_best`` with the square
-    of ``table`` row q pushed by 2 eps sign_c and projected onto [x0 - eps, x0 + eps] and [0, 1] (phy_obj_atk_square.py:284-291),
-    bit-equal to the torch expression.  q = n only absorbs; any other q outside [0, n) does nothing."""
-    C_, H, W = _square_operands("square_propose", x0, x_best, x_new, table, stripes)
-    if state.dtype != torch.int32 or state.numel() < 2:
-        raise RuntimeError("square_propose: state must be int32[2]")
-    if not float(eps) >= 0.0:
-        raise RuntimeError("square_propose: eps must not be negative")
-    N.check(N.lib().dmh_square_propose(N.ptr(x0), N.ptr(x_best), N.ptr(x_new), N.ptr(table), N.ptr(stripes), N.ptr(state),
-                                       int(table.shape[0]), C_, H, W, float(eps), N.stream()))
-    return x_new
-
-
-def square_host(x0, x_best, x_new, table, stripes, q, accept, eps):
-    """Host twin of K27 in torch on the CPU (``Phy_obj_atk_Square(host_chain=True)``): returns the new (x_best, x_new) for query
-    ``q`` after the decision ``accept`` about query q - 1, with the reference's own expressions (:259-260, :284-291)."""
-    C_, H, W = _square_operands("square_host", x0, x_best, x_new, torch.as_tensor(table), stripes)
-    n = len(table)
-    if accept and 0 < q <= n:
-        x_best = x_new.clone()
-    if q == 0:
-        x_new = torch.clamp(x0 + eps * stripes.reshape(1, C_, 1, W), 0., 1.).reshape(x0.shape)
-    elif 0 < q < n:
-        vh, vw, s = (int(v) for v in table[q][:3])
-        new_deltas = torch.zeros([C_, H, W])
-        new_deltas[:, vh:vh + s, vw:vw + s] = 2. * eps * torch.as_tensor(table[q][3:]).float().reshape(C_, 1, 1)
-        x_new = x_best.reshape(C_, H, W) + new_deltas
-        x_new = torch.min(torch.max(x_new, x0.reshape(C_, H, W) - eps), x0.reshape(C_, H, W) + eps)
-        x_new = torch.clamp(x_new, 0., 1.).reshape(x0.shape)
-    return x_best, x_new
-
-
-def l0_compose_fwd_launch(obj, pos, neg, l0_clip, finalize):
-    """K5 on contiguous tensors: (adv, count int32 [1])."""
-    if obj.dim() != 4 or obj.shape[0] != 1 or obj.shape != pos.shape or obj.shape != neg.shape:
-        raise RuntimeError("l0_compose: obj/pos/neg must all be [1,C,H,W]")
-    adv = torch.empty_like(obj)
-    count = torch.zeros(1, device=obj.device, dtype=torch.int32)
-    N.check(N.lib().dmh_l0_compose_fwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), obj.shape[1], obj.shape[2] * obj.shape[3],
-                                       float(l0_clip), int(finalize), N.ptr(adv), N.ptr(count), N.stream()))
-    return adv, count
-
-
-def l0_compose_bwd_launch(obj, pos, neg, g_adv):
-    g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
-    N.check(N.lib().dmh_l0_compose_bwd(N.ptr(obj), N.ptr(pos), N.ptr(neg), N.ptr(g_adv), obj.shape[1], obj.shape[2] * obj.shape[3],
-                                       N.ptr(g_pos), N.ptr(g_neg), 0, N.stream()))
-    return g_pos, g_neg
-
-
-class _L0Compose(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, obj, pos, neg, l0_clip, finalize):
-        adv, count = l0_compose_fwd_launch(obj, pos, neg, l0_clip, finalize)
-        ctx.save_for_backward(obj, pos, neg)
-        ctx.mark_non_differentiable(count)
-        return adv, count
-
-    @staticmethod
-    def backward(ctx, g_adv, g_count):
-        obj, pos, neg = ctx.saved_tensors
-        g_pos, g_neg = l0_compose_bwd_launch(obj, pos, neg, _c(g_adv))
-        return None, g_pos, g_neg, None, None
-
-
-def l0_compose(obj, pos, neg, l0_clip=1.0 / 255.0, finalize=False):
-    """adv = clamp(obj + clamp(pos,0,1) - clamp(neg,0,1), 0, 1) and the L0 count of the thresholded
-    pattern (phy_obj_atk_l0.py:94-99, 43-52; finalize=True applies :143-150).  Returns (adv, count[int32,1])."""
-    return _L0Compose.apply(_c(obj), _c(pos), _c(neg), float(l0_clip), bool(finalize))
-
-
-def l0_mask_cost_fwd_launch(pos, neg):
-    if pos.dim() != 4 or pos.shape[0] != 1 or pos.shape != neg.shape:
-        raise RuntimeError("l0_mask_cost: pos/neg must be [1,C,H,W]")
-    lib = N.lib()
-    Cc, HW = pos.shape[1], pos.shape[2] * pos.shape[3]
-    part = torch.empty(lib.dmh_l0_mask_partials_size(HW), device=pos.device, dtype=torch.float32)
-    cost = torch.empty((), device=pos.device, dtype=torch.float32)
-    N.check(lib.dmh_l0_mask_cost_fwd(N.ptr(pos), N.ptr(neg), Cc, HW, N.ptr(part), N.ptr(cost), N.stream()))
-    return cost
-
-
-def l0_mask_cost_bwd_launch(pos, neg, g):
-    g_pos, g_neg = torch.empty_like(pos), torch.empty_like(neg)
-    N.check(N.lib().dmh_l0_mask_cost_bwd(N.ptr(pos), N.ptr(neg), pos.shape[1], pos.shape[2] * pos.shape[3],
-                                         N.ptr(_c(g.to(torch.float32))), None, N.ptr(g_pos), N.ptr(g_neg), 0, N.stream()))
-    return g_pos, g_neg
-
-
-class _L0MaskCost(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pos, neg):
-        ctx.save_for_backward(pos, neg)
-        return l0_mask_cost_fwd_launch(pos, neg)
-
-    @staticmethod
-    def backward(ctx, g):
-        return l0_mask_cost_bwd_launch(*ctx.saved_tensors, g)
-
-
-def l0_mask_cost(pos, neg):
-    """mean(max_c(tanh(pos/10)/(2-1e-7)+0.5)) + same for neg (phy_obj_atk_l0.py:130-132)."""
-    return _L0MaskCost.apply(_c(pos), _c(neg))
-
-
-L0_REC = 8          # floats per record of the fused L0 update (DMH_L0_REC)
-L0_BETAS = (0.5, 0.9)   # phy_obj_atk_l0.py:85; K23 holds them as constants
-
-
-def l0_adam_table(steps, lr):
-    """Adam's bias corrections for t = 1 .. 2 * steps as K23 reads them: a host fp32 tensor [2 * steps, 2] of
-    (lr / (1 - b1^t), sqrt(1 - b2^t)), computed in double and rounded once."""
-    import math
-    b1, b2 = L0_BETAS
-    rows = [(float(lr) / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)) for t in range(1, 2 * int(steps) + 1)]
-    return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
-
-
-class L0FusedState(object):
-    """The device buffers of one fused L0 attack of ``steps`` (2 * steps iterations at the most): the two patterns (taken over,
-    updated in place), Adam's m / v for both, the composed patch, and the controller's words -- count int32 [2 steps + 1], rec
-    [2 steps, L0_REC], cursor int32 [2], tab [2 steps, 2].  Nothing here is read by the host while the attack runs."""
-
-    def __init__(self, pos, neg, steps, lr):
-        steps = int(steps)
-        if steps < 1 or steps >= 1 << 24:
-            raise RuntimeError("L0FusedState: steps must lie in [1, 2^24)")
-        _need_cuda(pos)
-        dev = pos.device
-        self.steps = steps
-        self.pos, self.neg = _c(pos.detach()), _c(neg.detach())
-        state = torch.zeros((4,) + tuple(pos.shape), device=dev, dtype=torch.float32)
-        self.m_pos, self.v_pos, self.m_neg, self.v_neg = state[0], state[1], state[2], state[3]
-        self.adv = torch.empty_like(self.pos)
-        self.count = torch.zeros(2 * steps + 1, device=dev, dtype=torch.int32)
-        self.rec = torch.zeros((2 * steps, L0_REC), device=dev, dtype=torch.float32)
-        self.cursor = torch.zeros(2, device=dev, dtype=torch.int32)
-        self.tab = l0_adam_table(steps, lr).to(dev, non_blocking=True)
-
-    def step(self, obj, g_adv, adv_cost, mask_cost, mask_wt, thresh, l0_clip):
-        return l0_fused_step(obj, self.pos, self.neg, self.m_pos, self.v_pos, self.m_neg, self.v_neg, g_adv, self.adv,
-                             self.count, self.rec, self.cursor, self.tab, adv_cost, mask_cost, self.steps, mask_wt, thresh,
-                             l0_clip)
-
-
-def l0_fused_step(obj, pos, neg, m_pos, v_pos, m_neg, v_neg, g_adv, adv, count, rec, cursor, tab, adv_cost, mask_cost, steps,
-                  mask_wt, thresh, l0_clip=1.0 / 255.0):
-    """K23, in place: iteration i = cursor[0] of the L0 attack from ``g_adv`` = d adv_cost / d composed patch to the next composed
-    patch ``adv`` -- mask weight from count[i] / count[0] <= thresh, both clamps' gates, the mask cost's gradient, Adam on both
-    patterns, compose, count[i + 1], record i, cursor + 1 (phy_obj_atk_l0.py:92-138).  No host value of the iteration enters."""
-    steps = int(steps)
-    if obj.dim() != 4 or obj.shape[0] != 1:
-        raise RuntimeError("l0_fused_step: obj must be [1,C,H,W]")
-    n = obj.numel()
-    for t in (obj, pos, neg, m_pos, v_pos, m_neg, v_neg, g_adv, adv):
-        if t.numel() != n or t.dtype != torch.float32:
-            raise RuntimeError("l0_fused_step: the patch-sized tensors must be fp32 and of one size")
-    if steps < 1 or steps >= 1 << 24:
-        raise RuntimeError("l0_fused_step: steps must lie in [1, 2^24)")
-    if count.dtype != torch.int32 or count.numel() < 2 * steps + 1:
-        raise RuntimeError("l0_fused_step: count must be int32[2 * steps + 1]")
-    if rec.dtype != torch.float32 or rec.numel() < 2 * steps * L0_REC:
-        raise RuntimeError("l0_fused_step: rec must hold 2 * steps records of %d floats" % L0_REC)
-    if tab.dtype != torch.float32 or tab.numel() < 4 * steps:
-        raise RuntimeError("l0_fused_step: tab must hold 2 * steps pairs of floats")
-    if cursor.dtype != torch.int32 or cursor.numel() < 2:
-        raise RuntimeError("l0_fused_step: cursor must be int32[2]")
-    for name, t in (("adv_cost", adv_cost), ("mask_cost", mask_cost)):
-        if t is not None and (t.numel() != 1 or t.dtype != torch.float32):
-            raise RuntimeError("l0_fused_step: %s must be one fp32 value" % name)
-    N.check(N.lib().dmh_l0_fused_step(N.ptr(obj), N.ptr(pos), N.ptr(neg), N.ptr(m_pos), N.ptr(v_pos), N.ptr(m_neg), N.ptr(v_neg),
-                                      N.ptr(g_adv), N.ptr(adv), N.ptr(count), N.ptr(rec), N.ptr(cursor), N.ptr(tab),
-                                      N.ptr(adv_cost), N.ptr(mask_cost), steps, obj.shape[1], obj.shape[2] * obj.shape[3],
-                                      float(mask_wt), float(thresh), float(l0_clip), N.stream()))
-    return adv
 
 
 class _UpCatPad(torch.autograd.Function):
@@ -3055,188 +2452,6 @@ def encoder_head_incremental(x, plan, tab, clean, conv1_weight, aff0, blocks, la
     return _EncHeadInc.apply(_c(x), plan, _c(tab), clean, *_head_args(conv1_weight, aff0, *blocks, *(layer2 or ())))
 
 
-def masked_depth_errors(disp_gt, disp_pred, mask=None, min_depth=0.1, max_depth=100.0, scale=5.4, clamp_lo=1e-3,
-                        clamp_hi=80.0):
-    """The eight attack-evaluation metrics of MD2/evaluate_depth.py:57-99 computed from two disparity maps in one
-    pass on the device: returns a tensor [abs_err, abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3]."""
-    lib = N.lib()
-    disp_gt, disp_pred = _c(disp_gt.detach()), _c(disp_pred.detach())
-    n = disp_gt.numel()
-    if disp_pred.numel() != n or (mask is not None and mask.numel() != n):
-        raise RuntimeError("masked_depth_errors: size mismatch")
-    part = torch.empty(lib.dmh_depth_errors_partials_size(n), device=disp_gt.device, dtype=torch.float32)
-    out = torch.empty(8, device=disp_gt.device, dtype=torch.float32)
-    N.check(lib.dmh_masked_depth_errors(N.ptr(disp_gt), N.ptr(disp_pred), N.ptr(None if mask is None else _c(mask)), n,
-                                        min_depth, max_depth, scale, clamp_lo, clamp_hi, N.ptr(part), N.ptr(out),
-                                        N.stream()))
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------------------- K25
-EIGEN_REC, EIGEN_CHUNK, EIGEN_MAX_BATCH = 8, 8192, 64       # DMH_EIGEN_* of include/dmh_hip.h
-
-
-def eigen_crop(gt_h, gt_w):
-    """The Eigen crop (y0, y1, x0, x1) of a gt_h x gt_w map, in double and truncated as MD2/evaluate_depth.py:363-364 does."""
-    return np.array([0.40810811 * gt_h, 0.99189189 * gt_h, 0.03594771 * gt_w, 0.96405229 * gt_w]).astype(np.int32)
-
-
-def _eigen_f32(t, name):
-    if not torch.is_tensor(t) or t.dtype != torch.float32:
-        raise RuntimeError("libdmh_hip ops compute in fp32; got %s for %s" % (getattr(t, "dtype", type(t)), name))
-    return t
-
-
-def _eigen_i32(t, name):
-    if not torch.is_tensor(t) or t.dtype != torch.int32:
-        raise RuntimeError("%s must be int32; got %s" % (name, getattr(t, "dtype", type(t))))
-    return t
-
-
-def _eigen_ws(n, device):
-    return torch.empty(N.lib().dmh_eigen_select_ws_size(n), device=device, dtype=torch.int32)
-
-
-def eigen_gt_stats(gt, table, blk_img, first, n, b0, grid, eigen):
-    """K25 on the ground truth alone: (medians fp32 [n], valid counts int32 [n]) of the images first .. first + n - 1 of a pack
-    (np.median of the valid values; NaN and 0 for a map without a valid pixel).  Three histogram passes, no sort."""
-    lib = N.lib()
-    _eigen_f32(gt, "gt"), _eigen_i32(table, "table"), _eigen_i32(blk_img, "blk_img")
-    if not 0 < n <= EIGEN_MAX_BATCH:
-        raise RuntimeError("eigen_gt_stats: 1 .. %d images per call; got %d" % (EIGEN_MAX_BATCH, n))
-    med = torch.empty(n, device=gt.device, dtype=torch.float32)
-    cnt = torch.empty(n, device=gt.device, dtype=torch.int32)
-    ws = _eigen_ws(n, gt.device)
-    N.check(lib.dmh_eigen_gt_stats(N.ptr(gt), gt.numel(), N.ptr(table), N.ptr(blk_img), int(table.shape[0]), blk_img.numel(),
-                                   int(first), int(n), int(b0), int(grid), int(bool(eigen)), N.ptr(ws), N.ptr(med), N.ptr(cnt),
-                                   N.stream()))
-    return med, cnt
-
-
-def eigen_depth_errors_launch(pred_disp, pred_disp_flip, gt, table, blk_img, med_gt, first, b0, grid, px0, npx, eigen,
-                              scale_factor=1.0, median_scaling=True):
-    """K25's launches for one batch on plain tensors (what ``eigen_depth_errors`` and ``torch.ops.dmh.eigen_depth_errors`` share):
-    (errors [n, 8], ratios [n], depth [npx], medians of the valid depths [n]).  ``px0`` / ``npx``: offset and pixel count of the
-    batch inside ``gt``; ``b0`` / ``grid``: its work blocks.  Without median scaling the medians are not computed: they and
-    ``ratios`` are NaN."""
-    lib = N.lib()
-    _eigen_f32(pred_disp, "pred_disp"), _eigen_f32(gt, "gt"), _eigen_f32(med_gt, "med_gt")
-    _eigen_i32(table, "table"), _eigen_i32(blk_img, "blk_img")
-    if pred_disp.dim() != 3:
-        raise RuntimeError("eigen_depth_errors: pred_disp must be [n, h, w]")
-    n, h, w = [int(v) for v in pred_disp.shape]
-    if not 0 < n <= EIGEN_MAX_BATCH:
-        raise RuntimeError("eigen_depth_errors: 1 .. %d predictions per call; got %d" % (EIGEN_MAX_BATCH, n))
-    if pred_disp_flip is not None and (_eigen_f32(pred_disp_flip, "pred_disp_flip").shape != pred_disp.shape):
-        raise RuntimeError("eigen_depth_errors: pred_disp_flip must have pred_disp's shape")
-    if med_gt.numel() != table.shape[0] or table.dim() != 2 or table.shape[1] != EIGEN_REC:
-        raise RuntimeError("eigen_depth_errors: table must be [N, %d] and med_gt [N]" % EIGEN_REC)
-    if px0 < 0 or npx <= 0 or px0 + npx > gt.numel():
-        raise RuntimeError("eigen_depth_errors: the batch's pixels must lie in gt")
-    dev = pred_disp.device
-    pred_disp = _c(pred_disp.detach())
-    flip = None if pred_disp_flip is None else _c(pred_disp_flip.detach())
-    depth = torch.empty(int(npx), device=dev, dtype=torch.float32)
-    errors = torch.empty((n, 8), device=dev, dtype=torch.float32)
-    part = torch.empty(lib.dmh_eigen_partials_size(int(grid)), device=dev, dtype=torch.float32)
-    ws = _eigen_ws(n, dev) if median_scaling else None
-    sizes = (int(table.shape[0]), blk_img.numel(), int(first), n, int(b0), int(grid))
-    N.check(lib.dmh_eigen_pred_depth(N.ptr(pred_disp), N.ptr(flip), h, w, N.ptr(gt), gt.numel(), N.ptr(table), N.ptr(blk_img),
-                                     *sizes, int(bool(eigen)), float(scale_factor), int(px0), N.ptr(depth), depth.numel(),
-                                     N.ptr(ws), N.stream()))
-    if median_scaling:
-        med = torch.empty(n, device=dev, dtype=torch.float32)
-        ratios = torch.empty(n, device=dev, dtype=torch.float32)
-        N.check(lib.dmh_eigen_pred_ratio(N.ptr(depth), depth.numel(), int(px0), gt.numel(), N.ptr(table), N.ptr(blk_img), *sizes,
-                                         N.ptr(ws), N.ptr(med_gt), N.ptr(med), N.ptr(ratios), N.stream()))
-    else:
-        ratios = torch.full((n,), float("nan"), device=dev, dtype=torch.float32)
-        med = ratios.clone()
-    N.check(lib.dmh_eigen_metrics(N.ptr(gt), gt.numel(), N.ptr(depth), depth.numel(), int(px0), N.ptr(table), N.ptr(blk_img),
-                                  *sizes, N.ptr(ratios if median_scaling else None), N.ptr(part), N.ptr(errors), N.stream()))
-    return errors, ratios, depth, med
-
-
-class EigenGtPack(object):
-    """The ground truth of an evaluation set on the device (``eigen_gt_pack``): ``gt`` the maps one after the other (fp32),
-    ``table`` / ``blk_img`` K25's tables, ``counts`` / ``medians`` the valid pixels and np.median of the valid values of every map
-    (they depend on the ground truth only: computed once, here).  Host copies: ``shapes``, ``crops`` (y0, y1, x0, x1),
-    ``offsets`` [N + 1] and ``blk_first`` [N + 1]."""
-
-    def __init__(self, gt, table, blk_img, shapes, crops, offsets, blk_first, eval_split):
-        self.gt, self.table, self.blk_img = gt, table, blk_img
-        self.shapes, self.crops, self.offsets, self.blk_first = shapes, crops, offsets, blk_first
-        self.eval_split, self.eigen = eval_split, eval_split == "eigen"
-        self.counts = self.medians = None
-
-    def __len__(self):
-        return len(self.shapes)
-
-    def view(self, flat, first, i):
-        """Image ``first + i`` of a batch's flat buffer (``return_pred``) as [gt_h, gt_w]."""
-        o = int(self.offsets[first + i] - self.offsets[first])
-        gh, gw = self.shapes[first + i]
-        return flat[o:o + gh * gw].view(gh, gw)
-
-
-def eigen_gt_pack(gt_list, eval_split, device):
-    """Packs the 2-D ground-truth maps ``gt_list`` (their own, different sizes) for K25: one flat fp32 buffer, the record table
-    (crop bounds of MD2/evaluate_depth.py:363-364 for split ``eigen``, the whole map otherwise), and per map the number of valid
-    pixels and the median of the valid values."""
-    device = torch.device(device)
-    _need_cuda(device)
-    maps = [np.ascontiguousarray(np.asarray(g), dtype=np.float32) for g in gt_list]
-    if not maps or any(m.ndim != 2 or m.size == 0 for m in maps):
-        raise RuntimeError("eigen_gt_pack: need at least one ground-truth map, all of them 2-D and not empty")
-    shapes = [tuple(int(v) for v in m.shape) for m in maps]
-    sizes = np.array([h * w for h, w in shapes], dtype=np.int64)
-    offsets = np.concatenate([[0], np.cumsum(sizes)])
-    blocks = (sizes + EIGEN_CHUNK - 1) // EIGEN_CHUNK
-    blk_first = np.concatenate([[0], np.cumsum(blocks)])
-    if offsets[-1] >= 2 ** 31:
-        raise RuntimeError("eigen_gt_pack: %d pixels; a pack holds fewer than 2^31" % offsets[-1])
-    eigen = eval_split == "eigen"
-    crops = np.stack([eigen_crop(h, w) if eigen else np.array([0, h, 0, w], dtype=np.int32) for h, w in shapes])
-    table = np.zeros((len(maps), EIGEN_REC), dtype=np.int32)
-    table[:, 0], table[:, 1], table[:, 2] = offsets[:-1], [s[0] for s in shapes], [s[1] for s in shapes]
-    table[:, 3:7], table[:, 7] = crops, blk_first[:-1]
-    blk_img = np.repeat(np.arange(len(maps), dtype=np.int32), blocks)
-    flat = np.concatenate([m.ravel() for m in maps])
-    pack = EigenGtPack(torch.from_numpy(flat).to(device), torch.from_numpy(table).to(device), torch.from_numpy(blk_img).to(device),
-                       shapes, crops, offsets, blk_first, eval_split)
-    med, cnt = [], []
-    for first in range(0, len(maps), EIGEN_MAX_BATCH):
-        n = min(EIGEN_MAX_BATCH, len(maps) - first)
-        m, c = eigen_gt_stats(pack.gt, pack.table, pack.blk_img, first, n, int(blk_first[first]),
-                              int(blk_first[first + n] - blk_first[first]), eigen)
-        med.append(m)
-        cnt.append(c)
-    pack.medians, pack.counts = torch.cat(med), torch.cat(cnt)
-    return pack
-
-
-def eigen_depth_errors(pred_disp, pack, first, *, pred_disp_flip=None, scale_factor=1.0, median_scaling=True, return_pred=False):
-    """MD2/evaluate_depth.py:351-384 for the predictions ``pred_disp`` [n, h, w] (disparities at network resolution) of the images
-    ``first`` .. ``first + n - 1`` of ``pack``: (errors [n, 8], ratios [n]) on the device, nothing read by the host.
-    ``pred_disp_flip``: the predictions of the mirrored frames (not mirrored back): --post_process.  ``scale_factor``:
-    --pred_depth_scale_factor.  ``median_scaling`` off: no medians, ``ratios`` is NaN.  ``return_pred``: also the scratch buffer,
-    laid out like the batch's ground truth (``pack.view``): the depth before median scaling at the valid pixels, NaN (all bits
-    set) at the others; and the medians [n] of its valid values."""
-    if not isinstance(pack, EigenGtPack):
-        raise RuntimeError("eigen_depth_errors: pack must come from eigen_gt_pack")
-    if not torch.is_tensor(pred_disp) or pred_disp.dim() != 3:
-        raise RuntimeError("eigen_depth_errors: pred_disp must be [n, h, w]")
-    n, first = int(pred_disp.shape[0]), int(first)
-    if first < 0 or n == 0 or first + n > len(pack):
-        raise RuntimeError("eigen_depth_errors: predictions %d .. %d, but the pack holds %d ground-truth maps" % (
-            first, first + n - 1, len(pack)))
-    px0, b0 = int(pack.offsets[first]), int(pack.blk_first[first])
-    errors, ratios, depth, med = eigen_depth_errors_launch(
-        pred_disp, pred_disp_flip, pack.gt, pack.table, pack.blk_img, pack.medians, first, b0, int(pack.blk_first[first + n]) - b0,
-        px0, int(pack.offsets[first + n]) - px0, pack.eigen, scale_factor, median_scaling)
-    return (errors, ratios, depth, med) if return_pred else (errors, ratios)
-
-
 # ----------------------------------------------------------------------------------------------------------------- K29
 POSE_SCALE = 0.01       # MD2/networks/pose_decoder.py:49
 
@@ -3585,1448 +2800,3 @@ def cost_volume_bwd_host(current_feats, lookup_feats, poses, K, invK, depth_bins
                 np.add.at(out, flat.reshape(-1), dwt * wgt.reshape(-1, 1))
             d_look[b, l] = out.T.reshape(Cc, H, W)
     return d_cur, d_look
-
-
-# ------------------------------------------------------------------------------------ the loader operators (K31, K32, K34)
-class _UploadCache(object):
-    """The last ``cap`` sets of small tables a loader operator has uploaded, by key, so that a repeated batch shape launches with
-    the same device buffers and no copy.  An entry keeps the event of its upload -- a hit on another stream a moment later waits
-    for it -- and the pinned host copies, which live as long as the upload may.  A key a captured graph has launched with is
-    ``held``: a replay reads its buffers, so it is never evicted.  ``what``: the error a miss raises inside a capture."""
-
-    def __init__(self, cap, what):
-        self.cap, self.what, self.entries, self.held = cap, what, OrderedDict(), set()
-
-    def __len__(self):
-        return len(self.entries)
-
-    def __contains__(self, key):
-        return key in self.entries
-
-    def get(self, key, device, make):
-        """(device tensors, payload) of ``key``; at a miss ``make()`` gives (host tensors, payload): the tensors are pinned and
-        uploaded without a wait, the payload (host values that go with them) is kept as it is."""
-        hit = self.entries.get(key)
-        if hit is not None:
-            self.entries.move_to_end(key)
-            if torch.cuda.is_current_stream_capturing():
-                self.held.add(key)
-            elif not hit[1].query():
-                torch.cuda.current_stream(device).wait_event(hit[1])        # uploaded on another stream a moment ago
-            return hit[0], hit[3]
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(self.what)
-        host, payload = make()
-        host = [h.pin_memory() for h in host]
-        on_device = [h.to(device, non_blocking=True) for h in host]
-        uploaded = torch.cuda.Event()
-        uploaded.record(torch.cuda.current_stream(device))
-        self.entries[key] = (on_device, uploaded, host, payload)
-        for old in [k for k in self.entries if k not in self.held][:max(0, len(self.entries) - self.cap)]:
-            del self.entries[old]
-        return on_device, payload
-
-
-def _flip_operand(name, flip, n, dev):
-    """The per-item ``flip`` of a loader operator as the kernel reads it: None, or a contiguous int32 tensor of ``n`` entries on
-    ``dev`` (a host sequence of bools is uploaded from pinned memory)."""
-    if flip is None:
-        return None
-    if not torch.is_tensor(flip):
-        flip = torch.tensor([int(bool(v)) for v in flip], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-    if flip.dtype != torch.int32 or flip.numel() != n or flip.device != dev:
-        raise RuntimeError("%s: flip must be an int32 tensor of %d entries on %s" % (name, n, dev))
-    return _c(flip)
-
-
-# ----------------------------------------------------------------------------------------------------------------- K31
-PIL_FILTERS = {"lanczos": (N.PIL_LANCZOS, 3.0), "bilinear": (N.PIL_BILINEAR, 1.0)}      # name -> (PIL's number, support)
-PIL_PRECISION_BITS = 22
-PIL_DESC_CACHE = 64         # descriptor sets kept per process (a few hundred bytes each); the tables themselves are never repeated
-PilLevel = namedtuple("PilLevel", ["u8", "f32"])
-_pil_axis_cache = {}
-# (device, sizes, out, filter) -> descriptors on the device
-_pil_device_cache = _UploadCache(PIL_DESC_CACHE, "pil_resize: the first call with these source sizes uploads their descriptors; "
-                                                 "make it once before capturing a graph")
-_pil_graph_keys = _pil_device_cache.held
-
-
-def _pil_filter(filter):
-    try:
-        return PIL_FILTERS[str(filter).lower()]
-    except KeyError:
-        raise RuntimeError("pil_resize: filter must be one of %s; got %r" % (sorted(PIL_FILTERS), filter))
-
-
-def _pil_weight(x, support):
-    """Pillow's filter functions (Resample.c: bilinear_filter; lanczos_filter = sinc(x) sinc(x / 3) on [-3, 3)) on Python
-    floats: ``math.sin`` is the C library's, as Pillow's is."""
-    import math
-    if support == 1.0:
-        x = -x if x < 0.0 else x
-        return 1.0 - x if x < 1.0 else 0.0
-    if not -3.0 <= x < 3.0:
-        return 0.0
-
-    def sinc(v):
-        if v == 0.0:
-            return 1.0
-        v = v * math.pi
-        return math.sin(v) / v
-    return sinc(x) * sinc(x / 3)
-
-
-def pil_axis_table(in_size, out_size, filter="lanczos"):
-    """Host: Pillow's coefficients of one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc) for ``in_size`` ->
-    ``out_size``: (xmin int32 [out], count int32 [out], k int32 [out, ksize]).  float64 in Pillow's order -- the taps
-    ``filter((x + xmin - center + 0.5) * (1 / filterscale))`` summed by index, each divided by the sum -- then integers with 22
-    fraction bits, rounded half away from zero.  Equal sizes give the pass Pillow skips as the table (x, 1, 2^22).  Cached."""
-    in_size, out_size = int(in_size), int(out_size)
-    number, support0 = _pil_filter(filter)
-    if not (0 < in_size < (1 << 20) and 0 < out_size < (1 << 20)):
-        raise RuntimeError("pil_axis_table: sizes must be in [1, 2^20); got %d -> %d" % (in_size, out_size))
-    key = (in_size, out_size, number)
-    hit = _pil_axis_cache.get(key)
-    if hit is not None:
-        return hit
-    if in_size == out_size:
-        tab = (np.arange(out_size, dtype=np.int32), np.ones(out_size, dtype=np.int32),
-               np.full((out_size, 1), 1 << PIL_PRECISION_BITS, dtype=np.int32))
-    else:
-        import math
-        scale = in_size / out_size
-        filterscale = max(scale, 1.0)
-        support = support0 * filterscale
-        ksize = int(math.ceil(support)) * 2 + 1
-        ss = 1.0 / filterscale
-        xmins, counts = np.zeros(out_size, dtype=np.int32), np.zeros(out_size, dtype=np.int32)
-        k = np.zeros((out_size, ksize), dtype=np.int32)
-        one = float(1 << PIL_PRECISION_BITS)
-        for xx in range(out_size):
-            center = (xx + 0.5) * scale
-            xmin = max(int(center - support + 0.5), 0)
-            xmax = min(int(center + support + 0.5), in_size) - xmin
-            w = [_pil_weight((x + xmin - center + 0.5) * ss, support0) for x in range(xmax)]
-            ww = 0.0
-            for v in w:
-                ww += v
-            if ww != 0.0:
-                w = [v / ww for v in w]
-            xmins[xx], counts[xx] = xmin, xmax
-            k[xx, :xmax] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
-        tab = (xmins, counts, k)
-    for a in tab:
-        a.setflags(write=False)
-    _pil_axis_cache[key] = tab
-    return tab
-
-
-def _pil_pass_host(a, table, sums=None):
-    """One pass of Pillow's 8-bit resample along the last axis of uint8 ``a``: clip((2^21 + sum(p k)) >> 22, 0, 255) in int32.
-    ``sums`` (a list) receives the sums before the shift and the clip."""
-    xmin, count, k = table
-    idx = np.minimum(xmin[:, None] + np.arange(k.shape[1])[None, :], a.shape[-1] - 1)      # taps past ``count`` weigh 0
-    acc = (a[..., idx].astype(np.int32) * k).sum(-1, dtype=np.int32) + np.int32(1 << (PIL_PRECISION_BITS - 1))
-    if sums is not None:
-        sums.append(acc)
-    return np.clip(acc >> PIL_PRECISION_BITS, 0, 255).astype(np.uint8)
-
-
-def pil_quantize_host(x):
-    """torchvision's ``ToPILImage`` on a float tensor: ``pic.mul(255).byte()``, a truncation in fp32."""
-    return (np.asarray(x, dtype=np.float32) * np.float32(255.0)).astype(np.uint8)
-
-
-def pil_resize_host(img, out_size, filter="lanczos", flip=False, sums=None):
-    """Host twin of K31 in numpy: ``PIL.Image.fromarray(img).resize((out_w, out_h), filter)`` of uint8 ``img`` [..., H, W]
-    (planar: leading axes are channels or a batch), bit-equal to Pillow's.  ``flip``: transpose(FLIP_LEFT_RIGHT) first.  The
-    horizontal pass runs first into an 8-bit intermediate; a pass whose size does not change is skipped."""
-    img = np.asarray(img)
-    if img.dtype != np.uint8 or img.ndim < 2:
-        raise RuntimeError("pil_resize_host: need a uint8 array [..., H, W]; got %s %s" % (img.dtype, img.shape))
-    oh, ow = (int(v) for v in out_size)
-    if flip:
-        img = img[..., ::-1]
-    H, W = img.shape[-2:]
-    if W != ow:
-        img = _pil_pass_host(img, pil_axis_table(W, ow, filter), sums)
-    if H != oh:
-        img = np.swapaxes(_pil_pass_host(np.swapaxes(img, -1, -2), pil_axis_table(H, oh, filter), sums), -1, -2)
-    return np.ascontiguousarray(img)
-
-
-class _PilArena(object):
-    """The axis tables of one device: one int32 tensor that holds every distinct (in, out, filter) table once, at a word offset
-    that never changes.  KITTI raw has about five frame sizes, so the arena stops growing after the first batches; when a new
-    table arrives the whole arena is uploaded again (pinned, asynchronous) and the upload is waited for once, so that any stream
-    may read it afterwards."""
-
-    def __init__(self, device):
-        self.device, self.entries, self.words, self.tables = device, {}, [], None
-        self.tile_rows = {}
-
-    def place(self, n_in, n_out, number, filter):
-        """(word offset, ksize) of the table; ``self.tables`` is stale until ``sync`` when this added one."""
-        key = (n_in, n_out, number)
-        if key not in self.entries:
-            xmin, count, k = pil_axis_table(n_in, n_out, filter)
-            flat = np.concatenate([xmin, count, np.ascontiguousarray(k.T).reshape(-1)])
-            want = N.lib().dmh_pil_resample_tables_size(n_in, n_out, number)
-            if want != flat.size:
-                raise RuntimeError("pil_resize: the table of %d -> %d has %d words, the library expects %d" % (n_in, n_out, flat.size, want))
-            self.entries[key] = (sum(w.size for w in self.words), k.shape[1])
-            self.words.append(flat)
-            self.tables = None
-        return self.entries[key]
-
-    def rows(self, h, oh, filter, number):
-        """The most source rows one tile of PIL_TILE_ROWS output rows needs on the vertical axis h -> oh."""
-        key = (h, oh, number)
-        if key not in self.tile_rows:
-            tile = N.PIL_TILE_ROWS
-            ymin, count, _ = pil_axis_table(h, oh, filter)
-            last_i = np.minimum(np.arange(tile - 1, oh + tile - 1, tile), oh - 1)
-            self.tile_rows[key] = int((ymin[last_i] + count[last_i] - ymin[::tile]).max())
-        return self.tile_rows[key]
-
-    def sync(self):
-        if self.tables is None:
-            host = torch.from_numpy(np.concatenate(self.words)).pin_memory()
-            self.tables = host.to(self.device, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(self.device))
-            done.synchronize()          # once per new table: later calls, on any stream, read a finished upload
-        return self.tables
-
-
-_pil_arenas = {}
-
-
-def _pil_tables_device(device, sizes, oh, ow, number, filter):
-    """(tables int32 [words], desc int32 [N, 8], lds_rows) on ``device`` for a batch whose images have the source sizes
-    ``sizes`` (a tuple of (h, w)).  The tables live once per distinct (in, out, filter) in the device's arena; what depends on
-    the batch is the descriptor set alone (32 bytes per image), kept in ``_pil_device_cache``: a repeated batch shape -- a
-    captured graph's, a pyramid's coarser levels -- launches with the same device buffer and no copy."""
-    arena = _pil_arenas.get(str(device))
-    if arena is None:
-        arena = _pil_arenas[str(device)] = _PilArena(device)
-
-    def make():
-        desc, lds_rows = np.zeros((len(sizes), 8), dtype=np.int32), 1
-        for i, (h, w) in enumerate(sizes):
-            (ho, hk), (vo, vk) = arena.place(w, ow, number, filter), arena.place(h, oh, number, filter)
-            desc[i, :6] = (h, w, ho, hk, vo, vk)
-            lds_rows = max(lds_rows, arena.rows(h, oh, filter, number))
-        if lds_rows * ow > 65536:
-            raise RuntimeError("pil_resize: %d source rows of %d output columns per tile exceed the 64 KiB LDS tile; resize in two "
-                               "steps" % (lds_rows, ow))
-        return [torch.from_numpy(desc)], lds_rows
-    (desc_d,), lds_rows = _pil_device_cache.get((str(device), sizes, oh, ow, number), device, make)
-    return arena.sync(), desc_d, lds_rows
-
-
-def _pil_sizes(sizes, n, H, W):
-    if sizes is None:
-        return ((H, W),) * n
-    sizes = tuple((int(h), int(w)) for h, w in (sizes.tolist() if hasattr(sizes, "tolist") else sizes))
-    if len(sizes) != n or not all(0 < h <= H and 0 < w <= W for h, w in sizes):
-        raise RuntimeError("pil_resize: sizes must be %d pairs (h, w) within the buffer's %d x %d; got %s" % (n, H, W, sizes))
-    return sizes
-
-
-def pil_resize(src, out_size, filter="lanczos", flip=None, sizes=None, want_float=True, layout=None, want_u8=True):
-    """K31: ``PIL.Image.resize((out_w, out_h), filter)`` of a batch of 8-bit images, bit for bit, in one launch.
-
-    src      uint8 [N, H, W, C] (``layout="hwc"``, the default for uint8: decoded files), uint8 [N, C, H, W]
-             (``layout="chw"``: a previous level), or float32 [N, C, H, W] in [0, 1], quantised on read as ToPILImage does.
-    sizes    per image (h, w) <= (H, W): the image lies in the top-left corner of its slot (host values: they choose the tables).
-    flip     per image, a device int32 [N] (or a host sequence of bools): != 0 resizes transpose(FLIP_LEFT_RIGHT) of the image.
-    Returns  PilLevel(u8 uint8 [N, C, out_h, out_w] or None, f32 = u8.float() / 255 or None).
-
-    CPU tensors run the numpy restatement of the same integers (``pil_resize_host``)."""
-    number, _ = _pil_filter(filter)
-    oh, ow = (int(v) for v in out_size)
-    if oh < 1 or ow < 1:
-        raise RuntimeError("pil_resize: out_size must be positive; got %s" % (tuple(out_size),))
-    if src.dim() != 4 or src.dtype not in (torch.uint8, torch.float32):
-        raise RuntimeError("pil_resize: src must be uint8 or float32 with 4 dimensions; got %s %s" % (src.dtype, tuple(src.shape)))
-    if not (want_float or want_u8):
-        raise RuntimeError("pil_resize: nothing to return (want_float and want_u8 are both off)")
-    layout = layout or ("hwc" if src.dtype == torch.uint8 else "chw")
-    if layout not in ("hwc", "chw") or (src.dtype == torch.float32 and layout != "chw"):
-        raise RuntimeError("pil_resize: layout must be 'hwc' or 'chw' (float32 sources are 'chw'); got %r" % (layout,))
-    n, (H, W, C_) = int(src.shape[0]), ((int(v) for v in src.shape[1:]) if layout == "hwc" else (int(src.shape[2]), int(src.shape[3]), int(src.shape[1])))
-    sizes = _pil_sizes(sizes, n, H, W)
-    if src.device.type != "cuda":
-        planar = src.permute(0, 3, 1, 2) if layout == "hwc" else src
-        planar = planar.numpy() if src.dtype == torch.uint8 else pil_quantize_host(planar.numpy())
-        flips = [False] * n if flip is None else [bool(v) for v in (flip.tolist() if hasattr(flip, "tolist") else flip)]
-        if len(flips) != n:
-            raise RuntimeError("pil_resize: flip must have one entry per image")
-        u8 = torch.from_numpy(np.stack([pil_resize_host(planar[i, :, :h, :w], (oh, ow), filter, flips[i])
-                                        for i, (h, w) in enumerate(sizes)]))
-        return PilLevel(u8 if want_u8 else None, u8.float().div(255) if want_float else None)
-    src = _c(src)
-    dev = src.device
-    flip = _flip_operand("pil_resize", flip, n, dev)
-    tables, desc, lds_rows = _pil_tables_device(dev, sizes, oh, ow, number, filter)
-    u8 = torch.empty((n, C_, oh, ow), device=dev, dtype=torch.uint8) if want_u8 else None
-    f32 = torch.empty((n, C_, oh, ow), device=dev, dtype=torch.float32) if want_float else None
-    strides = (H * W * C_, 1, W * C_, C_) if layout == "hwc" else (C_ * H * W, H * W, W, 1)
-    N.check(_timed("pil_resample", lambda: N.lib().dmh_pil_resample(
-        N.ptr(src), int(src.dtype == torch.float32), *strides, H, W, N.ptr(tables), int(tables.numel()), N.ptr(desc),
-        N.ptr(flip), n, C_, oh, ow, lds_rows, N.ptr(u8), N.ptr(f32), N.stream()),
-        src.numel() * src.element_size() + n * C_ * oh * ow * (int(want_u8) + 4 * int(want_float))))
-    return PilLevel(u8, f32)
-
-
-def pil_pyramid(src, height, width, num_scales=4, filter="lanczos", flip=None, sizes=None, want_float=True, layout=None):
-    """The loader's image pyramid (MD2/datasets/mono_dataset.py:100-104,119-144): level 0 is ``src`` resized to height x width,
-    level i the 8-bit level i - 1 resized to (height // 2^i) x (width // 2^i) -- one launch of K31 per level.  ``flip`` applies to
-    level 0 (the reference flips the loaded image).  Returns ``num_scales`` PilLevel(u8, f32)."""
-    levels = []
-    for i in range(int(num_scales)):
-        s = 2 ** i
-        if height // s < 1 or width // s < 1:
-            raise RuntimeError("pil_pyramid: level %d of %d x %d is empty" % (i, height, width))
-        if i == 0:
-            levels.append(pil_resize(src, (height, width), filter, flip, sizes, want_float, layout))
-        else:
-            levels.append(pil_resize(levels[-1].u8, (height // s, width // s), filter, None, None, want_float, "chw"))
-    return levels
-
-
-# ---------------------------------------------------------------------------------------------------------------- K32
-VELO_EMPTY, VELO_DESC_CACHE = 0xFFFFFFFF, 16
-_velo_desc_cache = _UploadCache(VELO_DESC_CACHE, "velo_depth_map: the first call with these shapes uploads their descriptors; make "
-                                                 "it once before capturing a graph")     # (device, shapes) -> descriptors
-
-
-def nearest_index(n_in, n_out):
-    """Source index of every output index of K32's nearest resize: ((2 o + 1) n_in) // (2 n_out), the exact-arithmetic value of
-    the pixel-centre mapping round((o + 0.5) n_in / n_out - 0.5); the identity when the sizes agree."""
-    o = np.arange(int(n_out), dtype=np.int64)
-    return ((2 * o + 1) * int(n_in)) // (2 * int(n_out))
-
-
-def _velo_shapes(shapes, n):
-    shapes = tuple((int(h), int(w)) for h, w in (shapes.tolist() if hasattr(shapes, "tolist") else shapes))
-    if len(shapes) != n or not all(h >= 1 and w >= 2 for h, w in shapes):
-        raise RuntimeError("velo_depth_map: shapes must be %d pairs (H, W) with H >= 1 and W >= 2; got %s" % (n, shapes))
-    return shapes
-
-
-def _velo_frame_host(pts, P, H, W, vel_depth):
-    """One frame of K32 in numpy -> float32 [H, W]: the kernel's arithmetic in the kernel's order (csrc/velo_depth.hip)."""
-    idx = np.nonzero(pts[:, 0] >= 0)[0]                     # a NaN fails the test
-    x, y, z = (pts[idx, c].astype(np.float64) for c in range(3))
-    with np.errstate(all="ignore"):
-        q = [((P[r, 0] * x + P[r, 1] * y) + P[r, 2] * z) + P[r, 3] for r in range(3)]
-        u, v = np.rint(q[0] / q[2]) - 1.0, np.rint(q[1] / q[2]) - 1.0
-        keep = (u >= 0) & (v >= 0) & (u < W) & (v < H)      # NaN and inf fall out
-        d = (x if vel_depth else q[2])[keep]
-        val = np.where(d > 0, d, 0.0).astype(np.float32)    # float32(max(d, 0)); rounding and the clamp are monotone
-    idx, ui, vi = idx[keep], u[keep].astype(np.int64), v[keep].astype(np.int64)
-    if idx.size == 0:
-        return np.zeros((H, W), dtype=np.float32)
-    bits = val.view(np.uint32)                             # non-negative floats order as their bits do
-    cells = np.full(H * W, VELO_EMPTY, dtype=np.uint32)
-    np.minimum.at(cells, vi * W + ui, bits)
-    out = np.where(cells == VELO_EMPTY, np.uint32(0), cells).reshape(H, W)
-    if H > 1:
-        # the reference's sub2ind gives A = (y, W - 1) and B = (y + 1, 0) one key: where both hold points, the one that holds the
-        # pair's earliest point gets the minimum over both, the other keeps its last point's value
-        first = np.full((H, 2), np.iinfo(np.int64).max, dtype=np.int64)
-        last = np.full((H, 2), -1, dtype=np.int64)
-        for side, col in ((0, 0), (1, W - 1)):
-            on = ui == col
-            np.minimum.at(first[:, side], vi[on], idx[on])
-            np.maximum.at(last[:, side], vi[on], idx[on])
-        cells = cells.reshape(H, W)
-        a, b = cells[:-1, W - 1], cells[1:, 0]
-        both = (a != VELO_EMPTY) & (b != VELO_EMPTY)
-        a_first = first[:-1, 1] < first[1:, 0]
-        low = np.minimum(a, b)
-        pos = np.full(pts.shape[0], -1, dtype=np.int64)
-        pos[idx] = np.arange(idx.size)
-        last_a, last_b = bits[pos[np.maximum(last[:-1, 1], 0)]], bits[pos[np.maximum(last[1:, 0], 0)]]
-        out[:-1, W - 1] = np.where(both, np.where(a_first, low, last_a), out[:-1, W - 1])
-        out[1:, 0] = np.where(both, np.where(a_first, last_b, low), out[1:, 0])
-    return out.view(np.float32)
-
-
-def velo_depth_map_host(points, offsets, proj, shapes, vel_depth=False, out_size=None, flip=None):
-    """K32 in numpy, the definition the kernel is held to (and the path CPU tensors take): vectorised, no loop per duplicate.
-    points float32 [npts, 4], offsets [n + 1], proj float64 [n, 3, 4] or [n, 12], shapes n pairs (H, W).  Returns float32
-    [n, out_h, out_w] with ``out_size``, else the list of the n maps at their own sizes."""
-    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
-    offsets = [int(v) for v in np.asarray(offsets).reshape(-1)]
-    n = len(offsets) - 1
-    proj = np.asarray(proj, dtype=np.float64).reshape(n, 3, 4)
-    shapes = _velo_shapes(shapes, n)
-    flips = [False] * n if flip is None else [bool(v) for v in np.asarray(flip).reshape(-1)]
-    if len(flips) != n:
-        raise RuntimeError("velo_depth_map: flip must have one entry per frame")
-    if offsets[0] < 0 or offsets[-1] > points.shape[0] or any(a > b for a, b in zip(offsets[:-1], offsets[1:])):
-        raise RuntimeError("velo_depth_map: offsets must ascend within the %d points; got %s" % (points.shape[0], offsets))
-    maps = []
-    for f, (H, W) in enumerate(shapes):
-        m = _velo_frame_host(points[offsets[f]:offsets[f + 1]], proj[f], H, W, bool(vel_depth))
-        if out_size is not None:
-            m = m[nearest_index(H, out_size[0])][:, nearest_index(W, out_size[1])]
-        maps.append(np.ascontiguousarray(m[:, ::-1] if flips[f] else m))
-    return np.stack(maps) if out_size is not None else maps
-
-
-def _velo_desc_device(device, shapes):
-    def make():
-        cells = np.cumsum([0] + [h * w for h, w in shapes])
-        rows = np.cumsum([0] + [h for h, _ in shapes])
-        return [torch.tensor([[h, w, int(cells[i]), int(rows[i])] for i, (h, w) in enumerate(shapes)], dtype=torch.int32)], None
-    return _velo_desc_cache.get((str(device), shapes), device, make)[0][0]
-
-
-def velo_depth_map(points, offsets, proj, shapes, vel_depth=False, out_size=None, flip=None):
-    """K32: the sparse depth maps of a batch of velodyne scans (MD2/kitti_utils.py:46-98, generate_depth_map, float32-equal),
-    with the loader's nearest resize and flip (MD2/datasets/kitti_dataset.py:70-85).
-
-    points   float32 [npts, 4], the frames' points packed in file order; offsets int32 [n + 1] on the same device.
-    proj     float64 [n, 3, 4] (or [n, 12]): P_velo2im of each frame (datasets.kitti_velo.velo_projection).
-    shapes   n pairs (H, W): each frame's image size.  Host values: they size the workspace and the output.
-    flip     per frame, an int32 tensor [n] on the device (or a host sequence of bools): != 0 mirrors the columns.
-    Returns  float32 [n, out_h, out_w] with ``out_size``; without it (flat float32 [sum H W], cell offsets as a list of n + 1
-             ints): frame f is flat[off[f]:off[f + 1]].view(H, W).
-
-    CPU tensors run ``velo_depth_map_host``, the numpy restatement the kernel is bit-equal to."""
-    if not torch.is_tensor(points) or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4:
-        raise RuntimeError("velo_depth_map: points must be a float32 tensor [npts, 4]; got %s %s"
-                           % (getattr(points, "dtype", type(points)), tuple(getattr(points, "shape", ()))))
-    _eigen_i32(offsets, "offsets")
-    n = offsets.numel() - 1
-    if offsets.dim() != 1 or n < 1:
-        raise RuntimeError("velo_depth_map: offsets must hold n + 1 >= 2 entries; got %s" % (tuple(offsets.shape),))
-    if not torch.is_tensor(proj) or proj.dtype != torch.float64 or proj.numel() != 12 * n:
-        raise RuntimeError("velo_depth_map: proj must be a float64 tensor of %d x 12 entries; got %s %s"
-                           % (n, getattr(proj, "dtype", type(proj)), tuple(getattr(proj, "shape", ()))))
-    shapes = _velo_shapes(shapes, n)
-    if out_size is not None:
-        out_size = tuple(int(v) for v in out_size)
-        if len(out_size) != 2 or out_size[0] < 1 or out_size[1] < 1:
-            raise RuntimeError("velo_depth_map: out_size must be a positive (h, w); got %s" % (out_size,))
-    cell_off = [int(v) for v in np.cumsum([0] + [h * w for h, w in shapes])]
-    dev = points.device
-    if offsets.device != dev or proj.device != dev:
-        raise RuntimeError("velo_depth_map: points, offsets and proj must share a device")
-    if dev.type != "cuda":
-        res = velo_depth_map_host(points.numpy(), offsets.numpy(), proj.numpy(), shapes, vel_depth, out_size,
-                                  None if flip is None else (flip.tolist() if hasattr(flip, "tolist") else flip))
-        if out_size is not None:
-            return torch.from_numpy(res)
-        return torch.from_numpy(np.concatenate([m.reshape(-1) for m in res])), cell_off
-    flip = _flip_operand("velo_depth_map", flip, n, dev)
-    lib = N.lib()
-    total_cells, total_rows = cell_off[-1], sum(h for h, _ in shapes)
-    words = lib.dmh_velo_depth_ws_size(total_cells, total_rows)
-    if words < 0:
-        raise RuntimeError("velo_depth_map: %d cells and %d rows do not fit a 2^31-word workspace" % (total_cells, total_rows))
-    desc = _velo_desc_device(dev, shapes)
-    ws = torch.empty(words, device=dev, dtype=torch.int32)
-    out = torch.empty((n,) + out_size if out_size is not None else (total_cells,), device=dev, dtype=torch.float32)
-    points, proj = _c(points), _c(proj)
-    oh, ow = out_size if out_size is not None else (0, 0)
-    N.check(_timed("velo_depth_map", lambda: lib.dmh_velo_depth_map(
-        N.ptr(points) if points.numel() else None, int(points.shape[0]), N.ptr(_c(offsets)), N.ptr_f64(proj), N.ptr(desc),
-        N.ptr(flip), n, int(bool(vel_depth)), total_cells, total_rows, oh, ow, N.ptr(ws), N.ptr(out),
-        N.stream()), points.numel() * 4 + 8 * words + out.numel() * 4))
-    return out if out_size is not None else (out, cell_off)
-
-
-# ---------------------------------------------------------------------------------------------------------------- K33
-JITTER_MAX_TENSORS = 8                  # DMH_JITTER_MAX_TENSORS
-JITTER_MAX_PIXELS = (2 ** 32 - 1) // 255  # 255 H W must fit the 32-bit sum of L
-
-
-def _jitter_L(img):
-    """Pillow's ``convert("L")`` of uint8 [3, H, W] -> int32 [H, W]."""
-    r, g, b = (img[c].astype(np.int32) for c in range(3))
-    return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
-
-
-def _jitter_blend(deg, img, f):
-    """``Image.blend(degenerate, image, f)`` per channel: float32, the product and the sum rounded separately; truncated to a byte
-    for 0 <= f <= 1, clipped outside."""
-    f = np.float32(f)
-    d = np.asarray(deg).astype(np.float32)
-    t = d + f * (img.astype(np.float32) - d)
-    if np.float32(0) <= f <= np.float32(1):
-        return t.astype(np.int32).astype(np.uint8)
-    with np.errstate(invalid="ignore"):
-        return np.where(t <= 0, 0, np.where(t >= 255, 255, t.astype(np.int32))).astype(np.uint8)
-
-
-def _jitter_hue(img, shift):
-    """``convert("HSV")``, the shift added to the H byte modulo 256, ``convert("RGB")`` (Pillow's Convert.c rgb2hsv / hsv2rgb)."""
-    r, g, b = (img[c].astype(np.int32) for c in range(3))
-    mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
-    flat = mx == mn
-    cr = np.where(flat, 1, mx - mn).astype(np.float32)
-    s = cr / np.where(flat, 1, mx).astype(np.float32)
-    rc, gc, bc = ((mx - c).astype(np.float32) / cr for c in (r, g, b))
-    rc64, gc64, bc64 = (c.astype(np.float64) for c in (rc, gc, bc))
-    h = np.where(r == mx, bc64 - gc64, np.where(g == mx, 2.0 + rc64 - bc64, 4.0 + gc64 - rc64)).astype(np.float32)
-    h = np.fmod(h.astype(np.float64) / 6.0 + 1.0, 1.0).astype(np.float32)
-    H = np.where(flat, 0, np.clip((h.astype(np.float64) * 255.0).astype(np.int32), 0, 255))
-    S = np.where(flat, 0, np.clip((s.astype(np.float64) * 255.0).astype(np.int32), 0, 255))
-    V = mx
-    H = (H + int(shift)) & 255
-    fs = S / 255.0
-    x = H * 6.0 / 255.0
-    i = np.floor(x)
-    fr = x - i
-
-    def byte(z):        # C's round (half away from zero; z >= 0 here), then CLIP8
-        return np.clip(np.floor(z + 0.5), 0, 255).astype(np.int32)
-    p, q, t = byte(V * (1.0 - fs)), byte(V * (1.0 - fs * fr)), byte(V * (1.0 - fs * (1.0 - fr)))
-    k = i.astype(np.int32) % 6
-    grey = S == 0
-    out = [np.where(grey, V, np.choose(k, table)) for table in ((V, q, p, p, t, V), (t, V, V, q, p, p), (p, p, t, V, V, q))]
-    return np.stack(out).astype(np.uint8)
-
-
-def pil_color_jitter_host(images, records, sums=None):
-    """Host twin of K33 in numpy, bit-equal to Pillow: torchvision 0.8.2's ColorJitter on 8-bit PIL images.  ``images``: uint8
-    arrays [B, 3, H, W]; ``records``: int32 [B, 8] (color_jitter.pil_records).  Every operation ends in a byte: brightness =
-    blend(0, img, f), saturation = blend(L(img), img, f), contrast = blend(m, img, f) with m = int(mean of L over this image as the
-    operations before left it + 0.5), hue = the HSV round trip with the shifted H byte.  Returns the uint8 results; ``sums`` (a
-    list) receives the integer sum of L of every image that took a contrast step."""
-    records = np.asarray(records, dtype=np.int32).reshape(-1, 8)
-    out = []
-    for img in images:
-        img = np.asarray(img)
-        if img.dtype != np.uint8 or img.ndim != 4 or img.shape[1] != 3 or img.shape[0] != records.shape[0]:
-            raise RuntimeError("pil_color_jitter_host: need uint8 arrays [%d, 3, H, W]; got %s %s" % (records.shape[0], img.dtype, img.shape))
-        res = np.empty_like(img)
-        for i, rec in enumerate(records):
-            x = img[i]
-            factors = rec[2:5].view(np.float32)
-            seen_contrast = False
-            for k in range(min(max(int(rec[0]), 0), 4)):
-                op = (int(rec[1]) >> (8 * k)) & 255
-                if op == 0:
-                    x = _jitter_blend(0, x, factors[0])
-                elif op == 1:
-                    L = _jitter_L(x)
-                    S = int(L.sum(dtype=np.int64))
-                    if sums is not None and not seen_contrast:
-                        sums.append(S)
-                    seen_contrast = True
-                    x = _jitter_blend(int(S / float(L.size) + 0.5), x, factors[1])
-                elif op == 2:
-                    x = _jitter_blend(_jitter_L(x)[None], x, factors[2])
-                elif op == 3:
-                    x = _jitter_hue(x, int(rec[5]) & 255)
-            res[i] = x
-        out.append(res)
-    return out
-
-
-def pil_color_jitter(images, params, want_u8=False):
-    """K33: torchvision 0.8.2's ``ColorJitter`` on 8-bit PIL images (MD2/datasets/mono_dataset.py:344-348, :133, :144), Pillow's
-    bytes, for a whole batch and all its keys in two launches (one when no item has a contrast step).
-
-    images   a list of at most 8 uint8 tensors [B, 3, H, W] on one device (K31's level-0 ``u8``): item i of every tensor takes
-             transform i; every image has its own contrast mean.
-    params   a list of B ``color_jitter.JitterParams`` or None (None: the item is only converted), or the prepared int32 record
-             [B, 8] on the images' device (``color_jitter.pil_records``; a captured graph reads it at every replay).
-    Returns  a list of PilLevel(u8 or None, f32 = u8.float() / 255), one per tensor.
-
-    CPU tensors run ``pil_color_jitter_host``, the numpy restatement the kernel is bit-equal to."""
-    from . import color_jitter
-    from .my_utils import to_device_async
-    images = list(images)
-    if not 1 <= len(images) <= JITTER_MAX_TENSORS:
-        raise RuntimeError("pil_color_jitter: one call takes 1 .. %d tensors; got %d" % (JITTER_MAX_TENSORS, len(images)))
-    first = images[0]
-    for t in images:
-        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[1] != 3 or t.shape != first.shape or t.device != first.device:
-            raise RuntimeError("pil_color_jitter: images must be uint8 tensors [B, 3, H, W] of one shape on one device; got %s %s"
-                               % (getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    B, _, H, W = (int(v) for v in first.shape)
-    if B < 1 or H < 1 or W < 1 or H * W > JITTER_MAX_PIXELS:
-        raise RuntimeError("pil_color_jitter: need a non-empty batch of images of at most %d pixels (255 H W must fit 32 bits); "
-                           "got %d x %d x %d" % (JITTER_MAX_PIXELS, B, H, W))
-    dev = first.device
-    if torch.is_tensor(params):
-        if params.dtype != torch.int32 or params.numel() != 8 * B or params.device != dev:
-            raise RuntimeError("pil_color_jitter: a prepared record is an int32 tensor [%d, 8] on %s" % (B, dev))
-        rec, with_contrast = params, True
-    else:
-        host = color_jitter.pil_records(params)
-        if host.shape[0] != B:
-            raise RuntimeError("pil_color_jitter: params must hold one entry per item (%d); got %d" % (B, host.shape[0]))
-        with_contrast = bool(color_jitter.records_have_contrast(host))
-        rec = host if dev.type != "cuda" else to_device_async(host, dev)
-    if dev.type != "cuda":
-        res = [torch.from_numpy(a) for a in pil_color_jitter_host([t.numpy() for t in images], rec.numpy() if torch.is_tensor(rec) else rec)]
-        return [PilLevel(u8 if want_u8 else None, u8.float().div(255)) for u8 in res]
-    images = [_c(t) for t in images]
-    rec = _c(rec)
-    f32 = [torch.empty((B, 3, H, W), device=dev, dtype=torch.float32) for _ in images]
-    u8 = [torch.empty((B, 3, H, W), device=dev, dtype=torch.uint8) for _ in images] if want_u8 else None
-    T = len(images)
-    words = N.lib().dmh_color_jitter_ws_size(T, B, H, W)
-    if words < 0:
-        raise RuntimeError("pil_color_jitter: %d tensors of %d x 3 x %d x %d are more than one call takes (T B <= 65535, "
-                           "B 3 H W < 2^31)" % (T, B, H, W))
-    ws = torch.empty(words, device=dev, dtype=torch.int32) if with_contrast else None
-    N.check(_timed("color_jitter", lambda: N.lib().dmh_color_jitter(
-        N.ptr_array(images, JITTER_MAX_TENSORS), N.ptr_array(f32, JITTER_MAX_TENSORS),
-        N.ptr_array(u8, JITTER_MAX_TENSORS) if want_u8 else None, T, B, H, W, N.ptr(rec), int(with_contrast), N.ptr(ws), N.stream()),
-        T * B * H * W * 3 * (1 + 4 + int(want_u8)) + (T * B * H * W * 3 if with_contrast else 0)))
-    return [PilLevel(u8[i] if want_u8 else None, f32[i]) for i in range(T)]
-
-
-# ---------------------------------------------------------------------------------------------------------------- K34
-HINT_MAX_CANDIDATES = 16
-HINT_TABLE_CACHE = 8
-_hint_table_cache = _UploadCache(HINT_TABLE_CACHE, "depth_hint_prepare: the first call with these sizes uploads their index tables; "
-                                                   "make it once before capturing a graph")     # (device, Hs, Ws, H, W) -> (ytab, xtab)
-
-
-def hint_candidate_depths(cand, K):
-    """depth-hints/precompute_depth_hints.py:142,151 for a batch: StereoSGBM's int16 output [B, N, H, W] (disparity x 16, -16 where
-    nothing matched) -> float32 depths, fx 0.1 / (disp + 1e-7) * (disp > 0) with fx = K[b, 0, 0], as torch computes it on the CPU."""
-    disps = torch.from_numpy(cand.cpu().numpy() / 16).float()
-    fx = K.detach().cpu().float()[:, 0, 0].view(-1, 1, 1, 1)
-    return fx * 0.1 / (disps + 1e-7) * (disps > 0).float()
-
-
-def _hint_check(base, lookup, cand, K, inv_K, T):
-    if not (torch.is_tensor(base) and base.dtype == torch.uint8 and base.dim() == 4 and base.shape[1] == 3):
-        raise RuntimeError("depth_hint_fuse: base must be a uint8 tensor [B, 3, H, W]; got %s %s"
-                           % (getattr(base, "dtype", type(base)), tuple(getattr(base, "shape", ()))))
-    B, _, H, W = (int(v) for v in base.shape)
-    if not (torch.is_tensor(lookup) and lookup.dtype == torch.uint8 and lookup.shape == base.shape):
-        raise RuntimeError("depth_hint_fuse: lookup must be a uint8 tensor of base's shape %s; got %s %s"
-                           % (tuple(base.shape), getattr(lookup, "dtype", type(lookup)), tuple(getattr(lookup, "shape", ()))))
-    if not (torch.is_tensor(cand) and cand.dtype in (torch.int16, torch.float32) and cand.dim() == 4 and cand.shape[0] == B
-            and tuple(cand.shape[2:]) == (H, W)):
-        raise RuntimeError("depth_hint_fuse: cand must be int16 (disparity x 16) or float32 (depths) [%d, N, %d, %d]; got %s %s"
-                           % (B, H, W, getattr(cand, "dtype", type(cand)), tuple(getattr(cand, "shape", ()))))
-    n = int(cand.shape[1])
-    if not 1 <= n <= HINT_MAX_CANDIDATES:
-        raise RuntimeError("depth_hint_fuse: 1 <= N <= %d candidates; got %d" % (HINT_MAX_CANDIDATES, n))
-    if B < 1 or H < 2 or W < 2:
-        raise RuntimeError("depth_hint_fuse: need B >= 1 and H, W >= 2; got %d x %d x %d" % (B, H, W))
-    for name, m in (("K", K), ("inv_K", inv_K), ("T", T)):
-        if not (torch.is_tensor(m) and m.dtype == torch.float32 and tuple(m.shape) == (B, 4, 4)):
-            raise RuntimeError("depth_hint_fuse: %s must be a float32 tensor [%d, 4, 4]; got %s %s"
-                               % (name, B, getattr(m, "dtype", type(m)), tuple(getattr(m, "shape", ()))))
-    for t in (lookup, cand, K, inv_K, T):
-        if t.device != base.device:
-            raise RuntimeError("depth_hint_fuse: every operand must be on base's device %s; got %s" % (base.device, t.device))
-    return B, n, H, W
-
-
-def _hint_ssim(x, y):
-    """depth-hints/layers.py SSIM.forward."""
-    import torch.nn.functional as F
-    x, y = F.pad(x, (1, 1, 1, 1), mode="reflect"), F.pad(y, (1, 1, 1, 1), mode="reflect")
-    mu_x, mu_y = F.avg_pool2d(x, 3, 1), F.avg_pool2d(y, 3, 1)
-    sigma_x = F.avg_pool2d(x ** 2, 3, 1) - mu_x ** 2
-    sigma_y = F.avg_pool2d(y ** 2, 3, 1) - mu_y ** 2
-    sigma_xy = F.avg_pool2d(x * y, 3, 1) - mu_x * mu_y
-    C1, C2 = 0.01 ** 2, 0.03 ** 2
-    n = (2 * mu_x * mu_y + C1) * (2 * sigma_xy + C2)
-    d = (mu_x ** 2 + mu_y ** 2 + C1) * (sigma_x + sigma_y + C2)
-    return torch.clamp((1 - n / d) / 2, 0, 1)
-
-
-def depth_hint_fuse_host(base, lookup, cand, K, inv_K, T, want_losses=False, dtype=torch.float32):
-    """K34 in plain torch on the CPU, the definition the kernel is held to (and the path CPU tensors take): the lines
-    precompute_depth_hints.py:247-252 with BackprojectDepth, Project3D and SSIM of depth-hints/layers.py, item by item with the
-    candidates as the batch.  The candidate depths are float32 in every form (they are inputs: ``hint_candidate_depths`` for
-    int16); ``dtype=torch.float64`` computes everything after them in float64: the anchor.  Returns best_depth float32
-    [B, 1, H, W], with ``want_losses`` (best_depth, losses ``dtype`` [B, N, H, W])."""
-    import torch.nn.functional as F
-    B, n, H, W = _hint_check(base, lookup, cand, K, inv_K, T)
-    depths = hint_candidate_depths(cand, K) if cand.dtype == torch.int16 else cand.detach().cpu()
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=dtype), torch.arange(W, dtype=dtype), indexing="ij")
-    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W, dtype=dtype)], 0).unsqueeze(0)     # [1, 3, HW]
-    ones = torch.ones(n, 1, H * W, dtype=dtype)
-    best, losses = [], []
-    for b in range(B):
-        Kb, iKb, Tb = (m[b:b + 1].detach().cpu().to(dtype) for m in (K, inv_K, T))
-        d = depths[b].to(dtype)
-        cam = torch.matmul(iKb[:, :3, :3], pix)
-        cam = torch.cat([d.reshape(n, 1, -1) * cam, ones], 1)
-        P = torch.matmul(Kb, Tb)[:, :3, :]
-        cp = torch.matmul(P, cam)
-        pc = cp[:, :2, :] / (cp[:, 2, :].unsqueeze(1) + 1e-7)
-        pc = pc.view(n, 2, H, W).permute(0, 2, 3, 1)
-        pc[..., 0] /= W - 1
-        pc[..., 1] /= H - 1
-        pc = (pc - 0.5) * 2
-        img_l = (lookup[b:b + 1].cpu().to(dtype) / 255).expand(n, -1, -1, -1)
-        img_b = (base[b:b + 1].cpu().to(dtype) / 255).expand(n, -1, -1, -1)
-        sample = F.grid_sample(img_l, pc, padding_mode="border", align_corners=False)
-        l1 = torch.abs(img_b - sample).mean(1, True)
-        loss = 0.85 * _hint_ssim(sample, img_b).mean(1, True) + 0.15 * l1
-        index = torch.argmin(loss, dim=0)
-        best.append(torch.gather(depths[b].unsqueeze(1), 0, index.unsqueeze(0))[0])
-        losses.append(loss[:, 0])
-    best = torch.stack(best).float()
-    return (best, torch.stack(losses)) if want_losses else best
-
-
-def depth_hint_fuse(base, lookup, cand, K, inv_K, T, want_losses=False):
-    """K34: DepthHints' fused hint selection (depth-hints/precompute_depth_hints.py:247-252) for a batch of stereo pairs in one
-    launch: per candidate depth map the other view warped into the base view (grid_sample's defaults, border padding), SSIM + L1
-    against the base image, the lowest loss per pixel (the lowest index among equal float32 losses), its depth.
-
-    base, lookup  uint8 [B, 3, H, W] (``pil_resize(..., want_u8=True).u8``): the view the hint is for, and the other one.
-    cand          int16 [B, N, H, W]: StereoSGBM's raw output (disparity x 16, -16 = no match), converted as the reference does;
-                  or float32 [B, N, H, W]: depths.  1 <= N <= 16.
-    K, inv_K, T   float32 [B, 4, 4]; T[b, 0, 3] = -0.1 for a left base image, +0.1 for a right one.
-    Returns       best_depth float32 [B, 1, H, W]; with ``want_losses`` (best_depth, losses float32 [B, N, H, W]).
-
-    CPU tensors run ``depth_hint_fuse_host``."""
-    B, n, H, W = _hint_check(base, lookup, cand, K, inv_K, T)
-    if base.device.type != "cuda":
-        return depth_hint_fuse_host(base, lookup, cand, K, inv_K, T, want_losses)
-    if B * n * H * W >= 2 ** 31 or B > 65535:
-        raise RuntimeError("depth_hint_fuse: B N H W must stay below 2^31 and B below 65536; got %d x %d x %d x %d" % (B, n, H, W))
-    base, lookup, cand, K, inv_K, T = (_c(t) for t in (base, lookup, cand, K, inv_K, T))
-    best = torch.empty((B, 1, H, W), device=base.device, dtype=torch.float32)
-    losses = torch.empty((B, n, H, W), device=base.device, dtype=torch.float32) if want_losses else None
-    raw = cand.dtype == torch.int16
-    N.check(_timed("depth_hint_fuse", lambda: N.lib().dmh_depth_hint_fuse(
-        N.ptr(base), N.ptr(lookup), C.c_void_p(cand.data_ptr()), int(raw), N.ptr(K), N.ptr(inv_K), N.ptr(T), B, n, H, W, N.ptr(best),
-        N.ptr(losses), N.stream()), B * H * W * (6 + n * (2 if raw else 4) + 4 + (4 * n if want_losses else 0))))
-    return (best, losses) if want_losses else best
-
-
-def cv_nearest_index(n_src, n_dst):
-    """Source index of every destination index of OpenCV's INTER_NEAREST along one axis, as its source states it (resizeNN:
-    min(floor(dst * (double)src / dst_size), src - 1)); the identity when the sizes agree."""
-    scale = float(int(n_src)) / float(int(n_dst))
-    return np.minimum(np.floor(np.arange(int(n_dst), dtype=np.float64) * scale).astype(np.int64), int(n_src) - 1)
-
-
-def _hint_prepare_check(hints, flip, out_size):
-    if not (torch.is_tensor(hints) and hints.dtype == torch.float32 and hints.dim() == 4 and hints.shape[1] == 1 and hints.numel() > 0):
-        raise RuntimeError("depth_hint_prepare: hints must be a non-empty float32 tensor [B, 1, Hs, Ws]; got %s %s"
-                           % (getattr(hints, "dtype", type(hints)), tuple(getattr(hints, "shape", ()))))
-    out_size = tuple(int(v) for v in out_size)
-    if len(out_size) != 2 or out_size[0] < 1 or out_size[1] < 1:
-        raise RuntimeError("depth_hint_prepare: out_size must be a positive (h, w); got %s" % (out_size,))
-    B = int(hints.shape[0])
-    if flip is not None:
-        n = flip.numel() if torch.is_tensor(flip) else len(flip)
-        if n != B:
-            raise RuntimeError("depth_hint_prepare: flip must have one entry per item (%d); got %d" % (B, n))
-    return B, int(hints.shape[2]), int(hints.shape[3]), out_size[0], out_size[1]
-
-
-def depth_hint_prepare_host(hints, flip, out_size):
-    """depth-hints/datasets/mono_dataset.py:382-388 for a batch in numpy: np.fliplr of the flipped items, OpenCV's INTER_NEAREST
-    to ``out_size`` (``cv_nearest_index``), the mask (hint > 0).  Returns (depth_hint, depth_hint_mask) float32 [B, 1, H, W]."""
-    B, Hs, Ws, H, W = _hint_prepare_check(hints, flip, out_size)
-    src = hints.detach().cpu().numpy()
-    flips = [False] * B if flip is None else [bool(v) for v in (flip.tolist() if hasattr(flip, "tolist") else flip)]
-    yi, xi = cv_nearest_index(Hs, H), cv_nearest_index(Ws, W)
-    out = np.empty((B, 1, H, W), dtype=np.float32)
-    for b in range(B):
-        a = np.fliplr(src[b, 0]) if flips[b] else src[b, 0]
-        out[b, 0] = a[yi][:, xi]
-    hint = torch.from_numpy(out)
-    return hint, (hint > 0).float()
-
-
-def _hint_tables_device(device, Hs, Ws, H, W):
-    def make():
-        return [torch.from_numpy(cv_nearest_index(a, b).astype(np.int32)) for a, b in ((Hs, H), (Ws, W))], None
-    return _hint_table_cache.get((str(device), Hs, Ws, H, W), device, make)[0]
-
-
-def depth_hint_prepare(hints, flip, out_size):
-    """The loader's side of a stored depth hint (depth-hints/datasets/mono_dataset.py:382-388) for a batch in one launch.
-
-    hints     float32 [B, 1, Hs, Ws]: the loaded ``.npy`` files.
-    flip      None, an int32 tensor [B] on the hints' device, or a host sequence of bools: != 0 is np.fliplr before the resize.
-    out_size  (H, W): cv2.resize(..., INTER_NEAREST) to it; at Hs, Ws == H, W a (mirrored) copy.
-    Returns   (depth_hint, depth_hint_mask = (depth_hint > 0).float()), float32 [B, 1, H, W].
-
-    CPU tensors run ``depth_hint_prepare_host``."""
-    B, Hs, Ws, H, W = _hint_prepare_check(hints, flip, out_size)
-    dev = hints.device
-    if dev.type != "cuda":
-        return depth_hint_prepare_host(hints, flip, out_size)
-    flip = _flip_operand("depth_hint_prepare", flip, B, dev)
-    ytab, xtab = _hint_tables_device(dev, Hs, Ws, H, W)
-    hints = _c(hints)
-    hint = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
-    mask = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
-    N.check(_timed("depth_hint_prepare", lambda: N.lib().dmh_depth_hint_prepare(
-        N.ptr(hints), N.ptr(flip), N.ptr(ytab), N.ptr(xtab), H, W, B, Hs, Ws, H, W, N.ptr(hint),
-        N.ptr(mask), N.stream()), B * H * W * 12))
-    return hint, mask
-
-
-# ---------------------------------------------------------------------------------------------------------------- K35
-SGM_MAX_MATCHERS = 16
-SGM_MAX_WIDTH = 4096
-SGM_WORKSPACE_CAP = 2 << 30
-SGM_PC_MAX = 567                    # 3 channels x (126 prefiltered + 255 >> 2 raw): the largest pixel cost
-_SGM_KEYS = ("numDisparities", "blockSize", "P1", "P2", "preFilterCap", "uniquenessRatio", "disp12MaxDiff", "speckleWindowSize",
-             "speckleRange", "minDisparity")
-_SGM_DEFAULTS = dict(disp12MaxDiff=0, minDisparity=0)
-
-
-def _sgm_params(params):
-    """The parameter sets as tuples in ``_SGM_KEYS`` order, each refused where the matcher does not serve it."""
-    if isinstance(params, dict):
-        params = [params]
-    params = list(params)
-    if not 1 <= len(params) <= SGM_MAX_MATCHERS:
-        raise RuntimeError("sgm_disparity: 1 <= N <= %d parameter sets; got %d" % (SGM_MAX_MATCHERS, len(params)))
-    out = []
-    for p in params:
-        unknown = set(p) - set(_SGM_KEYS)
-        if unknown:
-            raise RuntimeError("sgm_disparity: unknown parameter(s) %s; the keys are %s" % (sorted(unknown), list(_SGM_KEYS)))
-        missing = [k for k in _SGM_KEYS if k not in p and k not in _SGM_DEFAULTS]
-        if missing:
-            raise RuntimeError("sgm_disparity: a parameter set lacks %s" % missing)
-        D, b, P1, P2, cap, uniq, d12, spw, spr, mind = t = tuple(int(p.get(k, _SGM_DEFAULTS.get(k, 0))) for k in _SGM_KEYS)
-        if mind != 0:
-            raise RuntimeError("sgm_disparity: minDisparity must be 0; got %d" % mind)
-        if D % 16 != 0 or not 16 <= D <= 256:
-            raise RuntimeError("sgm_disparity: numDisparities must be a multiple of 16 in [16, 256]; got %d" % D)
-        if not 1 <= b <= 3:
-            raise RuntimeError("sgm_disparity: blockSize must be 1, 2 or 3 (radius <= 1, for which int16 sums are exact); got %d" % b)
-        side = 2 * (b // 2) + 1
-        if P1 < 0 or P2 < 0 or 5 * (side * side * SGM_PC_MAX + P2) >= 32767:
-            raise RuntimeError("sgm_disparity: P1, P2 >= 0 and 5 ((2r+1)^2 %d + P2) < 32767 (int16 sums); got P1 %d, P2 %d at "
-                               "blockSize %d" % (SGM_PC_MAX, P1, P2, b))
-        if not 1 <= cap <= 63 or not 0 <= uniq <= 100 or not 0 <= d12 <= 32767 or spw < 0 or not 0 <= spr <= 4096:
-            raise RuntimeError("sgm_disparity: need preFilterCap in [1, 63], uniquenessRatio in [0, 100], disp12MaxDiff in [0, 32767], "
-                               "speckleWindowSize >= 0 and speckleRange in [0, 4096]; got %s" % (dict(zip(_SGM_KEYS, t)),))
-        out.append(t)
-    return out
-
-
-def _sgm_check(base, lookup, params, reverse):
-    if not (torch.is_tensor(base) and base.dtype == torch.uint8 and base.dim() == 4 and base.shape[1] == 3 and base.numel() > 0):
-        raise RuntimeError("sgm_disparity: base must be a non-empty uint8 tensor [B, 3, H, W]; got %s %s"
-                           % (getattr(base, "dtype", type(base)), tuple(getattr(base, "shape", ()))))
-    if not (torch.is_tensor(lookup) and lookup.dtype == torch.uint8 and lookup.shape == base.shape and lookup.device == base.device):
-        raise RuntimeError("sgm_disparity: lookup must be a uint8 tensor of base's shape %s on its device; got %s %s"
-                           % (tuple(base.shape), getattr(lookup, "dtype", type(lookup)), tuple(getattr(lookup, "shape", ()))))
-    B, _, H, W = (int(v) for v in base.shape)
-    plist = _sgm_params(params)
-    if W > SGM_MAX_WIDTH or H > 65535 or B * len(plist) * H * W >= 2 ** 31:
-        raise RuntimeError("sgm_disparity: need W <= %d, H <= 65535 and B N H W < 2^31; got %d x %d x %d x %d"
-                           % (SGM_MAX_WIDTH, B, len(plist), H, W))
-    if reverse is not None:
-        n = reverse.numel() if torch.is_tensor(reverse) else len(reverse)
-        if n != B:
-            raise RuntimeError("sgm_disparity: reverse must have one entry per item (%d); got %d" % (B, n))
-    return B, H, W, plist
-
-
-def _sgm_lo_hi(A):
-    left = np.concatenate([A[..., :1], A[..., :-1]], -1)
-    right = np.concatenate([A[..., 1:], A[..., -1:]], -1)
-    hl, hr = (A + left) >> 1, (A + right) >> 1
-    return np.minimum(A, np.minimum(hl, hr)), np.maximum(A, np.maximum(hl, hr))
-
-
-def _sgm_block_cost(base, lookup, D, r, cap):
-    """Steps 1-3 for one pair: C int32 [H, Wv, D]."""
-    _, H, W = base.shape
-    kinds = []
-    for img in (base.astype(np.int32), lookup.astype(np.int32)):
-        rows = np.pad(img, ((0, 0), (1, 1), (0, 0)), mode="edge")
-        dx = rows[:, :, 2:] - rows[:, :, :-2]                           # [3, H + 2, W - 2]
-        g = np.full(img.shape, cap, dtype=np.int32)
-        g[:, :, 1:W - 1] = np.clip(dx[:, :-2] + 2 * dx[:, 1:-1] + dx[:, 2:], -cap, cap) + cap
-        A = np.concatenate([g, img], 0)                                 # [6, H, W]
-        kinds.append((A,) + _sgm_lo_hi(A))
-    (u, lo_u, hi_u), (v, lo_v, hi_v) = kinds
-    cols = np.arange(D, W)[:, None] - np.arange(D)[None, :]             # [Wv, D]: the lookup column of (x, d)
-    pc = np.zeros((H, W - D, D), dtype=np.int32)
-    for k in range(6):                                                  # g of the three channels, then their bytes
-        a, lo_a, hi_a = (t[k][:, D:, None] for t in (u, lo_u, hi_u))
-        b, lo_b, hi_b = (t[k][:, cols] for t in (v, lo_v, hi_v))
-        bt = np.minimum(np.maximum(0, np.maximum(a - hi_b, lo_b - a)), np.maximum(0, np.maximum(b - hi_a, lo_a - b)))
-        pc += bt if k < 3 else bt >> 2
-    if r == 0:
-        return pc
-    pad = np.pad(pc, ((r, r), (r, r), (0, 0)), mode="edge")
-    Wv = W - D
-    return sum(pad[dy:dy + H, dx:dx + Wv] for dy in range(2 * r + 1) for dx in range(2 * r + 1))
-
-
-def _sgm_step(C, q, P1, P2):
-    """One step of a path for a whole front: C, q [..., D] -> L."""
-    big = np.int32(1 << 28)
-    m = q.min(-1, keepdims=True)
-    down = np.concatenate([np.full_like(q[..., :1], big), q[..., :-1]], -1)
-    up = np.concatenate([q[..., 1:], np.full_like(q[..., :1], big)], -1)
-    return C + np.minimum(np.minimum(q, np.minimum(down, up) + P1), m + P2) - m
-
-
-def _sgm_aggregate(C, P1, P2):
-    H, Wv, D = C.shape
-    S = np.zeros_like(C)
-    for cols in (range(Wv), range(Wv - 1, -1, -1)):                     # from the left, from the right: all rows at once
-        L = None
-        for x in cols:
-            L = C[:, x] if L is None else _sgm_step(C[:, x], L, P1, P2)
-            S[:, x] += L
-    for dx in (-1, 0, 1):                                               # from above: all columns at once
-        L = C[0]
-        S[0] += L
-        for y in range(1, H):
-            q = L if dx == 0 else np.roll(L, -dx, axis=0)               # q[x] = L[x + dx]
-            new = _sgm_step(C[y], q, P1, P2)
-            if dx == -1:
-                new[0] = C[y, 0]
-            elif dx == 1:
-                new[Wv - 1] = C[y, Wv - 1]
-            L = new
-            S[y] += L
-    return S
-
-
-def _sgm_select(S, W, uniq, d12):
-    """Steps 5 and 6: S [H, Wv, D] -> int32 [H, W]."""
-    H, Wv, D = S.shape
-    out = np.full((H, W), -16, dtype=np.int32)
-    d_star = S.argmin(-1)
-    min_s = np.take_along_axis(S, d_star[..., None], -1)[..., 0]
-    far = np.abs(np.arange(D)[None, None, :] - d_star[..., None]) > 1
-    unique = ~((S * (100 - uniq) < 100 * min_s[..., None]) & far).any(-1)
-    sm = np.take_along_axis(S, np.maximum(d_star - 1, 0)[..., None], -1)[..., 0]
-    sp = np.take_along_axis(S, np.minimum(d_star + 1, D - 1)[..., None], -1)[..., 0]
-    den = np.maximum(sm + sp - 2 * min_s, 1)
-    num = (sm - sp) * 16 + den
-    frac = np.sign(num) * (np.abs(num) // (2 * den))                    # C's division
-    value = 16 * d_star + np.where((d_star == 0) | (d_star == D - 1), 0, frac)
-    out[:, D:] = np.where(unique, value, -16)
-    xs = np.broadcast_to(np.arange(D, W)[None, :], (H, Wv))
-    ys = np.broadcast_to(np.arange(H)[:, None], (H, Wv))
-    none = np.int64(1) << 40
-    keys = np.full((H, W), none, dtype=np.int64)
-    np.minimum.at(keys, (ys[unique], (xs - d_star)[unique]), (min_s.astype(np.int64)[unique] << 16) | xs[unique])
-    owner = np.where(keys == none, D, keys & 0xffff).astype(np.int64)   # the proposer's column (D where nobody proposed)
-    disp2 = np.take_along_axis(d_star, owner - D, 1)
-    is_set = keys != none
-    xa = np.broadcast_to(np.arange(W)[None, :], (H, W))
-    bad = np.zeros((H, W), dtype=np.int32)
-    for k in (0, 15):
-        dd = (out + k) >> 4
-        x2 = xa - dd
-        inside = (x2 >= 0) & (x2 < W)
-        x2c = np.clip(x2, 0, W - 1)
-        hit = inside & np.take_along_axis(is_set, x2c, 1) & (np.abs(np.take_along_axis(disp2, x2c, 1) - dd) > d12)
-        bad += hit
-    out[(out >= 0) & (bad == 2)] = -16
-    return out
-
-
-def _sgm_speckle(disp, window, rng16):
-    """Step 7 by label propagation with pointer jumping; components do not depend on the order."""
-    H, W = disp.shape
-    valid = disp >= 0
-    lab = np.arange(H * W, dtype=np.int64).reshape(H, W)
-    right = valid[:, :-1] & valid[:, 1:] & (np.abs(disp[:, :-1] - disp[:, 1:]) <= rng16)
-    down = valid[:-1] & valid[1:] & (np.abs(disp[:-1] - disp[1:]) <= rng16)
-    while True:
-        new = lab.copy()
-        np.minimum(new[:, :-1], np.where(right, lab[:, 1:], new[:, :-1]), out=new[:, :-1])
-        np.minimum(new[:, 1:], np.where(right, lab[:, :-1], new[:, 1:]), out=new[:, 1:])
-        np.minimum(new[:-1], np.where(down, lab[1:], new[:-1]), out=new[:-1])
-        np.minimum(new[1:], np.where(down, lab[:-1], new[1:]), out=new[1:])
-        flat = new.reshape(-1)
-        for _ in range(4):
-            flat = flat[flat]
-        new = flat.reshape(H, W)
-        if np.array_equal(new, lab):
-            break
-        lab = new
-    sizes = np.bincount(lab[valid], minlength=H * W)
-    out = disp.copy()
-    out[valid & (sizes[lab] <= window)] = -16
-    return out
-
-
-def sgm_disparity_host(base, lookup, params, reverse=None):
-    """K35 in whole-image numpy on the CPU (the path CPU tensors take), bit-equal to the pixel-by-pixel statement of the matcher
-    in tests/sgm_ref.py.  Returns int16 [B, N, H, W]."""
-    B, H, W, plist = _sgm_check(base, lookup, params, reverse)
-    flips = [False] * B if reverse is None else [bool(v) for v in (reverse.tolist() if hasattr(reverse, "tolist") else reverse)]
-    b_np, l_np = base.detach().cpu().numpy(), lookup.detach().cpu().numpy()
-    out = np.full((B, len(plist), H, W), -16, dtype=np.int16)
-    for b in range(B):
-        ib, il = (a[b, :, :, ::-1] if flips[b] else a[b] for a in (b_np, l_np))
-        done = {}
-        for n, (D, blk, P1, P2, cap, uniq, d12, spw, spr, _) in enumerate(plist):
-            key = (D, blk // 2, P1, P2, cap, uniq, d12, spw, spr)
-            if key not in done:
-                disp = np.full((H, W), -16, dtype=np.int32)
-                if W > D:
-                    S = _sgm_aggregate(_sgm_block_cost(ib, il, D, blk // 2, cap), P1, P2)
-                    disp = _sgm_select(S, W, uniq, d12)
-                if spw > 0:
-                    disp = _sgm_speckle(disp, spw, 16 * spr)
-                done[key] = disp[:, ::-1] if flips[b] else disp
-            out[b, n] = done[key]
-    return torch.from_numpy(out)
-
-
-def _sgm_native_params(plist):
-    arr = (N.SgmParams * len(plist))()
-    for i, (D, blk, P1, P2, cap, uniq, d12, spw, spr, mind) in enumerate(plist):
-        arr[i] = N.SgmParams(D, blk, P1, P2, cap, uniq, d12, spw, spr, mind)
-    return arr
-
-
-def sgm_plan(B, H, W, params, workspace_cap=SGM_WORKSPACE_CAP):
-    """(workspace bytes, sequences of launches) of ``sgm_disparity`` for a batch under ``workspace_cap`` bytes; host only."""
-    plist = _sgm_params(params)
-    chunks = C.c_int(0)
-    nbytes = N.lib().dmh_sgm_plan(int(B), int(H), int(W), _sgm_native_params(plist), len(plist), int(workspace_cap), C.byref(chunks))
-    if nbytes < 0:
-        raise RuntimeError("libdmh_hip: " + N.lib().dmh_last_error().decode())
-    return int(nbytes), int(chunks.value)
-
-
-def sgm_disparity(base, lookup, params, reverse=None, workspace_cap=SGM_WORKSPACE_CAP, phases=N.SGM_ALL):
-    """K35: the integer semi-global stereo matcher of DESIGN.md section 3 (K35) for a batch of stereo pairs on the device; every
-    parameter set of ``params`` gives one map.
-
-    base, lookup   uint8 [B, 3, H, W] (``pil_resize(..., want_u8=True).u8``): the view the disparity is for, and the other one.
-    params         a list of at most 16 dicts with the keys of ``precompute_depth_hints.stereo_matcher_params()`` (and optionally
-                   ``disp12MaxDiff``, 0 by default).  numDisparities a multiple of 16 in [16, 256], blockSize <= 3, minDisparity 0.
-    reverse        None, an int32 tensor [B] on base's device, or a host sequence of bools: != 0 where the base image is the right
-                   view (the pair is matched mirrored and the result mirrored back).
-    workspace_cap  bytes the workspace may take (2 GiB by default); the batch is split into sequences of launches that fit.
-    phases         ``N.SGM_ALL``; a subset launches only those phases, for tools/sgm_bench.py (the result is then undefined).
-    Returns        int16 [B, N, H, W]: disparity x 16, -16 where nothing matched -- what ``depth_hint_fuse`` takes.
-
-    CPU tensors run ``sgm_disparity_host``."""
-    B, H, W, plist = _sgm_check(base, lookup, params, reverse)
-    dev = base.device
-    if dev.type != "cuda":
-        return sgm_disparity_host(base, lookup, params, reverse)
-    if reverse is not None and not torch.is_tensor(reverse):
-        reverse = torch.tensor([int(bool(v)) for v in reverse], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-    if reverse is not None and (reverse.dtype != torch.int32 or reverse.device != dev):
-        raise RuntimeError("sgm_disparity: reverse must be an int32 tensor of %d entries on %s" % (B, dev))
-    native = _sgm_native_params(plist)
-    nbytes = N.lib().dmh_sgm_plan(B, H, W, native, len(plist), int(workspace_cap), None)
-    if nbytes < 0:
-        raise RuntimeError("libdmh_hip: " + N.lib().dmh_last_error().decode())
-    base, lookup = _c(base), _c(lookup)
-    out = torch.empty((B, len(plist), H, W), device=dev, dtype=torch.int16)
-    ws = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
-    N.check(_timed("sgm_disparity", lambda: N.lib().dmh_sgm_disparity(
-        N.ptr(base), N.ptr(lookup), N.ptr(None if reverse is None else _c(reverse)), B, H, W, native, len(plist),
-        C.c_void_p(out.data_ptr()), N.ptr(ws), int(nbytes), int(phases), N.stream()), B * H * W * (6 + 2 * len(plist))))
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------------------- K37
-COLORIZE_MODES = {"min_p95": N.COLORIZE_MIN_P95, "zero_ref": N.COLORIZE_ZERO_REF, "min_max": N.COLORIZE_MIN_MAX}
-COLORIZE_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "magma_256.txt")
-ColorizeOut = namedtuple("ColorizeOut", ["rgb", "map", "stats"])
-_colorize_table_host = None
-_colorize_table_cache = _UploadCache(8, "disp_colorize: the first call on a device uploads the colour table; make it once before "
-                                        "capturing a graph")
-
-
-def magma_table():
-    """(matplotlib's magma at 256 entries * 255).astype(uint8) as uint8 [256, 3]: data/magma_256.txt (256 lines "r g b"), written once by
-    tools/make_goldens_colorize.py.  matplotlib is not imported."""
-    global _colorize_table_host
-    if _colorize_table_host is None:
-        with open(COLORIZE_TABLE_PATH) as f:
-            rows = [[int(v) for v in line.split()] for line in f if line.strip() and not line.startswith("#")]
-        if len(rows) != 256 or any(len(r) != 3 or min(r) < 0 or max(r) > 255 for r in rows):
-            raise RuntimeError("%s must hold 256 lines of three bytes" % COLORIZE_TABLE_PATH)
-        _colorize_table_host = np.array(rows, dtype=np.uint8)
-    return _colorize_table_host
-
-
-def percentile_plan(n, q=95):
-    """(lo, hi, g) of ``np.percentile(a, q)`` for a float32 ``a`` of n elements (numpy 2: float32 throughout): the result is
-    ``lerp(sorted[lo], sorted[hi], g)``.  numpy's own expressions (the "linear" method's virtual index ``(n - 1) * quantiles`` and
-    the bounds of ``_get_indexes``), evaluated in float32 as numpy evaluates them -- they depend on n and q only."""
-    n = int(n)
-    if n < 1:
-        raise RuntimeError("percentile_plan: n must be positive; got %d" % n)
-    quant = np.asanyarray(np.true_divide(q, np.float32(100)), dtype=np.float32)
-    if not 0 <= float(quant) <= 1:
-        raise RuntimeError("percentile_plan: q must lie in [0, 100]; got %r" % (q,))
-    vi = np.asanyarray((n - 1) * quant)
-    if vi.dtype != np.float32:
-        raise RuntimeError("percentile_plan: the virtual index left float32 (%s)" % vi.dtype)
-    if vi >= n - 1:
-        return n - 1, n - 1, 0.0
-    if vi < 0:
-        return 0, 0, 0.0
-    lo = np.floor(vi)
-    return int(lo), int(lo) + 1, float(np.float32(vi - lo))
-
-
-def _colorize_panels(panels, n_src):
-    """Panels as (a, b, mode number, ref) tuples; the default is one ``min_p95`` panel per map."""
-    if panels is None:
-        panels = [(i, -1, "min_p95", i) for i in range(n_src)]
-    out = []
-    for i, pn in enumerate(panels):
-        if len(pn) != 4:
-            raise RuntimeError("disp_colorize: a panel is (a, b, mode, ref); got %r" % (pn,))
-        a, b, mode, ref = pn
-        mode = COLORIZE_MODES.get(mode, mode)
-        if mode not in COLORIZE_MODES.values():
-            raise RuntimeError("disp_colorize: mode must be one of %s; got %r" % (sorted(COLORIZE_MODES), pn[2]))
-        a, b, ref = int(a), int(b), int(ref)
-        if not (0 <= a < n_src and -1 <= b < n_src):
-            raise RuntimeError("disp_colorize: panel %d names a map outside the batch of %d: a = %d, b = %d" % (i, n_src, a, b))
-        out.append((a, b, int(mode), ref))
-    if not 1 <= len(out) <= N.COLORIZE_MAX_PANELS:
-        raise RuntimeError("disp_colorize: 1 <= panels <= %d; got %d" % (N.COLORIZE_MAX_PANELS, len(out)))
-    for i, (a, b, mode, ref) in enumerate(out):
-        if mode == N.COLORIZE_ZERO_REF and not 0 <= ref < len(out):
-            raise RuntimeError("disp_colorize: panel %d takes its limit from panel %d, outside the %d panels" % (i, ref, len(out)))
-    return out
-
-
-def _colorize_check(maps, panels, out_size, out, origins):
-    if not (torch.is_tensor(maps) and maps.dtype == torch.float32 and maps.dim() == 3 and maps.numel() > 0):
-        raise RuntimeError("disp_colorize: maps must be a non-empty float32 tensor [B, h, w]; got %s %s"
-                           % (getattr(maps, "dtype", type(maps)), tuple(getattr(maps, "shape", ()))))
-    B, h, w = (int(v) for v in maps.shape)
-    H, W = (h, w) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    if H < 1 or W < 1:
-        raise RuntimeError("disp_colorize: out_size must be a positive (H, W); got %s" % (out_size,))
-    panels = _colorize_panels(panels, B)
-    if (out is None) != (origins is None):
-        raise RuntimeError("disp_colorize: out (a uint8 mosaic [Hm, Wm, 3]) and origins (one (y, x) per panel) go together")
-    offsets, pitch = [i * H * W * 3 for i in range(len(panels))], W * 3
-    if out is not None:
-        if not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.dim() == 3 and out.shape[2] == 3 and out.is_contiguous()
-                and out.device == maps.device):
-            raise RuntimeError("disp_colorize: out must be a contiguous uint8 tensor [Hm, Wm, 3] on the maps' device")
-        Hm, Wm = int(out.shape[0]), int(out.shape[1])
-        if len(origins) != len(panels):
-            raise RuntimeError("disp_colorize: one origin per panel (%d); got %d" % (len(panels), len(origins)))
-        offsets, pitch = [], Wm * 3
-        for y, x in origins:
-            y, x = int(y), int(x)
-            if not (0 <= y and y + H <= Hm and 0 <= x and x + W <= Wm):
-                raise RuntimeError("disp_colorize: a %d x %d panel at (%d, %d) leaves the %d x %d mosaic" % (H, W, y, x, Hm, Wm))
-            offsets.append((y * Wm + x) * 3)
-    return B, h, w, H, W, panels, offsets, pitch
-
-
-def colorize_bytes_host(a, vmin, vmax):
-    """The bytes of ``(ScalarMappable(Normalize(vmin, vmax), 'magma').to_rgba(a)[..., :3] * 255).astype(uint8)`` for a float32
-    array: float32 throughout, the index 0 where 256 x < 0, 255 where 256 x >= 256, trunc(256 x) otherwise."""
-    a, vmin, vmax = np.asarray(a, dtype=np.float32), np.float32(vmin), np.float32(vmax)
-    with np.errstate(all="ignore"):
-        x = np.zeros_like(a) if vmin == vmax else (a - vmin) / (vmax - vmin)
-        xa = x * np.float32(256)
-        idx = np.where(xa < 0, 0, np.where(xa >= 256, 255, np.trunc(xa))).astype(np.int64)
-    return magma_table()[idx]
-
-
-def disp_colorize_host(maps, panels=None, out_size=None, out=None, origins=None, return_map=False, q=95):
-    """K37's numpy twin, the arithmetic stated in csrc/disp_colorize.hip: sort instead of the radix select, numpy's float32 lerp,
-    float32 limits and index, the packaged table.  With ``out_size`` the map is resized by torch's own float32 CPU
-    ``F.interpolate(bilinear, align_corners=False)``, which is NOT bit-equal to the kernel's resize (torch's back ends differ among
-    themselves): colour the kernel's returned map (no ``out_size``) to compare bytes."""
-    B, h, w, H, W, panels, offsets, pitch = _colorize_check(maps, panels, out_size, out, origins)
-    src = maps.detach().cpu().numpy()
-    lo, hi, g = percentile_plan(H * W, q)
-    g = np.float32(g)
-    made, stats = [], np.zeros((len(panels), N.COLORIZE_STATS), dtype=np.float32)
-    for i, (a, b, mode, ref) in enumerate(panels):
-        m = src[a] if b < 0 else np.abs(src[a] - src[b])
-        if (H, W) != (h, w):
-            m = torch.nn.functional.interpolate(torch.from_numpy(np.ascontiguousarray(m))[None, None], (H, W), mode="bilinear",
-                                                align_corners=False)[0, 0].numpy()
-        s = np.sort(m, axis=None)
-        a_lo, a_hi = s[lo], s[hi]
-        d = a_hi - a_lo
-        p = a_hi - d * (1 - g) if g >= 0.5 else a_lo + d * g
-        stats[i] = (s[0], s[-1], a_lo, a_hi, p)
-        made.append(m)
-    rgb = np.empty((len(panels), H, W, 3), dtype=np.uint8)
-    for i, (a, b, mode, ref) in enumerate(panels):
-        vmin, vmax = ((stats[i, 0], stats[i, 4]) if mode == N.COLORIZE_MIN_P95 else
-                      (np.float32(0), stats[ref, 4]) if mode == N.COLORIZE_ZERO_REF else (stats[i, 0], stats[i, 1]))
-        rgb[i] = colorize_bytes_host(made[i], vmin, vmax)
-    if out is not None:
-        view = out.numpy()
-        for i, (y, x) in enumerate(origins):
-            view[int(y):int(y) + H, int(x):int(x) + W] = rgb[i]
-    return ColorizeOut(out if out is not None else torch.from_numpy(rgb), torch.from_numpy(np.stack(made)) if return_map else None,
-                       torch.from_numpy(stats))
-
-
-def disp_colorize(maps, panels=None, out_size=None, out=None, origins=None, return_map=False, q=95):
-    """K37: float maps to magma-coloured bytes, as MD2/test_simple.py:136-156 and the figures of my_utils.py:43-105 make them on
-    the host, in one fixed chain of launches with no host read.
-
-    maps      float32 [B, h, w], finite (disparities).
-    panels    what is coloured: a sequence of (a, b, mode, ref) -- maps[a], or |maps[a] - maps[b]| when b >= 0, with the limits
-              "min_p95" (the panel's own minimum and q-th percentile), "zero_ref" (0 and the percentile of panel ``ref``) or
-              "min_max" (the panel's minimum and maximum).  Default: every map, "min_p95".
-    out_size  (H, W): the source is resized first (bilinear, align_corners=False semantics); default (h, w), the input bits.
-    out, origins  a uint8 mosaic [Hm, Wm, 3] and one (y, x) per panel: the panels are written into their places, nothing else
-              is touched.  Without them a new uint8 [P, H, W, 3].
-    Returns   ColorizeOut(rgb, map, stats): the bytes (``out`` when given), the coloured float maps [P, H, W] with ``return_map``
-              (None otherwise), and float32 [P, 5] = min, max, sorted[lo], sorted[hi], the percentile as ``np.percentile`` gives it.
-
-    CPU tensors run ``disp_colorize_host``."""
-    B, h, w, H, W, panels, offsets, pitch = _colorize_check(maps, panels, out_size, out, origins)
-    dev = maps.device
-    if dev.type != "cuda":
-        return disp_colorize_host(maps, panels, out_size, out, origins, return_map, q)
-    P = len(panels)
-    if P * H * W >= 2 ** 31 or B * h * w >= 2 ** 31:
-        raise RuntimeError("disp_colorize: B h w and panels H W must stay below 2^31; got %d x %d x %d -> %d x %d x %d"
-                           % (B, h, w, P, H, W))
-    lo, hi, g = percentile_plan(H * W, q)
-    table = _colorize_table_cache.get(str(dev), dev, lambda: ([torch.from_numpy(magma_table().copy())], None))[0][0]
-    maps = _c(maps)
-    native = (N.ColorizePanel * P)(*[N.ColorizePanel(a, b, mode, ref, off) for (a, b, mode, ref), off in zip(panels, offsets)])
-    rgb = out if out is not None else torch.empty((P, H, W, 3), device=dev, dtype=torch.uint8)
-    fmap = torch.empty((P, H, W), device=dev, dtype=torch.float32)
-    stats = torch.empty((P, N.COLORIZE_STATS), device=dev, dtype=torch.float32)
-    ws = torch.empty(N.lib().dmh_disp_colorize_ws_size(P), device=dev, dtype=torch.int32)
-    N.check(_timed("disp_colorize", lambda: N.lib().dmh_disp_colorize(
-        N.ptr(maps), B, h, w, native, P, H, W, lo, hi, g, N.ptr(table), N.ptr(fmap), N.ptr(ws), N.ptr(stats), N.ptr(rgb),
-        rgb.numel(), pitch, N.stream()), 4 * P * (4 * H * W + h * w) + 3 * P * H * W))
-    return ColorizeOut(rgb, fmap if return_map else None, stats)
-
-
-# ---------------------------------------------------------------------------------------------------------------- K39
-PseudoLidarOut = namedtuple("PseudoLidarOut", ["points", "offsets"])
-LIDAR_FORMS = {"depth": N.LIDAR_DEPTH, "disp": N.LIDAR_DISP, "net": N.LIDAR_NET}
-LIDAR_BASELINE = 0.54                   # generate_lidar.py:12
-LIDAR_DESC_CACHE = 16
-_lidar_desc_cache = _UploadCache(LIDAR_DESC_CACHE, "pseudo_lidar: the first call with these shapes uploads their descriptors; make it "
-                                                   "once before capturing a graph")      # (device, form, shapes, offsets) -> tables
-
-
-def lidar_calib(path_or_text, crop=None):
-    """The 27 float64 values K39 takes for one frame -- f_u f_v c_u c_v b_x b_y, inv(R0), C2V -- from a KITTI-object calibration
-    file (or its text), made as the reference's ``Calibration.__init__`` makes them (datasets/kitti_object.py).
-    ``crop=(left, top)``: the scene was cropped by that many pixels; c_u and c_v move with it, nothing else does."""
-    from .datasets.kitti_object import Calibration
-    return Calibration(path_or_text, crop).packed()
-
-
-def _lidar_shapes(shapes, n):
-    shapes = tuple((int(h), int(w)) for h, w in (shapes.tolist() if hasattr(shapes, "tolist") else shapes))
-    if n < 1 or len(shapes) != n or not all(h >= 0 and w >= 0 and h * w < 2 ** 31 for h, w in shapes):
-        raise RuntimeError("pseudo_lidar: shapes must be n >= 1 pairs (H, W) with H, W >= 0, one per frame (%d); got %s" % (n, shapes))
-    return shapes
-
-
-def _lidar_offsets(form, shapes, offsets, src_len):
-    """The first element of every frame of a packed depth / disp input (K32's cell offsets); default: one map after the other."""
-    if form == "net":
-        if offsets is not None:
-            raise RuntimeError("pseudo_lidar: offsets belong to the packed depth / disp forms")
-        return None
-    if offsets is None:
-        offsets = np.cumsum([0] + [h * w for h, w in shapes])
-    offsets = tuple(int(v) for v in (offsets.tolist() if hasattr(offsets, "tolist") else offsets))
-    if len(offsets) not in (len(shapes), len(shapes) + 1) or any(o < 0 or o + h * w > src_len for o, (h, w) in zip(offsets, shapes)):
-        raise RuntimeError("pseudo_lidar: offsets must place every frame's H W values inside the %d values given; got %s for %s"
-                           % (src_len, offsets, shapes))
-    return offsets[:len(shapes)]
-
-
-def _lidar_lin_axis(dst, src):
-    """K25's lin_axis for every destination index of one axis: (s0, s1, f), f float32 (OpenCV's INTER_LINEAR coordinates)."""
-    scale = float(src) / float(dst)
-    f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
-    s = np.floor(f).astype(np.int64)
-    f = f - s.astype(np.float32)
-    lo, hi = s < 0, s >= src - 1
-    s = np.where(lo, 0, np.where(hi, src - 1, s))
-    f = np.where(lo | hi, np.float32(0), f).astype(np.float32)
-    return s, np.minimum(s + 1, src - 1), f
-
-
-def lidar_net_depth_host(disp, H, W, quantise=False):
-    """The net form's depth of one frame, float32 [H, W], from the sigmoid output [h, w]: disp_to_depth's scaling in fp32, the
-    bilinear resize, 5.4 / disp, evaluate's clamp and with ``quantise`` the 16-bit PNG round trip -- every operation a rounded
-    float32 one, in the kernel's order."""
-    disp = np.asarray(disp, dtype=np.float32)
-    h, w = disp.shape
-    with np.errstate(all="ignore"):
-        taps = np.float32(1.0 / 100.0) + np.float32(1.0 / 0.1 - 1.0 / 100.0) * disp
-        sx, sx1, fx = _lidar_lin_axis(W, w)
-        sy, sy1, fy = _lidar_lin_axis(H, h)
-        a0, a1 = np.float32(1) - fx, fx
-        b0, b1 = (np.float32(1) - fy)[:, None], fy[:, None]
-        rows = a0 * taps[:, sx] + a1 * taps[:, sx1]
-        small = b0 * rows[sy] + b1 * rows[sy1]
-        depth = (np.float32(1) / small) * np.float32(5.4)
-        depth = np.where(depth < np.float32(1e-3), np.float32(1e-3), depth)
-        depth = np.where(depth > np.float32(80), np.float32(80), depth)
-        if quantise:
-            q = depth * np.float32(256)
-            k = np.where(np.isnan(q), np.float32(0), q).astype(np.uint16)
-            depth = k.astype(np.float32) / np.float32(256)
-    return depth.astype(np.float32)
-
-
-def _lidar_frame_host(cal, H, W, d, keep, max_high):
-    """project_image_to_velo and the validity test on the candidates of one frame: ``d`` float64 [H W] in pixel order, ``keep`` the
-    candidate mask (None: all).  Element-wise float64 in the kernel's association; never ``np.dot``."""
-    p = np.arange(H * W, dtype=np.int64) if keep is None else np.nonzero(keep)[0]
-    v, u = (p // max(W, 1)).astype(np.float64), (p % max(W, 1)).astype(np.float64)
-    d = d[p]
-    f_u, f_v, c_u, c_v, b_x, b_y = (float(c) for c in cal[:6])
-    Ri, Cm = cal[6:15].reshape(3, 3), cal[15:27].reshape(3, 4)
-    with np.errstate(all="ignore"):
-        x = ((u - c_u) * d) / f_u + b_x
-        y = ((v - c_v) * d) / f_v + b_y
-        z = d
-        r = [(Ri[i, 0] * x + Ri[i, 1] * y) + Ri[i, 2] * z for i in range(3)]
-        o = [((Cm[i, 0] * r[0] + Cm[i, 1] * r[1]) + Cm[i, 2] * r[2]) + Cm[i, 3] for i in range(3)]
-        valid = (o[0] >= 0) & (o[2] < max_high)                 # a NaN fails either comparison
-        rows = np.stack([o[0][valid], o[1][valid], o[2][valid], np.ones(int(valid.sum()))], axis=1).astype(np.float32)
-    return rows
-
-
-def pseudo_lidar_host(src, form, shapes, calib, max_high=1, quantise=False, offsets=None):
-    """K39 in numpy, the definition the kernel is held to (and the path CPU tensors take).  ``src``: float32, the packed maps of
-    the depth / disp forms (frame f at ``offsets[f]``) or the network's output [n, h, w] of the net form.  ``calib``: float64
-    [n, 27].  Returns (float32 [M, 4], int64 [n + 1]): the kept rows of all frames in batch order and pixel order, and where each
-    frame's rows start."""
-    if form not in LIDAR_FORMS:
-        raise RuntimeError("pseudo_lidar: form must be one of %s; got %r" % (sorted(LIDAR_FORMS), form))
-    src = np.asarray(src, dtype=np.float32)
-    n = src.shape[0] if form == "net" else len(shapes)
-    if form == "net" and src.ndim != 3:
-        raise RuntimeError("pseudo_lidar: the net form takes [n, h, w]; got %s" % (src.shape,))
-    if quantise and form != "net":
-        raise RuntimeError("pseudo_lidar: quantise belongs to the net form")
-    shapes = _lidar_shapes(shapes, n)
-    calib = np.asarray(calib, dtype=np.float64).reshape(n, N.LIDAR_CALIB)
-    starts = _lidar_offsets(form, shapes, offsets, src.size)
-    flat = src.reshape(-1)
-    max_high = float(max_high)
-    clouds = []
-    for f, (H, W) in enumerate(shapes):
-        cal, keep = calib[f], None
-        if H * W == 0:
-            clouds.append(np.zeros((0, 4), dtype=np.float32))
-            continue
-        if form == "net":
-            d = lidar_net_depth_host(src[f], H, W, quantise).reshape(-1).astype(np.float64)
-        else:
-            m = flat[starts[f]:starts[f] + H * W]
-            if form == "depth":
-                d = m.astype(np.float64)
-            else:
-                with np.errstate(all="ignore"):
-                    s = np.where(m < 0, np.float32(0), m)       # a NaN stays and fails the mask
-                    keep = s > 0
-                    d = (cal[0] * LIDAR_BASELINE) / ((s.astype(np.float64) + 1.) - keep.astype(np.float64))
-        clouds.append(_lidar_frame_host(cal, H, W, d, keep, max_high))
-    counts = np.array([0] + [c.shape[0] for c in clouds], dtype=np.int64)
-    return np.concatenate(clouds).reshape(-1, 4), np.cumsum(counts)
-
-
-def _lidar_tables_device(device, form, shapes, starts):
-    def make():
-        tiles = [(h * w + N.LIDAR_TILE - 1) // N.LIDAR_TILE for h, w in shapes]
-        first = np.cumsum([0] + tiles)
-        desc = [[h, w, 0 if starts is None else starts[i], int(first[i])] for i, (h, w) in enumerate(shapes)]
-        tile_frame = np.repeat(np.arange(len(shapes)), tiles)
-        if tile_frame.size == 0:
-            tile_frame = np.array([-1])                         # never read: a launch has n_tiles = 0
-        return [torch.tensor(desc, dtype=torch.int32), torch.from_numpy(tile_frame.astype(np.int32))], int(first[-1])
-    (desc, tile_frame), n_tiles = _lidar_desc_cache.get((str(device), form, shapes, starts), device, make)
-    return desc, tile_frame, n_tiles
-
-
-def pseudo_lidar(src, form, shapes, calib, max_high=1, quantise=False, offsets=None):
-    """K39: maps of a batch of frames to velodyne-frame point clouds, as the reference's preprocessing/generate_lidar.py makes them
-    on the host (``project_depth_to_points`` / ``project_disp_to_points`` over ``Calibration.project_image_to_velo``), float32-equal,
-    in three launches with no host read.
-
-    src      float32.  ``form`` "depth": metric depth maps packed flat, frame f's H W values at ``offsets[f]`` (K32's layout; default
-             one map after the other); every pixel is a candidate.  "disp": the same layout of disparities in pixels; negatives
-             count as 0 and only pixels with a positive disparity are candidates.  "net": the network's sigmoid output [n, h, w]
-             (or [n, 1, h, w]); per frame it is scaled (disp_to_depth(., 0.1, 100)), resized to (H, W) as evaluate resizes it,
-             turned into 5.4 / disp, clamped to [1e-3, 80], and with ``quantise`` rounded down to 1 / 256 as a 16-bit PNG stores it.
-    shapes   n pairs (H, W): each frame's own size.  Host values: they size the launch.
-    calib    float64 [n, 27] on src's device: ``lidar_calib`` of every frame.
-    max_high a point is kept if its velodyne x >= 0 and z < max_high.
-    Returns  PseudoLidarOut(points, offsets): float32 [sum H W, 4], the kept rows (x, y, z, 1) of all frames in batch order, each
-             frame's in row-major pixel order, and int64 [n + 1] on the device: frame f is points[offsets[f]:offsets[f + 1]].
-             Rows from offsets[n] on are unspecified.
-
-    CPU tensors run ``pseudo_lidar_host``, the numpy restatement the kernel is bit-equal to."""
-    if form not in LIDAR_FORMS:
-        raise RuntimeError("pseudo_lidar: form must be one of %s; got %r" % (sorted(LIDAR_FORMS), form))
-    if not torch.is_tensor(src) or src.dtype != torch.float32:
-        raise RuntimeError("pseudo_lidar: src must be a float32 tensor; got %s" % (getattr(src, "dtype", type(src)),))
-    if form == "net":
-        if src.dim() == 4 and src.shape[1] == 1:
-            src = src[:, 0]
-        if src.dim() != 3 or src.shape[1] < 1 or src.shape[2] < 1:
-            raise RuntimeError("pseudo_lidar: the net form takes [n, h, w] or [n, 1, h, w]; got %s" % (tuple(src.shape),))
-        n, h, w = (int(v) for v in src.shape)
-    else:
-        if quantise:
-            raise RuntimeError("pseudo_lidar: quantise belongs to the net form")
-        if src.dim() != 1:
-            raise RuntimeError("pseudo_lidar: the %s form takes the maps packed flat; got %s" % (form, tuple(src.shape)))
-        n, h, w = len(shapes), 0, 0
-    shapes = _lidar_shapes(shapes, n)
-    if not torch.is_tensor(calib) or calib.dtype != torch.float64 or calib.numel() != N.LIDAR_CALIB * n:
-        raise RuntimeError("pseudo_lidar: calib must be a float64 tensor of %d x %d entries; got %s %s"
-                           % (n, N.LIDAR_CALIB, getattr(calib, "dtype", type(calib)), tuple(getattr(calib, "shape", ()))))
-    dev = src.device
-    if calib.device != dev:
-        raise RuntimeError("pseudo_lidar: src and calib must share a device; got %s and %s" % (dev, calib.device))
-    starts = _lidar_offsets(form, shapes, offsets, src.numel())
-    cap = sum(hh * ww for hh, ww in shapes)
-    if cap >= 2 ** 31 or src.numel() >= 2 ** 31:
-        raise RuntimeError("pseudo_lidar: the batch must hold fewer than 2^31 pixels; got %d" % cap)
-    if dev.type != "cuda":
-        pts, off = pseudo_lidar_host(src.numpy(), form, shapes, calib.numpy(), max_high, quantise, starts)
-        points = torch.zeros((cap, 4), dtype=torch.float32)
-        points[:pts.shape[0]] = torch.from_numpy(pts)
-        return PseudoLidarOut(points, torch.from_numpy(off))
-    desc, tile_frame, n_tiles = _lidar_tables_device(dev, form, shapes, starts)
-    src, calib = _c(src), _c(calib)
-    ws = torch.empty(2 * max(n_tiles, 1), device=dev, dtype=torch.int32)
-    points = torch.empty((cap, 4), device=dev, dtype=torch.float32)
-    off = torch.empty(n + 1, device=dev, dtype=torch.int64)
-    N.check(_timed("pseudo_lidar", lambda: N.lib().dmh_pseudo_lidar(
-        N.ptr(src) if src.numel() else None, src.numel(), LIDAR_FORMS[form], h, w, int(bool(quantise)), N.ptr_f64(calib), N.ptr(desc),
-        N.ptr(tile_frame), n, n_tiles, float(max_high), N.ptr(ws), N.ptr(points) if cap else None, cap, C.c_void_p(off.data_ptr()),
-        N.stream()), 2 * 4 * src.numel() + 16 * cap))
-    return PseudoLidarOut(points, off)
-
-
-def lidar_clouds(out):
-    """The clouds of a ``PseudoLidarOut`` on the host, one float32 [M_f, 4] array per frame: the n + 1 offsets are read first (they
-    say how many rows are in use), then only those rows are copied."""
-    off = out.offsets.cpu().numpy()
-    used = out.points[:int(off[-1])].cpu().numpy()
-    return [used[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]

@@ -13,6 +13,7 @@ from depthmodelhardening_amd.physicalTrans import PhysicalTrans, get_perspective
 from oracle import attack_ref, synth, tv082
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OPS_LEAVES = ("_launch", "attack_ops", "eval_ops", "data_ops")      # the modules whose names ops.py re-exports
 
 
 def test_quads_match_reference_golden(golden):
@@ -517,10 +518,11 @@ def test_environment_switches_are_the_documented_ones():
 def test_one_launch_site_per_kernel_behind_ops_and_library():
     """torch.ops.dmh.* (library.py) and the autograd Functions (ops.py) launch through the same launchers: library.py makes no call
     into the C library of its own, and each C entry point of the older kernels (K1-K6, the stand-alone layers) and of the 3x3
-    convolution family (K10, K11, K13, K16, K17, K18) is called at one place in ops.py -- a change of a C signature or of a
-    workspace size is made once."""
+    convolution family (K10, K11, K13, K16, K17, K18) is called at one place in ops.py and the modules it re-exports, taken
+    together -- a change of a C signature or of a workspace size is made once."""
     pkg = os.path.join(REPO, "depthmodelhardening_amd")
-    ops_text, lib_text = open(os.path.join(pkg, "ops.py")).read(), open(os.path.join(pkg, "library.py")).read()
+    ops_text = "".join(open(os.path.join(pkg, m + ".py")).read() for m in ("ops",) + OPS_LEAVES)
+    lib_text = open(os.path.join(pkg, "library.py")).read()
     assert "N.lib()" not in lib_text and "C.byref" not in lib_text and "import ctypes" not in lib_text
     assert re.findall(r"\bdmh_\w+\(", lib_text) == []
     for name in ("dmh_photo_loss_fwd", "dmh_photo_loss_bwd", "dmh_photo_loss_bwd_pose", "dmh_smooth_loss_fwd", "dmh_smooth_loss_bwd",
@@ -531,3 +533,28 @@ def test_one_launch_site_per_kernel_behind_ops_and_library():
                  "dmh_wino_conv3x3_ws", "dmh_wino32_conv3x3_ws", "dmh_wino_conv3x3_act", "dmh_wino_conv3x3_act_ws", "dmh_conv3x3_small",
                  "dmh_conv3x3_head", "dmh_conv3x3_head_bwd_data", "dmh_conv3x3_head_wrw", "dmh_conv3x3_small_wrw", "dmh_wino_wrw"):
         assert len(re.findall(r"\b%s\(" % name, ops_text)) == 1, name
+
+
+def test_ops_is_the_one_namespace_of_its_leaf_modules():
+    """ops.py re-exports _launch.py and the attack, eval and loader modules: every name one of them defines is an attribute of
+    ops and the same object, so an operator added to a leaf cannot be forgotten.  The profile state is the exception -- it is
+    rebound in _launch, and ops must hold no copy that could go stale.  No leaf imports ops: they stay leaves."""
+    import ast
+    import importlib
+    from depthmodelhardening_amd import ops
+    for leaf in OPS_LEAVES:
+        module = importlib.import_module("depthmodelhardening_amd." + leaf)
+        names = [k for k in vars(module) if not k.startswith("__")]
+        assert names and getattr(ops, leaf) is module
+        for k in names:
+            if k in ("_profile", "_profile_only"):
+                assert leaf == "_launch" and not hasattr(ops, k), k
+            else:
+                assert getattr(ops, k, None) is getattr(module, k), (leaf, k)
+        imported = set()
+        for node in ast.walk(ast.parse(open(module.__file__).read())):        # imports inside functions too
+            if isinstance(node, ast.Import):
+                imported.update(a.name for a in node.names)
+            elif isinstance(node, ast.ImportFrom):
+                imported.update([node.module or ""] + ["%s.%s" % (node.module or "", a.name) for a in node.names])
+        assert not [m for m in imported if m.split(".")[-1] == "ops"], leaf
