@@ -120,6 +120,25 @@ __device__ __forceinline__ float lane_next(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
 }
 
+// sum + p[0] + p[stride] + ... + p[(n - 1) stride], added in exactly that order (T = float or a float vector: elementwise).
+// The weight-gradient kernels leave one partial per workgroup, tens of KB apart, and their reduce kernels walk such chains.
+// A plain `for (s < n) sum += p[s * stride]` issues its loads as far ahead as the compiler unrolls a loop of unknown length
+// (little), so the chain ran at memory latency x n.  Here NB independent loads are issued into registers, then added in
+// order; the tail takes batches of NB / 2, NB / 4, ... 1, each at most once.
+template <typename T, int NB>
+__device__ __forceinline__ T chain_sum(const T* __restrict__ p, const size_t stride, int n, T sum) {
+    for (; n >= NB; n -= NB, p += (size_t)NB * stride) {
+        T v[NB];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) v[i] = p[(size_t)i * stride];
+        __builtin_amdgcn_sched_barrier(0);      // (left alone, the scheduler sinks every load to its add: one in flight)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) sum += v[i];
+    }
+    if constexpr (NB > 1) return chain_sum<T, NB / 2>(p, stride, n, sum);
+    return sum;
+}
+
 // Philox4x32-R counter-based generator (Salmon et al., SC'11); 7 rounds pass BigCrush.
 template <int ROUNDS = 7>
 struct Philox {

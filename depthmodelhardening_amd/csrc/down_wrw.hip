@@ -11,7 +11,9 @@
 //     (image, output row, 32 output pixels); wave (kq, cq) holds its 32 x 32 quadrant of the ten blocks in 160 accumulator
 //     registers for the whole slice;
 //   * per pixel pair: D_t[k][c] += G[k][2 px] X_t[2 px][c] on v_mfma_f32_32x32x2_f32 -- two gradient reads, nine input reads,
-//     ten MFMAs; tiles of g3 / gd (64 x 32) and x (64 channels x 3 rows x 68 columns, zero outside the image) in LDS, the
+//     ten MFMAs (the compiler pairs the reads over the loop's four unrolled pixel pairs: 22 ds_read2_b32 per 40 MFMAs, and the
+//     staging stores as ds_write2_b32; 16-byte stores would need a plane pitch that is a multiple of 4 floats, which puts the
+//     32 channels of an operand read on 8 banks); tiles of g3 / gd (64 x 32) and x (64 channels x 3 rows x 68 columns, zero outside the image) in LDS, the
 //     next tile prefetched into registers while the current one is multiplied;
 //   * one partial block set per workgroup; down_wrw_reduce_kernel adds the slices in order.  No atomics.
 #include "common.hpp"
@@ -146,19 +148,27 @@ __global__ __launch_bounds__(NT) void down_wrw_kernel(const DArgs a) {
 }
 
 // dW3[k][c][t] / dWd[k][c] = sum over the S slices, in order.  Threads run over (tap, k, c) with c fastest: the 84 MB of
-// partials are read in full lines, the (small) filters are written with a stride of nine floats
+// partials are read in full lines, the (small) filters are written with a stride of nine floats.  A thread owns FOUR
+// consecutive c (one 16-byte load per slice, 16 lanes per 256-byte row of a block) and issues its loads in batches of RNB
+// (chain_sum, common.hpp); a tap the caller does not want (the 1x1 without a shortcut gradient) is not read
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int RNB = 16;
 __global__ __launch_bounds__(NT) void down_wrw_reduce_kernel(const float* __restrict__ part, int K, int C, int S,
                                                             float* __restrict__ dw3, float* __restrict__ dwd) {
-    const int e = blockIdx.x * NT + threadIdx.x;
+    const int e4 = blockIdx.x * NT + threadIdx.x;
     const int KC = K * C;
-    if (e >= KC * 10) return;
-    const int t = e / KC, kc = e - t * KC, k = kc / C, c = kc - k * C;
+    if (e4 >= KC / 4 * 10) return;
+    const int e = e4 * 4;
+    const int t = e / KC, kc = e - t * KC, k = kc / C, c = kc - k * C;      // (C is a multiple of 64: c .. c + 3 share k and pair)
+    if (t == 9 && !dwd) return;
     const int pair = (k >> 6) * (C >> 6) + (c >> 6);
     const float* p = part + ((size_t)pair * S * 10 + t) * 4096 + (size_t)(k & 63) * 64 + (c & 63);
-    float sum = 0.f;
-    for (int s = 0; s < S; ++s) sum += p[(size_t)s * 10 * 4096];
-    if (t < 9) dw3[(size_t)kc * 9 + t] = sum;
-    else if (dwd) dwd[kc] = sum;
+    const f32x4 sum = chain_sum<f32x4, RNB>(reinterpret_cast<const f32x4*>(p), 10 * 1024, S, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (t < 9) dw3[(size_t)(kc + j) * 9 + t] = sum[j];
+        else dwd[kc + j] = sum[j];
+    }
 }
 
 int slices_for(int pairs, int ntiles) {
@@ -184,6 +194,7 @@ int dmh_down_wrw(const float* x, const float* g3, const float* gd, int B, int C,
     DMH_REQUIRE(B > 0 && C > 0 && K > 0 && C % 64 == 0 && K % 64 == 0, "both channel counts must be multiples of 64");
     DMH_REQUIRE(H >= 2 && W >= 8 && (H & 1) == 0 && (W & 7) == 0, "input height must be even, width a multiple of 8");
     DMH_REQUIRE((int64_t)B * C * H * W < ((int64_t)1 << 40) && (int64_t)K * C * 10 < ((int64_t)1 << 31), "tensor too large");
+    DMH_REQUIRE(((uintptr_t)workspace & 15) == 0, "the workspace must be 16-byte aligned");
     DArgs a;
     a.x = x; a.g3 = g3; a.gd = gd; a.part = workspace;
     a.B = B; a.C = C; a.K = K; a.H = H; a.W = W; a.Ho = H / 2; a.Wo = W / 2;
@@ -199,7 +210,7 @@ int dmh_down_wrw(const float* x, const float* g3, const float* gd, int B, int C,
     if (configure_dynamic_lds(down_wrw_kernel, smem, configured) != hipSuccess)
         return fail(DMH_ELAUNCH, "%s: cannot raise the dynamic LDS limit", "dmh_down_wrw");
     hipLaunchKernelGGL(down_wrw_kernel, dim3((unsigned)(pairs * a.S)), dim3(NT), smem, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(down_wrw_reduce_kernel, dim3((unsigned)(((int64_t)K * C * 10 + NT - 1) / NT)), dim3(NT), 0,
+    hipLaunchKernelGGL(down_wrw_reduce_kernel, dim3((unsigned)(((int64_t)K * C * 10 / 4 + NT - 1) / NT)), dim3(NT), 0,
                        (hipStream_t)stream, workspace, K, C, a.S, dw3, gd ? dwd : nullptr);
     return check_launch("dmh_down_wrw");
 }

@@ -8,11 +8,14 @@
 // four consecutive pixels of a row per MFMA, the gradient operand shared by the nine taps.  A workgroup stages a
 // TR x 64 pixel tile of g (16 planes) and the matching (TR+2) x 66 tile of x (C planes, zero padding by out-of-range
 // buffer offsets) in LDS with plane pitches == 4 (mod 64) floats, so that the 16 channels x 4 pixels of an operand read
-// hit 64 different banks; every operand is one ds_read_b32 at an immediate offset.  Workgroups are persistent: the
+// hit 64 different banks; every operand is one dword at an immediate offset (the compiler pairs them: the ten operands of a
+// pixel quad and those of its neighbours arrive as ds_read2_b32, 80 per 144 MFMAs).  Workgroups are persistent: the
 // 9 x C/16 accumulator blocks (36 registers per 16 input channels) stay in registers over all tiles of a workgroup, the
 // next tile is fetched into registers while the current one is multiplied, and only at the end the four waves are
 // added in LDS and one partial per workgroup goes to memory; small_wrw_reduce_kernel adds the partials in a fixed
-// order (deterministic, no atomics).
+// order (deterministic, no atomics).  The rows of g are staged as 16-byte words where they are whole words (GV below); the
+// rows of x stay dwords: the decoder's pre-padded inputs are 1026 / 514 floats wide, so every other row starts 8 bytes off
+// a word, and 66-float tile rows in LDS do too.
 #include "common.hpp"
 
 using namespace dmh;
@@ -38,15 +41,19 @@ struct Geo {
     static constexpr int GPLANE = TR * TW + 4;                             // == 4 (mod 64)
     static constexpr int XROWS = C * RH, GROWS = 16 * TR;
     static constexpr int XPW = (XROWS + NWV - 1) / NWV, GPW = GROWS / NWV; // rows per wave
+    static constexpr int GW4 = GROWS * (TW / 4) / NT;                      // 16-byte words of g per thread (GV form)
     static constexpr int XTAIL = (2 * XROWS + NT - 1) / NT;                // the two columns 64, 65 of every x row
     static constexpr int ACC = NCB * 9 * 4;                                // accumulator registers per lane
     static constexpr int TILE_FLOATS = C * XPLANE + 16 * GPLANE;
     static constexpr int RED_FLOATS = NWV * ACC * 64 + NWV * 64;           // the final cross-wave sum reuses the tile memory
     static constexpr int LDS_FLOATS = TILE_FLOATS > RED_FLOATS ? TILE_FLOATS : RED_FLOATS;
     static_assert(GROWS % NWV == 0, "g rows per wave");
+    static_assert(GROWS * (TW / 4) % NT == 0 && TR % 4 == 0, "whole g words per thread; the four rows of a wave's store in one plane");
 };
 
-template <int NCB, int TR>
+// GV: the rows of g are whole aligned 16-byte words (Wo a multiple of 4, g 16-byte aligned): sixteen lanes load a row, a
+// wave four rows per instruction -- a quarter of the dword form's g loads and LDS stores.  The tile in LDS is the same.
+template <int NCB, int TR, bool GV>
 __global__ __launch_bounds__(NT, 2) void small_wrw_kernel(const WArgs a) {
     using G = Geo<NCB, TR>;
     extern __shared__ float lds[];
@@ -65,6 +72,9 @@ __global__ __launch_bounds__(NT, 2) void small_wrw_kernel(const WArgs a) {
     constexpr int GQ_UNROLL = NCB == 1 ? TW / 4 : 4;    // two channel blocks: a full unroll preloads operands past 256 registers
 
     float px[G::XPW], pg[G::GPW], ptail[G::XTAIL];
+    f32x4 pg4[G::GW4];
+    // GV: word (tid & 15) of tile row (tid >> 4) + 16 k = (plane kk0 + (16 / TR) k, row gr0): all but the plane is the thread's own
+    const int gq4 = tid & 15, kk0 = (tid >> 4) / TR, gr0 = (tid >> 4) - kk0 * TR;
     // fetch tile t into registers (zero outside the image / beyond the output)
     auto fetch = [&](const int t) __attribute__((always_inline)) {
         int q = t;
@@ -84,12 +94,21 @@ __global__ __launch_bounds__(NT, 2) void small_wrw_kernel(const WArgs a) {
             const unsigned so = ok ? ((unsigned)c * HW + (unsigned)(iy * a.W)) * 4u : 0u;
             px[k] = ldb(rx, xo | (ok ? 0u : OOB), so);
         }
+        if constexpr (GV) {
+            const bool ok = oy0 + gr0 < a.Ho && ox0 + 4 * gq4 < a.Wo;                 // (a word lies inside or outside the row as a whole)
+            const unsigned vo = ok ? ((unsigned)kk0 * HWo + (unsigned)(gr0 * a.Wo + 4 * gq4)) * 4u : OOB;
+            const unsigned so = (unsigned)(oy0 * a.Wo + ox0) * 4u;                     // wave-uniform
 #pragma unroll
-        for (int k = 0; k < G::GPW; ++k) {
-            const int rr = wv + NWV * k, kk = rr / TR, r = rr - kk * TR, oy = oy0 + r;
-            const bool ok = oy < a.Ho;
-            const unsigned so = ok ? ((unsigned)kk * HWo + (unsigned)(oy * a.Wo)) * 4u : 0u;
-            pg[k] = ldb(rg, go | (ok ? 0u : OOB), so);
+            for (int k = 0; k < G::GW4; ++k)            // (OOB + the plane step stays beyond the buffer: 16 HWo < 2^28 floats)
+                pg4[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, vo + (unsigned)(k * (16 / TR)) * HWo * 4u, so, 0));
+        } else {
+#pragma unroll
+            for (int k = 0; k < G::GPW; ++k) {
+                const int rr = wv + NWV * k, kk = rr / TR, r = rr - kk * TR, oy = oy0 + r;
+                const bool ok = oy < a.Ho;
+                const unsigned so = ok ? ((unsigned)kk * HWo + (unsigned)(oy * a.Wo)) * 4u : 0u;
+                pg[k] = ldb(rg, go | (ok ? 0u : OOB), so);
+            }
         }
 #pragma unroll
         for (int k = 0; k < G::XTAIL; ++k) {
@@ -105,10 +124,16 @@ __global__ __launch_bounds__(NT, 2) void small_wrw_kernel(const WArgs a) {
             const int rr = wv + NWV * k, c = rr / G::RH, r = rr - c * G::RH;
             if (rr < G::XROWS) xt[c * G::XPLANE + r * G::RW + lane] = px[k];
         }
+        if constexpr (GV) {
 #pragma unroll
-        for (int k = 0; k < G::GPW; ++k) {
-            const int rr = wv + NWV * k, kk = rr / TR, r = rr - kk * TR;
-            gt[kk * G::GPLANE + r * TW + lane] = pg[k];
+            for (int k = 0; k < G::GW4; ++k)
+                *reinterpret_cast<f32x4*>(gt + (kk0 + k * (16 / TR)) * G::GPLANE + gr0 * TW + 4 * gq4) = pg4[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < G::GPW; ++k) {
+                const int rr = wv + NWV * k, kk = rr / TR, r = rr - kk * TR;
+                gt[kk * G::GPLANE + r * TW + lane] = pg[k];
+            }
         }
 #pragma unroll
         for (int k = 0; k < G::XTAIL; ++k) {
@@ -173,46 +198,61 @@ __global__ __launch_bounds__(NT, 2) void small_wrw_kernel(const WArgs a) {
 
 // g_w[k][c][tap] = sum over workgroups of part[wg][((cb * 9 + tap) * 4 + (k & 3)) * 64 + (c & 15) + 16 * (k >> 2)],
 // cb = c / 16;  g_b[k] = sum over workgroups and the four pixel slots of part[wg][ACC * 64 + k + 16 * slot].
-// One workgroup per 64 outputs: 64 lanes x 4 groups of workgroup partials, fixed order.
-__global__ __launch_bounds__(NT) void small_wrw_reduce_kernel(const float* __restrict__ part, int nwg, int C,
-                                                              float* __restrict__ g_w, float* __restrict__ g_b) {
-    __shared__ float red[NT];
+// One workgroup per 32 CONSECUTIVE PARTIAL ELEMENTS (one whole 128-byte line per workgroup partial; the last workgroup takes
+// the 16 bias sums): 32 lanes x 4 groups of workgroup partials (group g adds the partials g, g + 4, ... in order, the loads
+// in batches of RNB -- chain_sum, common.hpp), then group 0 adds the four sums as (0 + 1) + (2 + 3); the element's place in
+// the (small) filter is worked out for the store.
+constexpr int RNT = 128, RNB = 32;
+__global__ __launch_bounds__(RNT) void small_wrw_reduce_kernel(const float* __restrict__ part, int nwg, int C,
+                                                               float* __restrict__ g_w, float* __restrict__ g_b) {
+    __shared__ float red[4][32];
     const int P = (C / 16) * 9 * 4 * 64 + 64;
-    const int nout = 16 * C * 9 + 16;
-    const int j = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
+    const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const int i = blockIdx.x * 32 + o;                                  // over the P - 64 filter elements, then the 16 bias sums
+    const int n = nwg > grp ? (nwg - grp + 3) / 4 : 0;                  // partials of this group
+    const bool is_w = i < P - 64, is_b = !is_w && i < P - 48 && g_b;    // (workgroup-uniform but for the idle lanes)
     float s = 0.f;
-    if (j < nout) {
-        if (j < 16 * C * 9) {
-            const int k = j / (C * 9), rem = j - k * (C * 9), c = rem / 9, tap = rem - c * 9;
-            const int idx = (((c >> 4) * 9 + tap) * 4 + (k & 3)) * 64 + (c & 15) + 16 * (k >> 2);
-            for (int w = grp; w < nwg; w += NT / 64) s += part[(size_t)w * P + idx];
-        } else {
-            const int k = j - 16 * C * 9;
-            for (int w = grp; w < nwg; w += NT / 64) {
-                const float* p = part + (size_t)w * P + (P - 64);
-                s += (p[k] + p[k + 16]) + (p[k + 32] + p[k + 48]);
-            }
+    if (is_w) {
+        s = chain_sum<float, RNB>(part + (size_t)grp * P + i, (size_t)4 * P, n, s);
+    } else if (is_b) {
+        const float* p = part + (size_t)grp * P + i;                    // = the partial's bias block + k; slots at + 16, + 32, + 48
+        constexpr int BB = RNB / 4;
+        int w = 0;
+        for (; w + BB <= n; w += BB, p += (size_t)BB * 4 * P) {
+            float v[BB][4];
+#pragma unroll
+            for (int q = 0; q < BB; ++q)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[q][u] = p[(size_t)q * 4 * P + 16 * u];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < BB; ++q) s += (v[q][0] + v[q][1]) + (v[q][2] + v[q][3]);
         }
+        for (; w < n; ++w, p += (size_t)4 * P) s += (p[0] + p[16]) + (p[32] + p[48]);
     }
-    red[threadIdx.x] = s;
+    red[grp][o] = s;
     __syncthreads();
-    if (grp == 0 && j < nout) {
-        const float v = (red[threadIdx.x] + red[threadIdx.x + 64]) + (red[threadIdx.x + 128] + red[threadIdx.x + 192]);
-        if (j < 16 * C * 9)
-            g_w[j] = v;
-        else if (g_b)
-            g_b[j - 16 * C * 9] = v;
+    if (grp == 0) {
+        const float v = (red[0][o] + red[1][o]) + (red[2][o] + red[3][o]);
+        if (is_w) {
+            // i = ((cb * 9 + tap) * 4 + (k & 3)) * 64 + (c & 15) + 16 * (k >> 2)
+            const int u = i >> 6, cb = (u >> 2) / 9, tap = (u >> 2) - cb * 9;
+            const int k = 4 * ((i >> 4) & 3) + (u & 3), c = 16 * cb + (i & 15);
+            g_w[(k * C + c) * 9 + tap] = v;
+        } else if (is_b) {
+            g_b[i - (P - 64)] = v;
+        }
     }
 }
 
 constexpr int MAX_WG = 512;                 // two persistent workgroups per CU
 
-template <int NCB, int TR>
+template <int NCB, int TR, bool GV>
 int launch(WArgs& a, float* g_w, float* g_b, hipStream_t st) {
     using G = Geo<NCB, TR>;
     constexpr size_t smem = (size_t)G::LDS_FLOATS * sizeof(float);
     static std::atomic<uint64_t> configured{0};     // per device, see configure_dynamic_lds
-    if (configure_dynamic_lds(small_wrw_kernel<NCB, TR>, smem, configured) != hipSuccess)
+    if (configure_dynamic_lds(small_wrw_kernel<NCB, TR, GV>, smem, configured) != hipSuccess)
         return fail(DMH_ELAUNCH, "%s: cannot raise the dynamic LDS limit", "dmh_conv3x3_small_wrw");
     a.tx = (a.Wo + TW - 1) / TW;
     a.ty = (a.Ho + TR - 1) / TR;
@@ -220,9 +260,8 @@ int launch(WArgs& a, float* g_w, float* g_b, hipStream_t st) {
     if (tiles >= (1ll << 31)) return fail(DMH_EINVAL, "%s: grid too large", "dmh_conv3x3_small_wrw");
     a.ntiles = (int)tiles;
     const int nwg = (int)(tiles < MAX_WG ? tiles : MAX_WG);
-    hipLaunchKernelGGL((small_wrw_kernel<NCB, TR>), dim3(nwg), dim3(NT), smem, st, a);
-    hipLaunchKernelGGL(small_wrw_reduce_kernel, dim3((16 * a.C * 9 + 16 + 63) / 64), dim3(NT), 0, st, a.part, nwg, a.C, g_w,
-                       g_b);
+    hipLaunchKernelGGL((small_wrw_kernel<NCB, TR, GV>), dim3(nwg), dim3(NT), smem, st, a);
+    hipLaunchKernelGGL(small_wrw_reduce_kernel, dim3(G::ACC * 64 / 32 + 1), dim3(RNT), 0, st, a.part, nwg, a.C, g_w, g_b);
     return check_launch("dmh_conv3x3_small_wrw");
 }
 
@@ -253,8 +292,9 @@ int dmh_conv3x3_small_wrw(const float* x, const float* g, int B, int C, int H, i
     DMH_REQUIRE(a.Ho >= 1 && a.Wo >= 1, "image smaller than the filter");
     DMH_REQUIRE((int64_t)C * H * W < ((int64_t)1 << 28) && (int64_t)16 * a.Ho * a.Wo < ((int64_t)1 << 28),
                 "image too large (32-bit byte offsets)");
-    if (C == 16) return launch<1, 8>(a, g_w, g_b, (hipStream_t)stream);
-    return launch<2, 4>(a, g_w, g_b, (hipStream_t)stream);
+    const bool gv = a.Wo % 4 == 0 && ((uintptr_t)g & 15) == 0;          // whole 16-byte words of g (the kernel's GV form)
+    if (C == 16) return gv ? launch<1, 8, true>(a, g_w, g_b, (hipStream_t)stream) : launch<1, 8, false>(a, g_w, g_b, (hipStream_t)stream);
+    return gv ? launch<2, 4, true>(a, g_w, g_b, (hipStream_t)stream) : launch<2, 4, false>(a, g_w, g_b, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -146,25 +146,33 @@ __global__ __launch_bounds__(NT) void stem_wrw_kernel(const TArgs a) {
         }
 }
 
-// dW[k][tap] = sum over the (workgroup, wave) partials in a fixed order: a workgroup owns 32 consecutive outputs, its eight
-// thread rows each add one eighth of the partials, thread row 0 adds the eight sums
-__global__ __launch_bounds__(NT) void stem_wrw_reduce_kernel(const float* __restrict__ part, int nparts, float* __restrict__ dw) {
+// dW[k][tap] = sum over the (workgroup, wave) partials in a fixed order: a workgroup (one wave) owns one 32-tap row of a
+// partial block, i.e. up to 32 outputs of one k; its eight thread rows each add one eighth of the partials -- a thread four
+// consecutive taps by 16-byte loads, eight lanes one whole 128-byte line per partial, the loads in batches of RNB (chain_sum,
+// common.hpp) --, then 32 threads add the eight sums.  The padding taps 147..159 are neither read nor written.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int RNT = 64, RNB = 32;
+constexpr int PBLK = 2 * NBLK * 1024;                   // floats of one partial
+__global__ __launch_bounds__(RNT) void stem_wrw_reduce_kernel(const float* __restrict__ part, int nparts, float* __restrict__ dw) {
     __shared__ float red[8][32];
-    const int o = threadIdx.x & 31, ch = threadIdx.x >> 5;
-    const int e = blockIdx.x * 32 + o;                  // over 64 * 147 = 294 * 32
-    const int k = e / NTAP, tap = e - k * NTAP;
-    const int t = (k >> 5) * NBLK + (tap >> 5);
-    const float* p = part + (size_t)t * 1024 + (k & 31) * 32 + (tap & 31);
+    const int o = threadIdx.x & 7, ch = threadIdx.x >> 3;
+    const int t = blockIdx.x >> 5, kk = blockIdx.x & 31;                // over the 2 NBLK * 32 rows of a partial
+    const int k = (t / NBLK) * 32 + kk, tap0 = (t % NBLK) * 32;
     const int s0 = (int)((long long)nparts * ch / 8), s1 = (int)((long long)nparts * (ch + 1) / 8);
-    float sum = 0.f;
-    for (int s = s0; s < s1; ++s) sum += p[(size_t)s * (2 * NBLK) * 1024];
-    red[ch][o] = sum;
-    __syncthreads();
-    if (ch == 0) {
-        float tot = red[0][o];
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+    if (tap0 + 4 * o < NTAP) {
+        const float* p = part + (size_t)s0 * PBLK + (size_t)blockIdx.x * 32 + 4 * o;
+        sum = chain_sum<f32x4, RNB>(reinterpret_cast<const f32x4*>(p), PBLK / 4, s1 - s0, sum);
+    }
 #pragma unroll
-        for (int j = 1; j < 8; ++j) tot += red[j][o];
-        dw[e] = tot;
+    for (int j = 0; j < 4; ++j) red[ch][4 * o + j] = sum[j];
+    __syncthreads();
+    const int tap = tap0 + (int)threadIdx.x;
+    if (threadIdx.x < 32 && tap < NTAP) {
+        float tot = red[0][threadIdx.x];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) tot += red[j][threadIdx.x];
+        dw[k * NTAP + tap] = tot;
     }
 }
 
@@ -185,6 +193,7 @@ int dmh_stem_wrw(const float* x, const float* g, int B, int H, int W, float mean
     DMH_REQUIRE(x && g && workspace && dw, "null pointer");
     DMH_REQUIRE(B > 0 && H >= 2 && W >= 8 && (H & 1) == 0 && (W & 7) == 0, "image height must be even, width a multiple of 8");
     DMH_REQUIRE(std > 0.f, "std must be positive");
+    DMH_REQUIRE(((uintptr_t)workspace & 15) == 0, "the workspace must be 16-byte aligned");
     TArgs a;
     a.x = x; a.g = g; a.part = workspace;
     a.B = B; a.H = H; a.W = W; a.Ho = H / 2; a.Wo = W / 2;
@@ -197,8 +206,7 @@ int dmh_stem_wrw(const float* x, const float* g, int B, int H, int W, float mean
     a.inv_std = 1.0f / std;
     const int groups = stem_groups(a.ntiles);
     hipLaunchKernelGGL(stem_wrw_kernel, dim3((unsigned)groups), dim3(NT), 0, (hipStream_t)stream, a);
-    static_assert(64 * NTAP % 32 == 0, "the reduce kernel's workgroups cover the filter exactly");
-    hipLaunchKernelGGL(stem_wrw_reduce_kernel, dim3(64 * NTAP / 32), dim3(NT), 0, (hipStream_t)stream, workspace, groups * 4, dw);
+    hipLaunchKernelGGL(stem_wrw_reduce_kernel, dim3(2 * NBLK * 32), dim3(RNT), 0, (hipStream_t)stream, workspace, groups * 4, dw);
     return check_launch("dmh_stem_wrw");
 }
 

@@ -407,23 +407,26 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 }
 
 // dw[k][c][3][3] = G^T (sum over the slices of dU[.][k][c]) G,  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]; slices in order.
-// A block = 16 consecutive input channels of one output channel x the 16 positions: every thread adds the S slices of its
-// (c, p) (64-byte segments per slice), the 4 x 4 sums meet in LDS and 144 threads form one filter tap each.
-__global__ __launch_bounds__(NT) void wino_wrw_reduce_kernel(const float* __restrict__ ws, int K, int C, int kch, int cch, int nc,
-                                                             int S, float* __restrict__ dw) {
-    __shared__ float su[16][17];                        // [position][channel], padded
-    const int cl = threadIdx.x & 15, p = threadIdx.x >> 4;
-    const int cblocks = C >> 4;
-    const int k = (int)blockIdx.x / cblocks, c = ((int)blockIdx.x - k * cblocks) * 16 + cl;
-    const int pair = (k / kch) * nc + c / cch;
+// A block = 32 consecutive input channels of one output channel (32 divides every block width, so a block lies in one
+// pair) x the 16 positions: a thread adds the S slices of FOUR channels of its position -- eight lanes read one whole
+// 128-byte line per slice, the loads in batches of RNB (chain_sum, common.hpp) --, the 16 x 32 sums meet in LDS and every
+// thread forms filter taps from them.  Per output the additions and their order are those of a one-channel-per-thread walk.
+constexpr int RNT = 128, RNB = 32;
+__global__ __launch_bounds__(RNT) void wino_wrw_reduce_kernel(const float* __restrict__ ws, int K, int C, int kch, int cch, int nc,
+                                                              int S, float* __restrict__ dw) {
+    __shared__ float su[16][33];                        // [position][channel], padded
+    const int l8 = threadIdx.x & 7, p = threadIdx.x >> 3;
+    const int cgroups = C >> 5;
+    const int k = (int)blockIdx.x / cgroups, c0 = ((int)blockIdx.x - k * cgroups) * 32;
+    const int pair = (k / kch) * nc + c0 / cch;
     const size_t blk = (size_t)kch * cch;
-    const float* src = ws + (size_t)pair * S * (16 * blk) + (size_t)p * blk + (size_t)(k % kch) * cch + (c % cch);
-    float s = 0.f;
-    for (int q = 0; q < S; ++q) s += src[(size_t)q * (16 * blk)];
-    su[p][cl] = s;
+    const float* src = ws + (size_t)pair * S * (16 * blk) + (size_t)p * blk + (size_t)(k % kch) * cch + (c0 % cch) + 4 * l8;
+    const f32x4 s = chain_sum<f32x4, RNB>(reinterpret_cast<const f32x4*>(src), 4 * blk, S, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int j = 0; j < 4; ++j) su[p][4 * l8 + j] = s[j];
     __syncthreads();
-    if (threadIdx.x < 144) {
-        const int cc = threadIdx.x / 9, tap = threadIdx.x - cc * 9, r = tap / 3, col = tap - r * 3;
+    for (int i = threadIdx.x; i < 32 * 9; i += RNT) {
+        const int cc = i / 9, tap = i - cc * 9, r = tap / 3, col = tap - r * 3;
         // G^T row r and G column `col`: coefficients over the 4 transform rows / columns
         const float gr[3][4] = {{1.f, 0.5f, 0.5f, 0.f}, {0.f, 0.5f, -0.5f, 0.f}, {0.f, 0.5f, 0.5f, 1.f}};
         float o = 0.f;
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(NT) void wino_wrw_reduce_kernel(const float* __rest
             for (int b = 0; b < 4; ++b) t += su[a * 4 + b][cc] * gr[col][b];
             o += gr[r][a] * t;
         }
-        dw[((size_t)k * C + ((int)blockIdx.x - k * cblocks) * 16 + cc) * 9 + tap] = o;
+        dw[((size_t)k * C + c0) * 9 + i] = o;
     }
 }
 
@@ -510,13 +513,14 @@ int dmh_wino_wrw(const float* x, const float* dy, int B, int C, int K, int H, in
     DMH_REQUIRE(a.Ho >= 2 && a.Wo >= 2 && (a.Ho & 1) == 0 && (a.Wo & 1) == 0, "output height and width must be even");
     DMH_REQUIRE((int64_t)B * C * H * W * 4 <= (int64_t)0xFFFFFF00 && (int64_t)B * K * a.Ho * a.Wo < ((int64_t)1 << 30),
                 "tensor larger than 4 GB (32-bit byte offsets of the buffer loads)");
+    DMH_REQUIRE(((uintptr_t)workspace & 15) == 0, "the workspace must be 16-byte aligned");
     plan(a, kch, cch);
     int rc;
     if (shape == 1) rc = launch<2, 2>(a, (hipStream_t)stream);
     else if (shape == 2) rc = launch<1, 3>(a, (hipStream_t)stream);
     else rc = launch<1, 2>(a, (hipStream_t)stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(wino_wrw_reduce_kernel, dim3((unsigned)(K * (C / 16))), dim3(NT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(wino_wrw_reduce_kernel, dim3((unsigned)(K * (C / 32))), dim3(RNT), 0, (hipStream_t)stream,
                        workspace, K, C, kch, cch, a.nc, a.S, dw);
     return check_launch("dmh_wino_wrw (reduce)");
 }

@@ -418,6 +418,7 @@ int dmh_gt_depth_mse_bwd(const float* disp, const float* disp_gt, const float* o
  *     applied to (x - mean) / std (MD2/networks/resnet_encoder.py:89-90): dw[64][3][7][7] from x[B,3,H,W] and g[B,64,H/2,W/2];
  *     the normalisation is applied while the image tile is staged (zero in the padding), as in K14.  Same reduction scheme.
  *     H even, W a multiple of 8.  workspace: dmh_stem_wrw_workspace_size(B, H, W) floats.
+ *     The workspaces of K20 and K21 must be 16-byte aligned (their reduce passes read them in 16-byte words).
  * ---------------------------------------------------------------------------------- */
 int64_t dmh_down_wrw_workspace_size(int B, int C, int K, int H, int W);
 int dmh_down_wrw(const float* x, const float* g3, const float* gd, int B, int C, int K, int H, int W, float* workspace, float* dw3,
@@ -671,7 +672,8 @@ int dmh_wino32_conv3x3_ws(const float* x, const float* U, const float* bias, int
  *     fp32 MFMA: dw[K][C][3][3] = d/dw sum(dy * corr3x3(zero_pad(x, pad), w)) -- what autograd asks
  *     aten.convolution_backward(dy, x, w, ..., [False, True, False]) for in the train pass (MD2/trainer.py:305-309 backward
  *     through torchvision BasicBlock / MD2/layers.py:127-141 Conv3x3).  x [B,C,H,W], dy [B,K,H+2pad-2,W+2pad-2] (even sizes);
- *     workspace: dmh_wino_wrw_workspace_size(...) floats (per-workgroup partial sums, added in a fixed order: no atomics).
+ *     workspace: dmh_wino_wrw_workspace_size(...) floats, 16-byte aligned (per-workgroup partial sums, added in a fixed order:
+ *     no atomics).
  * ---------------------------------------------------------------------------------- */
 int64_t dmh_wino_wrw_workspace_size(int B, int C, int K, int H, int W, int pad);
 int dmh_wino_wrw(const float* x, const float* dy, int B, int C, int K, int H, int W, int pad, float* workspace, float* dw,
