@@ -20,7 +20,10 @@ The anchored kernels: K10, K11, K15, K16, K17, K18 here, K10's fused epilogues, 
 tests/test_gpu_conv_epilogue.py, and the stem and head convolutions -- K12 (image gradient of conv1), K13 (the disparity heads:
 tile and strip forward, backward-data, weight and bias gradient) and K14 (normalisation + conv1) -- in
 tests/test_gpu_stem_head_anchor.py: every launch form of theirs at the workload's shapes under this bound, and at ragged
-tile / strip edges element by element under a derived rounding bound (tests/util.py: assert_round_bound).
+tile / strip edges element by element under a derived rounding bound (tests/util.py: assert_round_bound).  The glue between
+them has its anchors too: K7 and K9's eval forms in tests/test_gpu_glue_anchor.py, and K9's train-mode BatchNorm kernels (batch
+statistics, running update, the fused backward) and the per-channel sum in tests/test_gpu_bn_train_anchor.py, under this bound
+with the chain term and, where arithmetic is exact or a plain fp32 sum, bit for bit or under assert_round_bound.
 """
 import pytest
 import torch
