@@ -220,6 +220,8 @@ _SIGNATURES = {
     "dmh_disp_colorize": (C.c_int, [_fp] + [C.c_int] * 3 + [C.POINTER(ColorizePanel)] + [C.c_int] * 5 + [C.c_float] + [_fp] * 5
                           + [C.c_int64, C.c_int64, _fp]),
     "dmh_pseudo_lidar": (C.c_int, [_fp, C.c_int64] + [C.c_int] * 4 + [_fp] * 3 + [C.c_int, C.c_int, C.c_double, _fp, _fp, C.c_int64, _fp, _fp]),
+    "dmh_pose_ate": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "dmh_stem_pair_norm_fwd": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _fp, _fp]),
 }
 
 EXPORTS = tuple(sorted(_SIGNATURES))

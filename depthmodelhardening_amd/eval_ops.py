@@ -1,8 +1,9 @@
-"""The evaluation operators: the masked depth errors, the benign KITTI evaluation (K25) and the fused percentile + colour map (K37).
+"""The evaluation operators: the masked depth errors, the benign KITTI evaluation (K25), the fused percentile + colour map (K37)
+and the odometry evaluation's trajectory error (K40) and pair stem (K41).
 ops.py re-exports every name, and callers reach them as ``ops.<name>``.
 
-The depth errors and K25 launch on the device only.  K37 takes CPU tensors too: they run ``disp_colorize_host``, the numpy
-restatement the kernel is held to.
+The depth errors, K25 and K41 launch on the device only.  K37 and K40 take CPU tensors too: they run ``disp_colorize_host`` /
+``pose_ate_host``, the numpy restatements the kernels are held to.
 """
 import functools
 import os
@@ -357,3 +358,136 @@ def disp_colorize(maps, panels=None, out_size=None, out=None, origins=None, retu
         N.ptr(maps), B, h, w, native, P, H, W, lo, hi, g, N.ptr(table), N.ptr(fmap), N.ptr(ws), N.ptr(stats), N.ptr(rgb),
         rgb.numel(), pitch, N.stream()), 4 * P * (4 * H * W + h * w) + 3 * P * H * W))
     return ColorizeOut(rgb, fmap if return_map else None, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------- K40
+POSE_TRACK_LENGTH = 5       # MD2/evaluate_pose.py:118
+PoseAteOut = namedtuple("PoseAteOut", ["ates", "stats"])
+
+
+def gt_local_poses(gt_global):
+    """MD2/evaluate_pose.py:104-114: the KITTI odometry ground truth ``gt_global`` [N + 1, 3, 4] (the rows of ``poses/<seq>.txt``)
+    to the N local poses ``inv(dot(inv(G[i - 1]), G[i]))`` of its 4x4 forms, float64 [N, 4, 4], in the reference's own expression.
+    Once per sequence, on the host: ground-truth preparation, not per-model work."""
+    g = np.asarray(gt_global, dtype=np.float64)
+    if g.ndim != 3 or g.shape[1:] != (3, 4) or g.shape[0] < 2:
+        raise RuntimeError("gt_local_poses: gt_global must be [N + 1, 3, 4] with N >= 1; got %s" % (g.shape,))
+    g = np.concatenate((g, np.zeros((g.shape[0], 1, 4))), 1)
+    g[:, 3, 3] = 1
+    return np.stack([np.linalg.inv(np.dot(np.linalg.inv(g[i - 1]), g[i])) for i in range(1, len(g))])
+
+
+def _pose_ate_check(pred_poses, gt_local, track_length):
+    """The refusals ``pose_ate`` and ``pose_ate_host`` share; returns N.  Arrays and tensors alike."""
+    for name, t, dtype in (("pred_poses", pred_poses, "float32"), ("gt_local", gt_local, "float64")):
+        is_t = torch.is_tensor(t)
+        if not (is_t or isinstance(t, np.ndarray)):
+            raise RuntimeError("pose_ate: %s must be a tensor or an array; got %s" % (name, type(t)))
+        if str(t.dtype).split(".")[-1] != dtype:
+            raise RuntimeError("pose_ate: %s must be %s; got %s" % (name, dtype, t.dtype))
+        if t.ndim != 3 or tuple(t.shape[1:]) != (4, 4):
+            raise RuntimeError("pose_ate: %s must be [N, 4, 4]; got %s" % (name, tuple(t.shape)))
+        if not (t.is_contiguous() if is_t else t.flags["C_CONTIGUOUS"]):
+            raise RuntimeError("pose_ate: %s must be contiguous" % name)
+    if len(pred_poses) != len(gt_local):
+        raise RuntimeError("pose_ate: %d predicted poses but %d ground-truth local poses" % (len(pred_poses), len(gt_local)))
+    if len(pred_poses) == 0:
+        raise RuntimeError("pose_ate: no poses")
+    if isinstance(track_length, bool) or int(track_length) != track_length or track_length < 2:
+        raise RuntimeError("pose_ate: track_length must be an integer >= 2; got %r" % (track_length,))
+    return len(pred_poses)
+
+
+def pose_ate_host(pred_poses, gt_local, track_length=POSE_TRACK_LENGTH):
+    """K40's numpy twin, the reference's loop restated (MD2/evaluate_pose.py:23-46, :116-125): ``dump_xyz`` chains ``np.dot`` from
+    the identity over ``poses[i:i + track_length - 1]`` -- slices that get shorter at the end of the sequence -- and ``compute_ate``
+    aligns by one scale factor and divides the root of the squared error by the point count.  Returns (ates float64 [N], mean,
+    np.std).  No guard on an all-zero prediction: 0 / 0 is NaN here as there."""
+    _pose_ate_check(pred_poses, gt_local, track_length)
+    pred = pred_poses.detach().cpu().numpy() if torch.is_tensor(pred_poses) else pred_poses
+    gt = gt_local.detach().cpu().numpy() if torch.is_tensor(gt_local) else gt_local
+
+    def dump_xyz(transformations):
+        cam_to_world = np.eye(4)
+        xyzs = [cam_to_world[:3, 3]]
+        for t in transformations:
+            cam_to_world = np.dot(cam_to_world, t)
+            xyzs.append(cam_to_world[:3, 3])
+        return np.array(xyzs)
+
+    ates = []
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i in range(len(pred)):
+            pred_xyz = dump_xyz(pred[i:i + track_length - 1])
+            gt_xyz = dump_xyz(gt[i:i + track_length - 1])
+            pred_xyz = pred_xyz + (gt_xyz[0] - pred_xyz[0])[None, :]
+            scale = np.sum(gt_xyz * pred_xyz) / np.sum(pred_xyz ** 2)
+            ates.append(np.sqrt(np.sum((pred_xyz * scale - gt_xyz) ** 2)) / gt_xyz.shape[0])
+    ates = np.array(ates, dtype=np.float64)
+    return ates, float(np.mean(ates)), float(np.std(ates))
+
+
+def pose_ate_launch(pred_poses, gt_local, track_length):
+    """K40's two launches on plain device tensors (what ``pose_ate`` and ``torch.ops.dmh.pose_ate`` share)."""
+    n = _pose_ate_check(pred_poses, gt_local, track_length)
+    _need_cuda(pred_poses)
+    if not torch.is_tensor(gt_local) or gt_local.device != pred_poses.device:
+        raise RuntimeError("pose_ate: pred_poses and gt_local must share a device")
+    if n > 2 ** 24 or track_length > 2 ** 16:
+        raise RuntimeError("pose_ate: at most 2^24 poses and a track_length of 2^16; got %d and %d" % (n, track_length))
+    ates = torch.empty(n, device=pred_poses.device, dtype=torch.float64)
+    stats = torch.empty(2, device=pred_poses.device, dtype=torch.float64)
+    N.check(_timed("pose_ate", lambda: N.lib().dmh_pose_ate(N.ptr(pred_poses), N.ptr_f64(gt_local), n, int(track_length), N.ptr_f64(ates),
+                                                           N.ptr_f64(stats), N.stream()), 192 * n))
+    return ates, stats
+
+
+def pose_ate(pred_poses, gt_local, track_length=POSE_TRACK_LENGTH):
+    """K40: the absolute trajectory error of the KITTI odometry protocol (MD2/evaluate_pose.py:23-46, :116-125) without leaving the
+    device.
+
+    pred_poses   float32 [N, 4, 4]: the predicted relative poses, K29's ``T[:, 0]`` of every frame pair, concatenated.
+    gt_local     float64 [N, 4, 4]: ``gt_local_poses`` of the sequence; a numpy array is uploaded to pred_poses' device.
+    Returns      PoseAteOut(ates float64 [N], stats float64 [2] = mean and np.std of ates), both on the device: nothing is read
+                 back until the caller asks.  Snippets at the end of the sequence are shorter, as the reference's slices are.
+
+    Refused with RuntimeError: lengths that differ, N = 0, track_length < 2, a wrong dtype or a non-contiguous operand.
+    CPU tensors run ``pose_ate_host``, the reference's loop."""
+    _pose_ate_check(pred_poses, gt_local, track_length)
+    if not torch.is_tensor(pred_poses):
+        raise RuntimeError("pose_ate: pred_poses must be a tensor (pose_ate_host takes arrays)")
+    if pred_poses.device.type != "cuda":
+        ates, mean, std = pose_ate_host(pred_poses, gt_local, track_length)
+        return PoseAteOut(torch.from_numpy(ates), torch.tensor([mean, std], dtype=torch.float64))
+    if not torch.is_tensor(gt_local):
+        gt_local = torch.from_numpy(gt_local).to(pred_poses.device, non_blocking=True)
+    return PoseAteOut(*pose_ate_launch(pred_poses, gt_local, int(track_length)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- K41
+def stem_pair_norm(a, b, weight, mean=0.45, std=0.225):
+    """K41: ``conv1((cat([a, b], 1) - mean) / std)`` for the pose encoder's first layer (MD2/evaluate_pose.py:94-96 into
+    MD2/networks/resnet_encoder.py:89-90 with num_input_images = 2: 6 -> 64 channels, 7x7, stride 2, padding 3, no bias) without
+    the concatenation and without the normalised copy.  ``a`` and ``b`` are [B, 3, H, W] with even H and W; they may be overlapping
+    views of one tensor (``f[:-1]`` and ``f[1:]``).  Forward only: a call that would need a gradient is refused."""
+    for name, t in (("a", a), ("b", b), ("weight", weight)):
+        _need_f32(t, name)
+    _need_cuda(a)
+    if (a.dim() != 4 or a.shape[1] != 3 or a.shape != b.shape or a.shape[2] % 2 or a.shape[3] % 2 or a.shape[0] == 0
+            or tuple(weight.shape) != (64, 6, 7, 7)):
+        raise RuntimeError("stem_pair_norm: a and b must be [B,3,H,W] with B >= 1 and even H, W, and weight [64,6,7,7]; got %s, %s, %s"
+                           % (tuple(a.shape), tuple(b.shape), tuple(weight.shape)))
+    if b.device != a.device or weight.device != a.device:
+        raise RuntimeError("stem_pair_norm: a, b and weight must share a device")
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad or weight.requires_grad):
+        raise RuntimeError("stem_pair_norm is forward only (K41 has no backward): call it under torch.no_grad(), or take "
+                           "ResnetEncoder.forward(torch.cat([a, b], 1)), which differentiates")
+    if not std > 0:
+        raise RuntimeError("stem_pair_norm: std must be positive; got %r" % (std,))
+    a, b, weight = _c(a.detach()), _c(b.detach()), _c(weight.detach())
+    B, _, H, W = a.shape
+    y = torch.empty((B, 64, H // 2, W // 2), device=a.device, dtype=torch.float32)
+    N.check(_timed("stem_pair_fwd", lambda: N.lib().dmh_stem_pair_norm_fwd(N.ptr(a), N.ptr(b), N.ptr(weight), B, H, W, float(mean),
+                                                                          float(std), N.ptr(y), N.stream()),
+                   4 * (2 * a.numel() + 3 * y.numel()), 2 * 294 * y.numel()))
+    return y

@@ -48,6 +48,9 @@ the same bits.  There is no CPU kernel behind any of them: CPU tensors are rejec
                               (K37, no autograd)
     dmh::pseudo_lidar         preprocessing/generate_lidar.py:10-33 + kitti_util.py:159-175 (maps to velodyne-frame clouds, float32-equal)
                               (K39, no autograd)
+    dmh::pose_ate             MD2/evaluate_pose.py:23-46,116-125 (dump_xyz, compute_ate, np.mean, np.std in float64)   (K40, no autograd)
+    dmh::stem_pair_norm       MD2/evaluate_pose.py:94-96 + MD2/networks/resnet_encoder.py:89-90 (cat, normalise, the 6 -> 64 conv1)
+                              (K41, forward only)
 """
 from typing import List, Optional, Tuple
 
@@ -813,6 +816,33 @@ def _(src, form, shapes, calib, max_high=1.0, quantise=False, offsets=None):
             src.new_empty((len(shapes) // 2 + 1,), dtype=torch.int64))
 
 
+# ---------------------------------------------------------------------------------------------------------------- K40
+@custom_op("dmh::pose_ate", mutates_args=())
+def pose_ate(pred_poses: torch.Tensor, gt_local: torch.Tensor, track_length: int = 5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ates float64 [N], stats float64 [2] = mean, np.std) of MD2/evaluate_pose.py:116-125 (``ops.pose_ate``).  Errors carry no
+    gradient: there is no autograd formula."""
+    ops._need_cuda(pred_poses)
+    return ops.pose_ate_launch(pred_poses, gt_local, track_length)
+
+
+@pose_ate.register_fake
+def _(pred_poses, gt_local, track_length=5):
+    return gt_local.new_empty((pred_poses.shape[0],)), gt_local.new_empty((2,))
+
+
+# ---------------------------------------------------------------------------------------------------------------- K41
+@custom_op("dmh::stem_pair_norm", mutates_args=())
+def stem_pair_norm(a: torch.Tensor, b: torch.Tensor, weight: torch.Tensor, mean: float = 0.45, std: float = 0.225) -> torch.Tensor:
+    """conv1((cat([a, b], 1) - mean) / std) of the pose encoder (``ops.stem_pair_norm``).  Forward only: there is no autograd
+    formula, and a backward through it raises."""
+    return ops.stem_pair_norm(a, b, weight, mean, std)
+
+
+@stem_pair_norm.register_fake
+def _(a, b, weight, mean=0.45, std=0.225):
+    return a.new_empty((a.shape[0], 64, a.shape[2] // 2, a.shape[3] // 2))
+
+
 def sgm_params_flat(params):
     """A list of parameter dicts as the flat integer list ``torch.ops.dmh.sgm_disparity`` takes."""
     return [int(v) for t in ops._sgm_params(params) for v in t]
@@ -830,4 +860,5 @@ OPS = ("eot_paste", "eot_paste_bwd", "masked_sq_mean", "masked_sq_mean_bwd", "gt
        "apgd_step", "apgd_commit", "l0_fused_step", "tube_light_compose", "tube_light_commit",
        "gauss_blur_windows", "gauss_blur_compose", "square_propose", "pgd_l2_step", "eigen_gt_stats", "eigen_depth_errors", "pose_head", "pose_head_bwd",
        "cost_volume", "cost_volume_into", "cost_volume_stack", "cost_volume_stack_bwd", "pil_resample", "velo_depth_map", "color_jitter", "depth_hint_fuse", "sgm_disparity",
-       "reduce_conv_degenerate", "reduce_conv_degenerate_bwd", "disp_colorize", "pseudo_lidar")
+       "reduce_conv_degenerate", "reduce_conv_degenerate_bwd", "disp_colorize", "pseudo_lidar", "pose_ate",
+       "stem_pair_norm")

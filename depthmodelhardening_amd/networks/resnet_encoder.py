@@ -296,6 +296,30 @@ class ResnetEncoder(nn.Module):
         self.features = [f0, f1, f2, f3, f4]
         return self.features
 
+    def _pair_stem_ok(self, a, b):
+        """K41's conditions: two CUDA fp32 [B,3,H,W] frames with even H and W, the standard six-channel conv1, BatchNorm in eval
+        mode (the fused eval path), and no gradient owed to the frames or to the filter."""
+        e, c = self.encoder, self.encoder.conv1
+        if not (ops.WINO_ENABLED and torch.is_tensor(a) and torch.is_tensor(b) and a.dim() == 4 and a.shape == b.shape
+                and a.shape[1] == 3 and a.shape[0] > 0 and a.shape[2] % 2 == 0 and a.shape[3] % 2 == 0
+                and a.is_cuda and a.device == b.device and a.dtype == torch.float32 and b.dtype == torch.float32):
+            return False
+        if not (tuple(c.weight.shape) == (64, 6, 7, 7) and c.stride == (2, 2) and c.padding == (3, 3) and c.dilation == (1, 1)
+                and c.groups == 1 and c.bias is None and c.weight.dtype == torch.float32 and c.weight.device == a.device):
+            return False
+        if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad or c.weight.requires_grad):
+            return False
+        return e.fused_eval_ok(a)
+
+    def forward_pair(self, a, b):
+        """``forward(torch.cat([a, b], 1))`` for the pose encoder (num_input_images = 2) without the concatenation: the first
+        layer is one K41 call on the two frames (``ops.stem_pair_norm``; a and b may be overlapping views ``f[:-1]``, ``f[1:]``
+        of one tensor), the rest is the fused eval path.  Whenever K41's conditions do not hold it IS that ``forward`` call."""
+        if not self._pair_stem_ok(a, b):
+            return self.forward(torch.cat([a, b], 1))
+        self.features = self._forward_fused_eval(a, stem=ops.stem_pair_norm(a, b, self.encoder.conv1.weight, 0.45, 0.225))
+        return self.features
+
     def _conv1(self, x):
         c = self.encoder.conv1
         if (x.is_cuda and x.dtype == torch.float32 and c.kernel_size == (7, 7) and c.stride == (2, 2)
@@ -323,7 +347,8 @@ class ResnetEncoder(nn.Module):
         return ((a.conv1.weight, aff[a.bn1], a.downsample[0].weight, aff[a.downsample[1]], a.conv2.weight, aff[a.bn2]),
                 (b.conv1.weight, aff[b.bn1], b.conv2.weight, aff[b.bn2]))
 
-    def _forward_fused_eval(self, input_image, roi=None, clean=None):
+    def _forward_fused_eval(self, input_image, roi=None, clean=None, stem=None):
+        """``stem``: conv1's output when the caller has it already (``forward_pair``); the stem is not run then."""
         e = self.encoder
         aff = e.eval_affine()
         if ops.weights_frozen():
@@ -353,7 +378,7 @@ class ResnetEncoder(nn.Module):
                 if feats is None:
                     feats, layers = [f0, y], layers[1:]
         if feats is None:
-            z = self._stem(input_image)
+            z = self._stem(input_image) if stem is None else stem
             if z.shape[2] % 2 == 0 and z.shape[3] % 2 == 0:
                 f0, y = ops.stem_bn_relu_pool(z, *aff[e.bn1])
             else:

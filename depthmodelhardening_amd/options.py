@@ -62,7 +62,8 @@ class MonodepthOptions:
         # LOGGING
         p.add_argument("--log_frequency", type=int, default=250)
         p.add_argument("--save_frequency", type=int, default=1)
-        # EVALUATION (read by evaluate_depth.evaluate; --eval_out_dir belongs to scripts that are out of scope)
+        # EVALUATION (read by evaluate_depth.evaluate; --eval_split odom_9 / odom_10 by evaluate_pose.evaluate; --eval_out_dir
+        # belongs to the benchmark export, which is out of scope)
         p.add_argument("--eval_stereo", action="store_true")
         p.add_argument("--eval_mono", action="store_true")
         p.add_argument("--disable_median_scaling", action="store_true")

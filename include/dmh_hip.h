@@ -1086,6 +1086,32 @@ int dmh_pseudo_lidar(const float* src, int64_t src_len, int form, int h, int w, 
                      const int32_t* desc, const int32_t* tile_frame, int n, int n_tiles, double max_high, int32_t* ws,
                      float* out, int64_t cap, int64_t* offsets, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * K40 Trajectory error of the KITTI odometry protocol: MD2/evaluate_pose.py:23-46 (dump_xyz, compute_ate) and :116-125.
+ *   pred_poses  float [n][4][4]: the predicted relative poses (K29's T), row-major.
+ *   gt_local    double [n][4][4]: the ground truth's local poses, inv(inv(G[i-1]) G[i]) of the global ones.
+ *   Snippet i in [0, n) takes the m = min(track_length - 1, n - i) poses from i on (shorter at the end of the sequence, as the
+ *   reference's slices are), chains C = C . T from the identity in float64, index order, for both, and collects the m + 1
+ *   translations; offset = gt_0 - pred_0, pred += offset, scale = sum(gt pred) / sum(pred^2),
+ *   ates[i] = sqrt(sum((pred scale - gt)^2)) / (m + 1).  sum(pred^2) = 0 gives NaN, as numpy's 0 / 0 does.
+ *   ates        double [n].   stats  double [2]: mean and population standard deviation (np.std) of ates.
+ *     Two launches (one thread per snippet; one workgroup with a fixed-order tree); no atomics, no host read: bitwise
+ *     reproducible, capturable.
+ * ---------------------------------------------------------------------------------- */
+int dmh_pose_ate(const float* pred_poses, const double* gt_local, int n, int track_length, double* ates, double* stats,
+                 void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * K41 The pose encoder's first layer on a pair of frames: y = conv7x7s2p3((cat(a, b) - mean) / std, w), forward only.
+ *   a, b   float [B][3][H][W] each, H and W even; two base pointers that may overlap (frames[:-1] and frames[1:] of one block).
+ *   w      float [64][6][7][7];   y  float [B][64][H/2][W/2], not aliasing an input.
+ *     Two launches of K14's tile kernel (w[:, :3] over a writes y, then w[:, 3:] over b adds into it, with the same tile and lane
+ *     maps); every output is two k-ordered fp32 fma chains of 147 taps and one addition: no atomics, bitwise reproducible,
+ *     capturable.
+ * ---------------------------------------------------------------------------------- */
+int dmh_stem_pair_norm_fwd(const float* a, const float* b, const float* w, int B, int H, int W, float mean, float std, float* y,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
