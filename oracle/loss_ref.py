@@ -35,12 +35,14 @@ def disp_to_depth(disp, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH):
 def backproject(depth, inv_K):
     """layers.py:163-168 -- depth [B,1,H,W], inv_K [B,4,4] -> cam points [B,4,H*W]."""
     B, _, H, W = depth.shape
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=depth.dtype), torch.arange(W, dtype=depth.dtype), indexing="ij")
-    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W, dtype=depth.dtype)], 0)
+    dev = depth.device      # (the tests run this file on the GPU as well, in float32 and float64, where the CPU is too slow)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=depth.dtype, device=dev), torch.arange(W, dtype=depth.dtype, device=dev),
+                            indexing="ij")
+    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(H * W, dtype=depth.dtype, device=dev)], 0)
     pix = pix.unsqueeze(0).repeat(B, 1, 1)
     cam = torch.matmul(inv_K[:, :3, :3], pix)
     cam = depth.view(B, 1, -1) * cam
-    ones = torch.ones(B, 1, H * W, dtype=depth.dtype)
+    ones = torch.ones(B, 1, H * W, dtype=depth.dtype, device=dev)
     return torch.cat([cam, ones], 1)
 
 

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from tests.photo_cases import PIX_ATOL, general_pose as _general_pose  # noqa: E402  (shared with test_gpu_photo_forms.py)
 from tests.util import GradPool, assert_close_frac, np_t, rel_l2, to_dev  # noqa: E402
 
 
@@ -18,12 +19,6 @@ def _mods():
     from depthmodelhardening_amd import _native as N, ops
     from oracle import attack_ref, loss_ref, synth, tv082
     return N, ops, loss_ref, attack_ref, synth, tv082
-
-
-# Per-pixel SSIM values carry fp32 conditioning noise: sigma = E[x^2] - mu^2 cancels ~0.25 - 0.25 down to
-# ~1e-3, so one ulp of the window sums moves (1 - SSIM)/2 by ~1e-5.  Scalars (means over >= 6k pixels) are
-# held to 2e-5 relative; per-pixel maps to 5e-5 absolute.
-PIX_ATOL = 5e-5
 
 
 def _near_tie_exclusion(loss_ref, inputs, outputs, noise, scale, variant, B, H, W, frame_ids=(0, "s")):
@@ -194,23 +189,6 @@ def test_photo_loss_golden_cfg1(golden, name):
             # pixel + delta form ~2e-6) and carries 99 % of HIP's squared error, while the reference's fp32 run flips 94
             # other elements (tools/diag_grad_outliers.py 2 320 1024 23); the pooled form of the rel-L2 bound is
             # test_gradients_within_fp32_conditioning_of_the_fp64_oracle at this shape (three seeds, all elements)
-
-
-def _general_pose(B, seed):
-    """A different rigid transform per sample: rotations of up to ~1 degree about all three axes + a translation."""
-    g = torch.Generator().manual_seed(seed)
-    ang = (torch.rand(B, 3, generator=g, dtype=torch.float64) - 0.5) * 0.03
-    T = torch.eye(4, dtype=torch.float64).repeat(B, 1, 1)
-    for b in range(B):
-        cx, cy, cz = torch.cos(ang[b])
-        sx, sy, sz = torch.sin(ang[b])
-        Rx = torch.tensor([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], dtype=torch.float64)
-        Ry = torch.tensor([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], dtype=torch.float64)
-        Rz = torch.tensor([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]], dtype=torch.float64)
-        T[b, :3, :3] = Rz @ Ry @ Rx
-    T[:, 0, 3], T[:, 1, 3], T[:, 2, 3] = 0.05, 0.01, -0.02
-    T[:, :3, 3] += (torch.rand(B, 3, generator=g, dtype=torch.float64) - 0.5) * 0.02
-    return T
 
 
 def test_photo_loss_two_frames_and_options():
